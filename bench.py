@@ -8,7 +8,7 @@ fp32 end to end.  A "step" = one render() call over `--rays` rays already reside
 Ranks shard views / rays with no data-path collective (gen_geo.py --num_p/--p_i is the reference's own scheme).
 
 --mode train: the timed step is the data-parallel geo TRAINING step instead (2560 rays per rank, forward + backward + Adam,
-one flat-bucket RCCL all-reduce of the gradients per step); `value` is then training rays/s.  In the default render mode a
+one flat-bucket RCCL all-reduce of the gradients per step); `value` is then training rays/s.  With --full, a render-mode
 multi-rank run also times that step and the reflectance (VQ) training step -- gradient bucket + codebook-statistics
 all-reduce -- after the timed render region and reports them under "extra.dp_train" (all-reduce time per step included).
 
@@ -17,10 +17,17 @@ timing windows, per-kernel tables -- is the sidecar gpurun_out/bench_detail.json
 `python bench.py --gpus N` without WORLD_SIZE starts its N ranks itself as a child `python -m torch.distributed.run` (before any
 GPU call) and exits with that child's code; if the data-parallel legs hang, every rank exits 3 after rank 0 printed the render line.
 
+A plain run (no --full) does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs of the last timed
+step if --dump-outputs DIR is given, and the line.  Everything else -- the live roofline.traffic passes, the CPU baselines and PSNR
+checks, the other precisions, the secondary workloads under `extra`, the data-parallel legs and the sidecar -- runs with --full.
+--dump-outputs DIR writes the arrays the timed step returns to its caller (render: the dict of NeuSRenderer.render; train: the
+step's losses and the networks' parameters after it) as DIR/<name>.npy, float32 (float64 for float64 and integer outputs), at most
+64 MB in all: beyond that every array with one row per ray is cut to the same fixed, seeded sample of rows.
+
 Extra objects in the JSON line:
   roofline     -- dominant kernel (vqn_neus_fine_points): algorithmic FLOPs per launch / its average
                   launch duration measured with HIP events on the launch stream, vs the dense f32 MFMA peak
-  cpu_baseline -- the faithful torch-CPU oracle (oracle/geo.py, a port of the reference op sequence) timed
+  cpu_baseline -- (--full) the faithful torch-CPU oracle (oracle/geo.py, a port of the reference op sequence) timed
                   on this host's cores over a bounded sample of the same workload (rank 0, N=1 only): B = 2560 rays spread
                   over the whole image, 1 warm-up + 3 timed calls, median
 """
@@ -1004,6 +1011,33 @@ def live_traffic(rays, timeout_s=170):
         '(DESIGN.md, round 3): the stream is not what bounds the kernel')
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rows, seed=0, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array of `arrays` as dirname/<name>.npy, float32 (float64 for float64 and integer outputs; None entries are
+    skipped).  If the set would exceed `limit` bytes, every array whose leading dimension is `rows` keeps the same fixed, seeded, sorted
+    sample of its rows -- as many as fit -- and the others are written whole.  Returns the names written."""
+    def host_dtype(t):
+        return torch.float64 if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool) else torch.float32
+    ts = {k: (v.detach() if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in arrays.items() if v is not None}
+    size = lambda t: t.numel() * host_dtype(t).itemsize
+    per_row = {k: t for k, t in ts.items() if rows and t.dim() >= 1 and t.shape[0] == rows}
+    fixed = sum(size(t) for k, t in ts.items() if k not in per_row)
+    row_bytes = sum(size(t) for t in per_row.values()) // rows if per_row else 0
+    sel = None
+    if fixed + row_bytes * (rows or 0) > limit:
+        n = (limit - fixed) // row_bytes if row_bytes else 0
+        assert n >= 1, f'--dump-outputs: {fixed} bytes of outputs cannot be cut to {limit}'
+        sel = np.sort(np.random.default_rng(seed).choice(rows, n, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for k, t in ts.items():
+        if sel is not None and k in per_row:
+            t = t[torch.as_tensor(sel, device=t.device)]
+        np.save(os.path.join(dirname, f'{k}.npy'), t.to(host_dtype(t)).cpu().numpy())
+    return list(ts)
+
+
 # ---- the ONE stdout line (driver contract) and its sidecar ----------------------------------------------------------------------------
 # The line carries numbers and short identifiers only and stays under LINE_LIMIT bytes (round 4's 22 KB line was not captured by the
 # driver); every note, sample description, window list and per-kernel table goes to the sidecar file `bench_detail.json`.
@@ -1196,7 +1230,13 @@ def main():
     ap.add_argument('--no-extras', action='store_true', help='skip the secondary workloads (train steps, decomp, VQ)')
     ap.add_argument('--no-traffic', action='store_true', help='do not measure roofline.traffic with child rocprofv3 --pmc passes')
     ap.add_argument('--no-detail', action='store_true', help='do not write the sidecar bench_detail.json (profiler / counter passes of this command)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline: traffic passes, CPU baselines, other precisions, secondary and '
+                         'data-parallel legs, the sidecar (the --no-* options then deselect parts of it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if not args.full:                                           # a plain run: the headline only
+        args.no_cpu_baseline = args.no_extras = args.no_traffic = args.no_detail = True
     global NO_DETAIL
     NO_DETAIL = bool(args.no_detail)
 
@@ -1207,7 +1247,7 @@ def main():
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run'
     # HBM-side traffic of the dominant kernel, measured live by child profiler passes -- before this process initialises the GPU
-    measured_traffic = (None, 'not measured (--no-traffic, --mode train or a multi-rank run)')
+    measured_traffic = (None, 'not measured (no --full, --no-traffic, --mode train or a multi-rank run)')
     if world == 1 and not args.no_traffic and args.mode == 'render' and os.environ.get('VQN_BENCH_NO_TRAFFIC', '0') in ('', '0'):
         _log('roofline.traffic: two child rocprofv3 --pmc passes')
         measured_traffic = live_traffic(args.rays)
@@ -1264,6 +1304,8 @@ def main():
     dt, clock = _timed_steps(step, args.steps, args.warmup, dev, world, backend)
     _log('headline render done')
     out = out_box[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, args.rays)
     assert torch.isfinite(out['color_fine']).all()
 
     # every rank takes part in the data-parallel training legs (collectives); only rank 0 reports.  Those legs have run on two ranks
@@ -1461,6 +1503,9 @@ def main_train(args, dev, rank, world, backend):
     from vqnerf_release_amd import _C
     runner, gstep = geo_train_setup(dev, rank)
     dt, clock = _timed_steps(gstep, args.steps, args.warmup, dev, world, backend, prime=PRIME_LAUNCHES // 300)
+    if args.dump_outputs and rank == 0:                         # the step's losses and the weights it leaves behind
+        params = {f'{net}.{k}': v for net in ('sdf_network', 'deviation_network', 'color_network') for k, v in getattr(runner, net).named_parameters()}
+        dump_outputs(args.dump_outputs, dict(runner.last_stats, **params), rows=None)
     sdf, col = runner.sdf_network, runner.color_network
     m_sdf, m_col = macs_per_point(sdf, col)
     B = 2560

@@ -15,7 +15,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 tail -3 $OUT/smoke.log; echo "smoke rc=$rc" | tee -a $OUT/status.txt
 [ $rc -ne 0 ] && exit $rc
 echo "== bench" | tee -a $OUT/status.txt
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; rc=$?
 cat $OUT/bench.json; tail -3 $OUT/bench.err; echo "bench rc=$rc" | tee -a $OUT/status.txt
 [ $rc -ne 0 ] && exit $rc
 echo "== rocprofv3 kernel trace" | tee -a $OUT/status.txt

@@ -111,3 +111,34 @@ def test_world_size_mismatch_is_still_an_error():
     env = dict(os.environ, WORLD_SIZE='1', RANK='0')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     assert r.returncode != 0 and 'WORLD_SIZE=1' in r.stderr
+
+
+def test_dump_outputs_keeps_one_seeded_row_sample_under_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 files; past the byte limit every per-ray array keeps the SAME seeded rows, the rest stays
+    whole, and two dumps of the same arrays are identical."""
+    import numpy as np
+    import torch
+    rows = 1000
+    g = torch.Generator().manual_seed(0)
+    arrays = {'color': torch.rand(rows, 3, generator=g), 'weights': torch.rand(rows, 128, generator=g), 'row': torch.arange(rows),
+              'hit': torch.rand(rows, 1, generator=g) > 0.5, 'loss': torch.tensor(0.25, dtype=torch.float64),
+              'w': torch.rand(7, 5, generator=g), 'unused': None}
+    whole = bench.dump_outputs(str(tmp_path / 'whole'), arrays, rows)
+    assert sorted(whole) == ['color', 'hit', 'loss', 'row', 'w', 'weights']
+    for k in whole:
+        a = np.load(tmp_path / 'whole' / f'{k}.npy')
+        assert a.dtype == (np.float64 if k in ('row', 'loss') else np.float32), k
+        assert np.array_equal(a, arrays[k].numpy().astype(a.dtype)), k
+    limit = 100_000
+    for d in ('cut1', 'cut2'):
+        bench.dump_outputs(str(tmp_path / d), arrays, rows, limit=limit)
+    got = {k: np.load(tmp_path / 'cut1' / f'{k}.npy') for k in whole}
+    assert sum(a.nbytes for a in got.values()) <= limit
+    sel = got['row'].astype(np.int64)
+    assert 1 <= len(sel) < rows and np.all(np.diff(sel) > 0)
+    for k in ('color', 'weights', 'hit'):
+        assert np.array_equal(got[k], arrays[k].numpy()[sel].astype(np.float32)), k
+    assert np.array_equal(got['w'], arrays['w'].numpy()) and float(got['loss']) == 0.25
+    for k in whole:
+        assert np.array_equal(got[k], np.load(tmp_path / 'cut2' / f'{k}.npy')), k
+
