@@ -27,7 +27,6 @@ def test_library_exports_every_declared_symbol():
 
 def test_argument_errors_do_not_need_a_gpu():
     lib = _C.lib()
-    lib.vqn_last_error.restype = ctypes.c_char_p
     rc = lib.vqn_vq_assign(None, ctypes.c_int64(-1), 256, None, 16, None, None, None, None, None, None)
     assert rc == -1 and b'bad argument' in lib.vqn_last_error()
     rc = lib.vqn_vq_assign(None, ctypes.c_int64(0), 256, None, 16, None, None, None, None, None, None)
@@ -37,7 +36,6 @@ def test_argument_errors_do_not_need_a_gpu():
                                   None, None) == -1 and b'null pointer' in lib.vqn_last_error()
     assert lib.vqn_neus_train_bwd(None, None, None, None, None, None, None, ctypes.c_int64(8), None, ctypes.c_int64(0), None, 0, None, 0,
                                   None) == -1
-    lib.vqn_neus_train_bwd_scratch_bytes.restype = ctypes.c_int64
     assert lib.vqn_neus_train_bwd_scratch_bytes(None) == -1
     bad = (ctypes.c_int32 * 76)()                                   # all zeros: no layers
     assert lib.vqn_neus_train_bwd_scratch_bytes(bad) == -1
@@ -119,7 +117,6 @@ SDF_SHAPES = [
 def test_c_sdf_pack_equals_python_pack(dims, skip_in, multires, f16s):
     from vqnerf_release_amd.geo import packing
     lib = _C.lib()
-    lib.vqn_neus_sdf_pack_plan.restype = ctypes.c_int64
     mode = ('f32', 'f16s', 'x3')[f16s]
     plan = packing.SdfPackPlan(dims, skip_in, multires, 1.5, max_tiles=8, mode=mode)
     n_lin = len(dims) - 1
@@ -167,7 +164,6 @@ def test_c_sdf_pack_equals_python_pack(dims, skip_in, multires, f16s):
 def test_c_colour_pack_equals_python_pack(d_feature, mode, d_hidden, n_layers, mv, f16s):
     from vqnerf_release_amd.geo import packing
     lib = _C.lib()
-    lib.vqn_neus_col_pack_plan.restype = ctypes.c_int64
     ft = (d_feature + 31) // 32
     plan = packing.ColPackPlan(d_feature, mode, d_hidden, n_layers, 3, mv, True, ft, matrix_mode=('f32', 'f16s', 'x3')[f16s])
     rng = np.random.default_rng(d_feature + n_layers)
@@ -191,8 +187,6 @@ def test_c_colour_pack_equals_python_pack(d_feature, mode, d_hidden, n_layers, m
 
 def test_c_pack_plan_rejects_unsupported_shapes():
     lib = _C.lib()
-    lib.vqn_neus_sdf_pack_plan.restype = ctypes.c_int64
-    lib.vqn_last_error.restype = ctypes.c_char_p
     dims = (ctypes.c_int32 * 4)(39, 64, 64, 65)
     assert lib.vqn_neus_sdf_pack_plan(dims, 3, 2, 6, ctypes.c_float(1.0), 0, 1, 0, None, None, ctypes.c_int64(0)) == -2   # skip into the last layer
     assert b'skip' in lib.vqn_last_error()
@@ -231,8 +225,6 @@ def _chain_model(mlp_width=128, z=256, nf=10):
 @pytest.mark.parametrize('shape', [(128, 256, 10), (64, 128, 6), (96, 160, 4)])
 def test_c_chain_program_equals_python_program(program, shape):
     lib = _C.lib()
-    lib.vqn_chain_pack_plan.restype = ctypes.c_int64
-    lib.vqn_last_error.restype = ctypes.c_char_p
     w, z, nf = shape
     m = _chain_model(*shape)
     fe, bn = m.net['fine_enc'], m.net['bottleneck']
@@ -273,7 +265,6 @@ def test_c_chain_program_equals_python_program(program, shape):
 
 def test_c_chain_program_rejects_what_it_does_not_build():
     lib = _C.lib()
-    lib.vqn_chain_pack_plan.restype = ctypes.c_int64
     bad_head = (_Stack * 1)(_stack(1, [256, 256, 3], ['relu', 'relu', 'sigmoid'], skip_at=1, out_slot=0))      # middle layer > 128 wide
     assert lib.vqn_chain_pack_plan(0, 256, 0, 1, bad_head, None, None, ctypes.c_int64(0)) == -2
     fwd_ref = (_Stack * 1)(_stack(0, [64], ['relu'], input=0))                                               # reads a stack that is not there yet

@@ -41,9 +41,6 @@ def test_c_packs_equal_python_packs_on_the_device(name, mode):
     ren.matrix_mode = mode
     wb_s, d_s, wb_c, d_c = ren._packs()
     lib = _C.lib()
-    for f in ('vqn_neus_pack_sdf_desc', 'vqn_neus_pack_col_desc', 'vqn_neus_pack_sdf_wbuf', 'vqn_neus_pack_col_wbuf'):
-        getattr(lib, f).restype = ctypes.c_void_p
-    lib.vqn_neus_pack_sdf_floats.restype = lib.vqn_neus_pack_col_floats.restype = ctypes.c_int64
     dims = list(sdf.dims)
     s_lins = [getattr(sdf, f'lin{l}') for l in range(sdf.num_layers - 1)]
     c_lins = [getattr(col, f'lin{l}') for l in range(col.num_layers - 1)]

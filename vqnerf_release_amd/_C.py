@@ -2,15 +2,54 @@
 
 There is NO fallback: if the library is missing or a call fails this raises.  Tensors are passed as
 raw device pointers (tensor.data_ptr()) plus sizes; work is enqueued on torch's current HIP stream.
+This is the package's only door to the library: every entry point is declared in ABI and launched through _call.
 """
+import contextlib
 import ctypes
 import os
+import re
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VQN_LIB', os.path.join(_HERE, 'lib', 'libvqnerf_hip.so'))     # VQN_LIB: diagnostic builds only
 _lib = None
+
+# Every function of include/vqnerf_hip.h as `R name(A...)`, one code per type: p pointer (device or host, None = NULL), i int /
+# int32_t, l int64_t, f float, d double, and for returns s const char* and v void.  lib() installs them as restype / argtypes;
+# tests/test_binding.py holds the table to the header.
+_ABI = """
+i vqn_version()  s vqn_last_error()  i vqn_vq_assign(plipipppppp)  i vqn_vq_assign_variant(iiii)  i vqn_vq_ema_stats(ppliippplp)
+l vqn_vq_ema_stats_ws_bytes(lii)  i vqn_vq_ste_loss(pplfpppp)  i vqn_vq_ema_update(pppiidfpppppppp)
+i vqn_decomp_loss_fwd(ppppppliiffffffpp)  i vqn_decomp_loss_bwd(ppppppliiffffffpppppp)  i vqn_l2_normalize_rows(plifpp)
+i vqn_l2_normalize_rows_bwd(pplifpp)  i vqn_vq_ste_loss_bwd(pppplpp)  i vqn_codebook_prep(ppiifpp)  i vqn_sim_smooth_fwd(piifpp)
+i vqn_sim_smooth_bwd(pppiifpp)  i vqn_vq_quantize_rows(plipipffpppppp)  i vqn_vq_train_bwd(pppppflifpp)
+i vqn_vq_quantize_rows_train(plipipfffppppppp)  i vqn_mlp_chain_fwd(ppplpipipipip)  i vqn_mlp_chain_fwd_f16s(ppplpipipipip)
+i vqn_brdf_shade_fwd(pppppppliippppppppppppipipp)  i vqn_brdf_shade_fwd_rows(ppppppppliippppppppppppipipp)
+l vqn_brdf_shade_bwd_partials(l)  i vqn_brdf_shade_bwd(pppppppliipppppppppppppppp)  i vqn_neus_sdf_points(pppppplipp)
+l vqn_neus_fine_scratch_bytes(p)  i vqn_neus_fine_points(pppppppppliplpppp)  i vqn_neus_train_fwd(pppppplplpiiiipppp)
+l vqn_neus_train_bwd_scratch_bytes(p)  i vqn_neus_train_bwd(ppppppplplpipip)  l vqn_neus_train_bwd_x3_scratch_bytes(p)
+i vqn_neus_train_bwd_x3(pppppppplplpipip)  i vqn_pack_x3_gather(pplpp)  i vqn_pack_x3_gather2(pplpplpp)
+i vqn_neus_sdf_points_f16s(pppppplipp)  i vqn_neus_fine_points_f16s(pppppppppliplpppp)  i vqn_neus_sdf_points_x3(pppppplipp)
+i vqn_neus_fine_points_x3(pppppppppliplpppp)  i vqn_neus_train_fwd_x3(pppppplplpiiiipppp)  i vqn_neus_pack_create(piiifiiiiiip)
+i vqn_neus_pack_update(pppppp)  p vqn_neus_pack_sdf_desc(p)  p vqn_neus_pack_col_desc(p)  p vqn_neus_pack_sdf_wbuf(p)
+p vqn_neus_pack_col_wbuf(p)  l vqn_neus_pack_sdf_floats(p)  l vqn_neus_pack_col_floats(p)  v vqn_neus_pack_destroy(p)
+l vqn_neus_sdf_pack_plan(piiifiiippl)  l vqn_neus_col_pack_plan(iiiiiiiiippl)  i vqn_mlp_chain_vq_fwd(ppppplpppppiffpppppp)
+i vqn_vq_codebook_frags(piipp)  i vqn_linear2srgb(plpp)  i vqn_chain_pack_create(iiiipp)  i vqn_chain_pack_update(pppp)
+i vqn_chain_pack_n_weights(p)  p vqn_chain_pack_desc(p)  p vqn_chain_pack_wbuf(p)  l vqn_chain_pack_floats(p)
+v vqn_chain_pack_destroy(p)  l vqn_chain_pack_plan(iiiipppl)  i vqn_neus_upsample(ppppliffpipp)  i vqn_neus_merge(ppppliippp)
+i vqn_neus_section_mids(plifpppp)  i vqn_neus_composite_fwd(pppppppppliffppppppppppp)  i vqn_neus_composite_bwd(pppppppppliffpppppppppp)
+i vqn_tile_program(pppppilp)  l vqn_tile_program_grid(pl)  i vqn_weight_norm_fwd(ipppppp)  i vqn_weight_norm_bwd(ipppppppp)
+i vqn_tfmt_pack(plilpip)  i vqn_tfmt_pack_delta(plilpipip)  i vqn_tfmt_unpack(piliplp)  i vqn_wgrad_partials(piiipiiilippp)
+i vqn_wgrad_partials_x3(piiipiiilippp)  i vqn_wgrad_partials_batched(ipppppppplippip)  i vqn_reduce_partials(piiiplip)
+i vqn_wgrad_finalize(ipppppppppppppp)  i vqn_clip_preserve(plffpp)  i vqn_loss_total(plppiiipp)  i vqn_ks_split_fwd(ppilppp)
+i vqn_ks_split_bwd(ppilppppp)  i vqn_wgrad_thin_batched(ippppppppplippp)  i vqn_multi_copy(ipppp)  i vqn_refl_train_desc_ints()
+i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppiip)  l vqn_refl_train_bwd_x3_scratch_bytes(p)
+i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
+"""
+ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
+_CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
 class VqnError(RuntimeError):
@@ -32,9 +71,11 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise VqnError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                            '(or `make -C vqnerf_release_amd/csrc`). There is no non-HIP fallback.')
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.vqn_last_error.restype = ctypes.c_char_p
-        _lib.vqn_version.restype = ctypes.c_int
+        L = ctypes.CDLL(LIB_PATH)
+        for name, (ret, args) in ABI.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = _CTYPES[ret], [_CTYPES[a] for a in args]
+        _lib = L
     return _lib
 
 
@@ -46,19 +87,44 @@ def require_device(t, what):
     lib()
 
 
-def _check(rc, name):
-    if rc != 0:
-        raise VqnError(f'{name} failed (rc={rc}): {lib().vqn_last_error().decode()}')
+def _check(rc, name, count=False):
+    """rc of `name`: 0 on success -- or, count=True, a positive count, which is returned."""
+    if (rc > 0) if count else (rc == 0):
+        return rc
+    raise VqnError(f'{name} failed (rc={rc or -3}): {lib().vqn_last_error().decode()}')
+
+
+def _call(name, *args, clock=True, count=False):
+    """lib().<name>(*args, torch's current stream), checked (see _check), inside the KernelClock bracket `clock`: True = the
+    entry's own name, a string = that label, False = not clocked."""
+    with _clock(name if clock is True else clock) if clock else contextlib.nullcontext():
+        rc = getattr(lib(), name)(*args, _stream())
+    return _check(rc, name, count)
 
 
 def _ptr(t):
-    if t is None:
-        return ctypes.c_void_p(0)
-    return ctypes.c_void_p(t.data_ptr())
+    """pointer argument of a tensor (None: NULL; an int is an address already)"""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def _ptrs(ts, n=1):
+    """host array of the pointers of `ts` (as _ptr), at least n entries (the rest NULL)"""
+    return (ctypes.c_void_p * max(n, len(ts)))(*[_ptr(t) for t in ts])
+
+
+def _host(a, dtype=np.int32):
+    """host array of the values `a` for a pointer argument (no copy of a contiguous array of that dtype)"""
+    return np.ascontiguousarray(a, dtype=dtype).ctypes
+
+
+def _i32(desc):
+    """-> (desc as a contiguous int32 array, its pointer argument)"""
+    d = np.ascontiguousarray(desc, dtype=np.int32)
+    return d, d.ctypes.data_as(ctypes.c_void_p)
 
 
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 class KernelClock:
@@ -140,16 +206,13 @@ def vq_assign(x, codebook, sel_mask=None, want_quant=True, want_dist=False):
         sel_mask = _f32c(sel_mask.reshape(-1).to(torch.float32).contiguous(), 'sel_mask')
         assert sel_mask.numel() == K
         ws = torch.empty((4,), dtype=torch.float32, device=x.device)
-    with _clock('vqn_vq_assign'):
-        rc = lib().vqn_vq_assign(_ptr(x), ctypes.c_int64(N), ctypes.c_int(D), _ptr(codebook), ctypes.c_int(K),
-                                 _ptr(sel_mask), _ptr(ws), _ptr(idx), _ptr(quant), _ptr(dist), _stream())
-    _check(rc, 'vqn_vq_assign')
+    _call('vqn_vq_assign', _ptr(x), N, D, _ptr(codebook), K, _ptr(sel_mask), _ptr(ws), _ptr(idx), _ptr(quant), _ptr(dist))
     return idx, quant, dist
 
 
 def vq_assign_variant(D, K, has_sel_mask=False, has_dist=False):
     """0: the f32 kernel, 1: the prefiltered kernel (vqn_vq_assign_variant)."""
-    return int(lib().vqn_vq_assign_variant(ctypes.c_int(D), ctypes.c_int(K), ctypes.c_int(bool(has_sel_mask)), ctypes.c_int(bool(has_dist))))
+    return lib().vqn_vq_assign_variant(D, K, bool(has_sel_mask), bool(has_dist))
 
 
 def vq_ema_stats(x, idx, K):
@@ -159,14 +222,9 @@ def vq_ema_stats(x, idx, K):
     assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == N
     counts = torch.empty((K,), dtype=torch.float32, device=x.device)
     dw = torch.empty((D, K), dtype=torch.float32, device=x.device)
-    L = lib()
-    L.vqn_vq_ema_stats_ws_bytes.restype = ctypes.c_int64
-    need = int(L.vqn_vq_ema_stats_ws_bytes(ctypes.c_int64(N), ctypes.c_int(D), ctypes.c_int(K)))
+    need = lib().vqn_vq_ema_stats_ws_bytes(N, D, K)
     ws = torch.empty((need // 4,), dtype=torch.float32, device=x.device) if need > 0 else None
-    with _clock('vqn_vq_ema_stats'):
-        rc = L.vqn_vq_ema_stats(_ptr(x), _ptr(idx), ctypes.c_int64(N), ctypes.c_int(D), ctypes.c_int(K),
-                                _ptr(counts), _ptr(dw), _ptr(ws), ctypes.c_int64(need), _stream())
-    _check(rc, 'vqn_vq_ema_stats')
+    _call('vqn_vq_ema_stats', _ptr(x), _ptr(idx), N, D, K, _ptr(counts), _ptr(dw), _ptr(ws), need)
     return counts, dw
 
 
@@ -175,10 +233,7 @@ def vq_counts(idx, K):
     """idx [N] int64 -> counts [K] float32 (= one_hot(idx, K).sum(0) without the [N,K] pass)."""
     assert idx.dtype == torch.int64 and idx.is_contiguous()
     counts = torch.empty((K,), dtype=torch.float32, device=idx.device)
-    with _clock('vqn_vq_ema_stats'):
-        rc = lib().vqn_vq_ema_stats(None, _ptr(idx), ctypes.c_int64(idx.numel()), ctypes.c_int(4), ctypes.c_int(K), _ptr(counts),
-                                    None, None, ctypes.c_int64(0), _stream())
-    _check(rc, 'vqn_vq_ema_stats')
+    _call('vqn_vq_ema_stats', None, _ptr(idx), idx.numel(), 4, K, _ptr(counts), None, None, 0)
     return counts
 
 
@@ -190,10 +245,7 @@ def vq_ste_loss(x, quant, want_ste=True):
     ste = torch.empty_like(x) if want_ste else None
     loss = torch.empty((), dtype=torch.float32, device=x.device)
     ws = torch.empty((1024,), dtype=torch.float32, device=x.device)
-    with _clock('vqn_vq_ste_loss'):
-        rc = lib().vqn_vq_ste_loss(_ptr(x), _ptr(quant), ctypes.c_int64(n), ctypes.c_float(1.0 / n if n else 0.0), _ptr(ste),
-                                   _ptr(loss), _ptr(ws), _stream())
-    _check(rc, 'vqn_vq_ste_loss')
+    _call('vqn_vq_ste_loss', _ptr(x), _ptr(quant), n, 1.0 / n if n else 0.0, _ptr(ste), _ptr(loss), _ptr(ws))
     return ste, loss
 
 def vq_ema_update(counts, dw, codebook, decay, eps, ema_cs, ema_dw):
@@ -204,11 +256,8 @@ def vq_ema_update(counts, dw, codebook, decay, eps, ema_cs, ema_dw):
         _f32c(m.hidden, 'hidden'); _f32c(m.average, 'average')
         assert m.counter.dtype == torch.int64 and m.counter.is_cuda
     update = torch.empty_like(codebook)
-    with _clock('vqn_vq_ema_update'):
-        rc = lib().vqn_vq_ema_update(_ptr(counts), _ptr(dw), _ptr(codebook), ctypes.c_int(D), ctypes.c_int(K), ctypes.c_double(decay),
-                                     ctypes.c_float(eps), _ptr(ema_cs.hidden), _ptr(ema_cs.average), _ptr(ema_cs.counter),
-                                     _ptr(ema_dw.hidden), _ptr(ema_dw.average), _ptr(ema_dw.counter), _ptr(update), _stream())
-    _check(rc, 'vqn_vq_ema_update')
+    _call('vqn_vq_ema_update', _ptr(counts), _ptr(dw), _ptr(codebook), D, K, decay, eps, _ptr(ema_cs.hidden), _ptr(ema_cs.average),
+          _ptr(ema_cs.counter), _ptr(ema_dw.hidden), _ptr(ema_dw.average), _ptr(ema_dw.counter), _ptr(update))
     return update
 
 
@@ -220,16 +269,14 @@ def _loss_args(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w):
             _f32c(t, n)
     N = rgb_pred.shape[0]
     D = 0 if z is None else z.shape[1]
-    return (_ptr(rgb_pred), _ptr(vq_rgb), _ptr(rgb_gt), _ptr(z), _ptr(spec), _ptr(rough), ctypes.c_int64(N), ctypes.c_int(D),
-            ctypes.c_int(1 if nerf else 0)) + tuple(ctypes.c_float(float(w[k])) for k in ('rgb', 'chr', 'smooth', 'alpha', 'thres', 'lambert'))
+    return (_ptr(rgb_pred), _ptr(vq_rgb), _ptr(rgb_gt), _ptr(z), _ptr(spec), _ptr(rough), N, D, 1 if nerf else 0) + \
+        tuple(float(w[k]) for k in ('rgb', 'chr', 'smooth', 'alpha', 'thres', 'lambert'))
 
 
 def decomp_loss_fwd(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w):
     """-> terms [N,5] (rgb, vqrgb, chromaticity, chr_smooth, lambert); w: dict of the six scalars (see include/vqnerf_hip.h)."""
     terms = torch.empty((rgb_pred.shape[0], 5), dtype=torch.float32, device=rgb_pred.device)
-    with _clock('vqn_decomp_loss_fwd'):
-        rc = lib().vqn_decomp_loss_fwd(*_loss_args(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w), _ptr(terms), _stream())
-    _check(rc, 'vqn_decomp_loss_fwd')
+    _call('vqn_decomp_loss_fwd', *_loss_args(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w), _ptr(terms))
     return terms
 
 
@@ -238,10 +285,8 @@ def decomp_loss_bwd(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w, g_terms):
     g_pred, g_vq = torch.empty_like(rgb_pred), torch.empty_like(vq_rgb)
     g_z = None if z is None else torch.empty_like(z)
     g_spec = None if spec is None else torch.empty_like(spec)
-    with _clock('vqn_decomp_loss_bwd'):
-        rc = lib().vqn_decomp_loss_bwd(*_loss_args(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w), _ptr(g_terms), _ptr(g_pred), _ptr(g_vq),
-                                       _ptr(g_z), _ptr(g_spec), _stream())
-    _check(rc, 'vqn_decomp_loss_bwd')
+    _call('vqn_decomp_loss_bwd', *_loss_args(rgb_pred, vq_rgb, rgb_gt, z, spec, rough, nerf, w), _ptr(g_terms), _ptr(g_pred), _ptr(g_vq),
+          _ptr(g_z), _ptr(g_spec))
     return g_pred, g_vq, g_z, g_spec
 
 
@@ -251,28 +296,21 @@ def codebook_prep(raw, g=None, eps=1e-6):
     if g is not None:
         _f32c(g, 'g')
     out = torch.empty_like(raw)
-    with _clock('vqn_codebook_prep'):
-        rc = lib().vqn_codebook_prep(_ptr(raw), _ptr(g), ctypes.c_int(raw.shape[0]), ctypes.c_int(raw.shape[1]), ctypes.c_float(eps), _ptr(out), _stream())
-    _check(rc, 'vqn_codebook_prep')
+    _call('vqn_codebook_prep', _ptr(raw), _ptr(g), raw.shape[0], raw.shape[1], eps, _ptr(out))
     return out
 
 
 def sim_smooth_fwd(cb, weight):
     _f32c(cb, 'codebook')
     out = torch.empty(4, dtype=torch.float32, device=cb.device)
-    with _clock('vqn_sim_smooth_fwd'):
-        rc = lib().vqn_sim_smooth_fwd(_ptr(cb), ctypes.c_int(cb.shape[0]), ctypes.c_int(cb.shape[1]), ctypes.c_float(weight), _ptr(out), _stream())
-    _check(rc, 'vqn_sim_smooth_fwd')
+    _call('vqn_sim_smooth_fwd', _ptr(cb), cb.shape[0], cb.shape[1], weight, _ptr(out))
     return out
 
 
 def sim_smooth_bwd(cb, fwd4, g_loss, weight):
     _f32c(cb, 'codebook'); _f32c(fwd4, 'fwd4'); _f32c(g_loss, 'g_loss')
     g = torch.empty_like(cb)
-    with _clock('vqn_sim_smooth_bwd'):
-        rc = lib().vqn_sim_smooth_bwd(_ptr(cb), _ptr(fwd4), _ptr(g_loss), ctypes.c_int(cb.shape[0]), ctypes.c_int(cb.shape[1]), ctypes.c_float(weight),
-                                      _ptr(g), _stream())
-    _check(rc, 'vqn_sim_smooth_bwd')
+    _call('vqn_sim_smooth_bwd', _ptr(cb), _ptr(fwd4), _ptr(g_loss), cb.shape[0], cb.shape[1], weight, _ptr(g))
     return g
 
 
@@ -282,10 +320,7 @@ def l2_normalize_rows_bwd(x, g, eps=1e-6):
     if x.shape != g.shape or x.dim() != 2:
         raise VqnError('l2_normalize_rows_bwd: x and g must be [N, D]')
     gx = torch.empty_like(x)
-    with _clock('vqn_l2_normalize_rows_bwd'):
-        rc = lib().vqn_l2_normalize_rows_bwd(_ptr(x), _ptr(g), ctypes.c_int64(x.shape[0]), ctypes.c_int(x.shape[1]), ctypes.c_float(eps), _ptr(gx),
-                                             _stream())
-    _check(rc, 'vqn_l2_normalize_rows_bwd')
+    _call('vqn_l2_normalize_rows_bwd', _ptr(x), _ptr(g), x.shape[0], x.shape[1], eps, _ptr(gx))
     return gx
 
 
@@ -295,9 +330,7 @@ def vq_ste_loss_bwd(x, quant, g_ste, g_loss):
     if g_ste is not None:
         _f32c(g_ste, 'g_ste')
     gx = torch.empty_like(x)
-    with _clock('vqn_vq_ste_loss_bwd'):
-        rc = lib().vqn_vq_ste_loss_bwd(_ptr(x), _ptr(quant), _ptr(g_ste), _ptr(g_loss), ctypes.c_int64(x.numel()), _ptr(gx), _stream())
-    _check(rc, 'vqn_vq_ste_loss_bwd')
+    _call('vqn_vq_ste_loss_bwd', _ptr(x), _ptr(quant), _ptr(g_ste), _ptr(g_loss), x.numel(), _ptr(gx))
     return gx
 
 
@@ -309,10 +342,7 @@ def vq_train_bwd(z, xnorm, quant, g_ste, g_loss, eps=1e-6, loss_post=1.0):
     if g_ste is not None:
         _f32c(g_ste, 'g_ste')
     gz = torch.empty_like(z)
-    with _clock('vqn_vq_train_bwd'):
-        rc = lib().vqn_vq_train_bwd(_ptr(z), _ptr(xnorm), _ptr(quant), _ptr(g_ste), _ptr(g_loss), ctypes.c_float(loss_post), ctypes.c_int64(z.shape[0]),
-                                    ctypes.c_int(z.shape[1]), ctypes.c_float(eps), _ptr(gz), _stream())
-    _check(rc, 'vqn_vq_train_bwd')
+    _call('vqn_vq_train_bwd', _ptr(z), _ptr(xnorm), _ptr(quant), _ptr(g_ste), _ptr(g_loss), loss_post, z.shape[0], z.shape[1], eps, _ptr(gz))
     return gz
 
 
@@ -320,9 +350,7 @@ def l2_normalize_rows(x, eps=1e-6):
     """x [N,D] -> x / sqrt(max(sum_d x^2, eps)) row by row, in the defined summation order of vqn_vq_assign's |x|^2."""
     _f32c(x, 'x')
     y = torch.empty_like(x)
-    with _clock('vqn_l2_normalize_rows'):
-        rc = lib().vqn_l2_normalize_rows(_ptr(x), ctypes.c_int64(x.shape[0]), ctypes.c_int(x.shape[1]), ctypes.c_float(eps), _ptr(y), _stream())
-    _check(rc, 'vqn_l2_normalize_rows')
+    _call('vqn_l2_normalize_rows', _ptr(x), x.shape[0], x.shape[1], eps, _ptr(y))
     return y
 
 
@@ -345,31 +373,48 @@ def vq_quantize_rows(z, codebook, sel_mask=None, eps=1e-6, want_ste=True, want_x
     n = N * D
     if want_xnorm:                                         # the training form: the normalised rows are kept (EMA statistics, backward)
         xnorm = torch.empty((N, D), dtype=torch.float32, device=dev)
-        with _clock('vqn_vq_quantize_rows_train'):
-            rc = lib().vqn_vq_quantize_rows_train(_ptr(z), ctypes.c_int64(N), ctypes.c_int(D), _ptr(codebook), ctypes.c_int(K), _ptr(sel_mask),
-                                                  ctypes.c_float(eps), ctypes.c_float(1.0 / n if n else 0.0), ctypes.c_float(loss_post), _ptr(ws), _ptr(idx),
-                                                  _ptr(ste), _ptr(loss), _ptr(counts), _ptr(xnorm), _stream())
-        _check(rc, 'vqn_vq_quantize_rows_train')
+        _call('vqn_vq_quantize_rows_train', _ptr(z), N, D, _ptr(codebook), K, _ptr(sel_mask), eps, 1.0 / n if n else 0.0, loss_post, _ptr(ws),
+              _ptr(idx), _ptr(ste), _ptr(loss), _ptr(counts), _ptr(xnorm))
         return idx, ste, loss, counts, xnorm
-    with _clock('vqn_vq_quantize_rows'):
-        rc = lib().vqn_vq_quantize_rows(_ptr(z), ctypes.c_int64(N), ctypes.c_int(D), _ptr(codebook), ctypes.c_int(K), _ptr(sel_mask),
-                                        ctypes.c_float(eps), ctypes.c_float(1.0 / n if n else 0.0), _ptr(ws), _ptr(idx), _ptr(ste),
-                                        _ptr(loss), _ptr(counts), _stream())
-    _check(rc, 'vqn_vq_quantize_rows')
+    _call('vqn_vq_quantize_rows', _ptr(z), N, D, _ptr(codebook), K, _ptr(sel_mask), eps, 1.0 / n if n else 0.0, _ptr(ws), _ptr(idx), _ptr(ste),
+          _ptr(loss), _ptr(counts))
     return idx, ste, loss, counts
 
 
 # --------------------------------------------------------------------------------------
+# device scratch of the fused kernels
+_scratch_cache = {}      # (device, stream, tag) -> [buffer, held]
+_scratch_held = []       # held buffers a larger request replaced: kept for the life of the process
+
+
+def _scratch(tag, need, device, stream=None, capturing=None):
+    """A uint8 buffer of at least `need` bytes for a launch on `stream` (default: torch's current one): one per (device, stream, tag),
+    grown, never shrunk; equal tags share it.  A buffer handed out while a graph records (`capturing`, default: asks torch) is held:
+    the graph replays with its pointer, so when a larger request replaces it, it stays alive in _scratch_held instead of being freed."""
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    if capturing is None:
+        capturing = torch.cuda.is_current_stream_capturing()
+    key = (str(device), stream, tag)
+    entry = _scratch_cache.get(key)
+    if entry is None or entry[0].numel() < need:
+        if entry is not None and entry[1]:
+            _scratch_held.append(entry[0])
+        entry = _scratch_cache[key] = [torch.empty((need,), dtype=torch.uint8, device=device), False]
+    entry[1] = entry[1] or capturing
+    return entry[0]
+
+
+def _scratch_bytes(name, desc):
+    """the scratch size query `name` of a descriptor; raises on an invalid one"""
+    need = getattr(lib(), name)(desc)
+    if need <= 0:
+        raise VqnError(f'{name}: invalid descriptor')
+    return need
+
+
+# --------------------------------------------------------------------------------------
 # fused NeuS networks (csrc/neus_mlp.hip)
-_scratch = {}
-
-
-def _i32(desc):
-    import numpy as np
-    d = np.ascontiguousarray(desc, dtype=np.int32)
-    return d, d.ctypes.data_as(ctypes.c_void_p)
-
-
 def neus_sdf_points(sdf_desc, wbuf_sdf, rays_o=None, rays_d=None, z=None, pts=None, mode='f32', pack=None):
     """SDF value at ray samples (rays_o/rays_d [B,3], z [B,S]) or at explicit pts [P,3] -> [P].  pack: a NeusPackHandle (its
     descriptor and SDF buffer are used, `mode` names the engine it was created for)."""
@@ -377,8 +422,7 @@ def neus_sdf_points(sdf_desc, wbuf_sdf, rays_o=None, rays_d=None, z=None, pts=No
         dp, wp = pack.sdf_desc, pack.sdf_wbuf
     else:
         _f32c(wbuf_sdf, 'wbuf_sdf')
-        d, dp = _i32(sdf_desc)
-        wp = _ptr(wbuf_sdf)
+        dp, wp = _host(sdf_desc), _ptr(wbuf_sdf)
     if pts is not None:
         _f32c(pts, 'pts'); P, S = pts.shape[0], 1
         dev = pts.device
@@ -389,18 +433,14 @@ def neus_sdf_points(sdf_desc, wbuf_sdf, rays_o=None, rays_d=None, z=None, pts=No
         dev = z.device
     out = torch.empty((P,), dtype=torch.float32, device=dev)
     entry = {'f32': 'vqn_neus_sdf_points', 'f16s': 'vqn_neus_sdf_points_f16s', 'x3': 'vqn_neus_sdf_points_x3'}[mode]
-    with _clock(entry):
-        rc = getattr(lib(), entry)(dp, wp, _ptr(rays_o), _ptr(rays_d), _ptr(z), _ptr(pts),
-                                   ctypes.c_int64(P), ctypes.c_int(S), _ptr(out), _stream())
-    _check(rc, entry)
+    _call(entry, dp, wp, _ptr(rays_o), _ptr(rays_d), _ptr(z), _ptr(pts), P, S, _ptr(out))
     return out
 
 
 def neus_fine_points(sdf_desc, wbuf_sdf, col_desc, wbuf_col, rays_o=None, rays_d=None, z=None, pts=None, dirs=None, mode='f32'):
     """sdf [P], d sdf/d x [P,3], rgb [P,3] at ray samples or explicit (pts, dirs)."""
     _f32c(wbuf_sdf, 'wbuf_sdf'); _f32c(wbuf_col, 'wbuf_col')
-    sd, sdp = _i32(sdf_desc)
-    cd, cdp = _i32(col_desc)
+    sdp, cdp = _host(sdf_desc), _host(col_desc)
     if pts is not None:
         _f32c(pts, 'pts'); _f32c(dirs, 'dirs'); P, S = pts.shape[0], 1
         dev = pts.device
@@ -409,25 +449,13 @@ def neus_fine_points(sdf_desc, wbuf_sdf, col_desc, wbuf_col, rays_o=None, rays_d
         B, S = z.shape
         P = B * S
         dev = z.device
-    L = lib()
-    L.vqn_neus_fine_scratch_bytes.restype = ctypes.c_int64
-    need = int(L.vqn_neus_fine_scratch_bytes(sdp))
-    if need <= 0:
-        raise VqnError('vqn_neus_fine_scratch_bytes: invalid SDF descriptor')
-    key = (str(dev), torch.cuda.current_stream().cuda_stream)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < need:
-        buf = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _scratch[key] = buf
+    buf = _scratch('fine', _scratch_bytes('vqn_neus_fine_scratch_bytes', sdp), dev)
     sdf = torch.empty((P,), dtype=torch.float32, device=dev)
     grad = torch.empty((P, 3), dtype=torch.float32, device=dev)
     rgb = torch.empty((P, 3), dtype=torch.float32, device=dev)
     entry = {'f32': 'vqn_neus_fine_points', 'f16s': 'vqn_neus_fine_points_f16s', 'x3': 'vqn_neus_fine_points_x3'}[mode]
-    with _clock(entry):
-        rc = getattr(L, entry)(sdp, _ptr(wbuf_sdf), cdp, _ptr(wbuf_col), _ptr(rays_o), _ptr(rays_d), _ptr(z),
-                               _ptr(pts), _ptr(dirs), ctypes.c_int64(P), ctypes.c_int(S), _ptr(buf),
-                               ctypes.c_int64(buf.numel()), _ptr(sdf), _ptr(grad), _ptr(rgb), _stream())
-    _check(rc, entry)
+    _call(entry, sdp, _ptr(wbuf_sdf), cdp, _ptr(wbuf_col), _ptr(rays_o), _ptr(rays_d), _ptr(z), _ptr(pts), _ptr(dirs), P, S, _ptr(buf),
+          buf.numel(), _ptr(sdf), _ptr(grad), _ptr(rgb))
     return sdf, grad, rgb
 
 
@@ -437,23 +465,16 @@ class NeusPackHandle:
 
     def __init__(self, sdf_dims, sdf_skip, multires, scale, col_mode, col_d_hidden, col_n_layers, multires_view, squeeze_out, engine):
         L = lib()
-        for f in ('vqn_neus_pack_sdf_desc', 'vqn_neus_pack_col_desc', 'vqn_neus_pack_sdf_wbuf', 'vqn_neus_pack_col_wbuf'):
-            getattr(L, f).restype = ctypes.c_void_p
         self.h = ctypes.c_void_p()
-        dims = (ctypes.c_int32 * len(sdf_dims))(*sdf_dims)
-        _check(L.vqn_neus_pack_create(dims, ctypes.c_int(len(sdf_dims) - 1), ctypes.c_int(sdf_skip), ctypes.c_int(multires), ctypes.c_float(scale),
-                                      ctypes.c_int(col_mode), ctypes.c_int(col_d_hidden), ctypes.c_int(col_n_layers), ctypes.c_int(multires_view),
-                                      ctypes.c_int(int(squeeze_out)), ctypes.c_int(engine), ctypes.byref(self.h)), 'vqn_neus_pack_create')
-        self.sdf_desc, self.col_desc = ctypes.c_void_p(L.vqn_neus_pack_sdf_desc(self.h)), ctypes.c_void_p(L.vqn_neus_pack_col_desc(self.h))
-        self.sdf_wbuf, self.col_wbuf = ctypes.c_void_p(L.vqn_neus_pack_sdf_wbuf(self.h)), ctypes.c_void_p(L.vqn_neus_pack_col_wbuf(self.h))
+        _check(L.vqn_neus_pack_create(_host(sdf_dims), len(sdf_dims) - 1, sdf_skip, multires, scale, col_mode, col_d_hidden, col_n_layers,
+                                      multires_view, int(squeeze_out), engine, ctypes.byref(self.h)), 'vqn_neus_pack_create')
+        self.sdf_desc, self.col_desc = L.vqn_neus_pack_sdf_desc(self.h), L.vqn_neus_pack_col_desc(self.h)
+        self.sdf_wbuf, self.col_wbuf = L.vqn_neus_pack_sdf_wbuf(self.h), L.vqn_neus_pack_col_wbuf(self.h)
 
     def update(self, W, b, Wc, bc):
         for t in W + b + Wc + bc:
             _f32c(t, 'weight / bias')
-        arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        with _clock('vqn_neus_pack_update'):
-            rc = lib().vqn_neus_pack_update(self.h, arr(W), arr(b), arr(Wc), arr(bc), _stream())
-        _check(rc, 'vqn_neus_pack_update')
+        _call('vqn_neus_pack_update', self.h, _ptrs(W), _ptrs(b), _ptrs(Wc), _ptrs(bc))
 
     def __del__(self):
         try:
@@ -474,26 +495,11 @@ def neus_train_fwd(sdf_desc, wbuf_sdf, col_desc, wbuf_col, pts, dirs, saved, e_t
         sdp, cdp, wsp, wcp, entry = pack.sdf_desc, pack.col_desc, pack.sdf_wbuf, pack.col_wbuf, 'vqn_neus_train_fwd_x3'
     else:
         _f32c(wbuf_sdf, 'wbuf_sdf'); _f32c(wbuf_col, 'wbuf_col')
-        sd, sdp = _i32(sdf_desc)
-        cd, cdp = _i32(col_desc)
-        wsp, wcp, entry = _ptr(wbuf_sdf), _ptr(wbuf_col), 'vqn_neus_train_fwd'
+        sdp, cdp, wsp, wcp, entry = _host(sdf_desc), _host(col_desc), _ptr(wbuf_sdf), _ptr(wbuf_col), 'vqn_neus_train_fwd'
     P, dev = pts.shape[0], pts.device
-    L = lib()
-    L.vqn_neus_fine_scratch_bytes.restype = ctypes.c_int64
-    need = int(L.vqn_neus_fine_scratch_bytes(sdp))
-    if need <= 0:
-        raise VqnError('vqn_neus_fine_scratch_bytes: invalid SDF descriptor')
-    key = (str(dev), torch.cuda.current_stream().cuda_stream)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < need:
-        buf = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _scratch[key] = buf
-    ptrs = (ctypes.c_void_p * len(saved))(*[t.data_ptr() for t in saved])
-    with _clock(entry):
-        rc = getattr(L, entry)(sdp, wsp, cdp, wcp, _ptr(pts), _ptr(dirs), ctypes.c_int64(P), _ptr(buf),
-                               ctypes.c_int64(buf.numel()), ptrs, ctypes.c_int(len(saved)), ctypes.c_int(e_tiles),
-                               ctypes.c_int(outf_tiles), ctypes.c_int(extr_tiles), _ptr(out_sdf), _ptr(out_n), _ptr(out_rgb), _stream())
-    _check(rc, entry)
+    buf = _scratch('fine', _scratch_bytes('vqn_neus_fine_scratch_bytes', sdp), dev)
+    _call(entry, sdp, wsp, cdp, wcp, _ptr(pts), _ptr(dirs), P, _ptr(buf), buf.numel(), _ptrs(saved), len(saved), e_tiles, outf_tiles,
+          extr_tiles, _ptr(out_sdf), _ptr(out_n), _ptr(out_rgb))
 
 
 def pack_x3_gather(flat, gidx, n_steps, fidx=None):
@@ -504,17 +510,12 @@ def pack_x3_gather(flat, gidx, n_steps, fidx=None):
         raise VqnError('pack_x3_gather: gidx must be a contiguous int32 tensor of n_steps * 512 entries')
     out = torch.empty((n_steps, 3, 64, 8), dtype=torch.int16, device=flat.device)
     if fidx is None:
-        with _clock('vqn_pack_x3_gather'):
-            rc = lib().vqn_pack_x3_gather(_ptr(flat), _ptr(gidx), ctypes.c_int64(n_steps), _ptr(out), _stream())
-        _check(rc, 'vqn_pack_x3_gather')
+        _call('vqn_pack_x3_gather', _ptr(flat), _ptr(gidx), n_steps, _ptr(out))
         return out
     if fidx.dtype != torch.int32 or not fidx.is_contiguous() or fidx.device != flat.device:
         raise VqnError('pack_x3_gather: fidx must be a contiguous int32 tensor on the device of flat')
     wf = torch.empty(fidx.shape, dtype=torch.float32, device=flat.device)
-    with _clock('vqn_pack_x3_gather'):
-        rc = lib().vqn_pack_x3_gather2(_ptr(flat), _ptr(gidx), ctypes.c_int64(n_steps), _ptr(out), _ptr(fidx), ctypes.c_int64(fidx.numel()),
-                                       _ptr(wf), _stream())
-    _check(rc, 'vqn_pack_x3_gather2')
+    _call('vqn_pack_x3_gather2', _ptr(flat), _ptr(gidx), n_steps, _ptr(out), _ptr(fidx), fidx.numel(), _ptr(wf), clock='vqn_pack_x3_gather')
     return out, wf
 
 
@@ -523,25 +524,10 @@ def neus_train_bwd_x3(desc, wbuf_pieces, wbuf_f32, pts, g_rgb, rgb, g_n, g_sdf, 
     _f32c(wbuf_f32, 'wbuf_f32'); _f32c(pts, 'pts'); _f32c(g_rgb, 'g_rgb')
     for t in saved + outs + [t for t in (rgb, g_n, g_sdf) if t is not None]:
         _f32c(t, 'tensor')
-    d, dp = _i32(desc)
-    P, dev = pts.shape[0], pts.device
-    L = lib()
-    L.vqn_neus_train_bwd_x3_scratch_bytes.restype = ctypes.c_int64
-    need = int(L.vqn_neus_train_bwd_x3_scratch_bytes(dp))
-    if need <= 0:
-        raise VqnError('vqn_neus_train_bwd_x3_scratch_bytes: invalid descriptor')
-    key = (str(dev), torch.cuda.current_stream().cuda_stream, 'bwd')
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < need:
-        buf = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _scratch[key] = buf
-    sp = (ctypes.c_void_p * len(saved))(*[t.data_ptr() for t in saved])
-    op = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
-    with _clock('vqn_neus_train_bwd_x3'):
-        rc = L.vqn_neus_train_bwd_x3(dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), _ptr(pts), _ptr(g_rgb), _ptr(rgb), _ptr(g_n), _ptr(g_sdf),
-                                     ctypes.c_int64(P), _ptr(buf), ctypes.c_int64(buf.numel()), sp, ctypes.c_int(len(saved)), op,
-                                     ctypes.c_int(len(outs)), _stream())
-    _check(rc, 'vqn_neus_train_bwd_x3')
+    dp = _host(desc)
+    buf = _scratch('bwd', _scratch_bytes('vqn_neus_train_bwd_x3_scratch_bytes', dp), pts.device)
+    _call('vqn_neus_train_bwd_x3', dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), _ptr(pts), _ptr(g_rgb), _ptr(rgb), _ptr(g_n), _ptr(g_sdf),
+          pts.shape[0], _ptr(buf), buf.numel(), _ptrs(saved), len(saved), _ptrs(outs), len(outs))
 
 
 def neus_train_bwd(desc, wbuf, pts, g_rgb, rgb, g_n, g_sdf, saved, outs):
@@ -550,24 +536,10 @@ def neus_train_bwd(desc, wbuf, pts, g_rgb, rgb, g_n, g_sdf, saved, outs):
     _f32c(wbuf, 'wbuf'); _f32c(pts, 'pts'); _f32c(g_rgb, 'g_rgb')
     for t in saved + outs + [t for t in (rgb, g_n, g_sdf) if t is not None]:
         _f32c(t, 'tensor')
-    d, dp = _i32(desc)
-    P, dev = pts.shape[0], pts.device
-    L = lib()
-    L.vqn_neus_train_bwd_scratch_bytes.restype = ctypes.c_int64
-    need = int(L.vqn_neus_train_bwd_scratch_bytes(dp))
-    if need <= 0:
-        raise VqnError('vqn_neus_train_bwd_scratch_bytes: invalid descriptor')
-    key = (str(dev), torch.cuda.current_stream().cuda_stream, 'bwd')
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < need:
-        buf = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _scratch[key] = buf
-    sp = (ctypes.c_void_p * len(saved))(*[t.data_ptr() for t in saved])
-    op = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
-    with _clock('vqn_neus_train_bwd'):
-        rc = L.vqn_neus_train_bwd(dp, _ptr(wbuf), _ptr(pts), _ptr(g_rgb), _ptr(rgb), _ptr(g_n), _ptr(g_sdf), ctypes.c_int64(P), _ptr(buf),
-                                  ctypes.c_int64(buf.numel()), sp, ctypes.c_int(len(saved)), op, ctypes.c_int(len(outs)), _stream())
-    _check(rc, 'vqn_neus_train_bwd')
+    dp = _host(desc)
+    buf = _scratch('bwd', _scratch_bytes('vqn_neus_train_bwd_scratch_bytes', dp), pts.device)
+    _call('vqn_neus_train_bwd', dp, _ptr(wbuf), _ptr(pts), _ptr(g_rgb), _ptr(rgb), _ptr(g_n), _ptr(g_sdf), pts.shape[0], _ptr(buf),
+          buf.numel(), _ptrs(saved), len(saved), _ptrs(outs), len(outs))
 
 
 def multi_copy(dsts, srcs):
@@ -575,17 +547,11 @@ def multi_copy(dsts, srcs):
     k = len(dsts)
     if k == 0:
         return
-    import numpy as np
     for d, s in zip(dsts, srcs):
         _f32c(d, 'dst'); _f32c(s, 'src')
         if d.numel() != s.numel():
             raise VqnError('multi_copy: element counts differ')
-    sp = (ctypes.c_void_p * k)(*[t.data_ptr() for t in srcs])
-    dp = (ctypes.c_void_p * k)(*[t.data_ptr() for t in dsts])
-    n = np.array([t.numel() for t in dsts], np.int64)
-    with _clock('vqn_multi_copy'):
-        rc = lib().vqn_multi_copy(ctypes.c_int(k), sp, dp, n.ctypes.data_as(ctypes.c_void_p), _stream())
-    _check(rc, 'vqn_multi_copy')
+    _call('vqn_multi_copy', k, _ptrs(srcs), _ptrs(dsts), _host([t.numel() for t in dsts], np.int64))
 
 
 # --------------------------------------------------------------------------------------
@@ -595,11 +561,7 @@ def neus_upsample(rays_o, rays_d, z, sdf, r_limit, inv_s, u):
     B, n = z.shape
     m = u.numel()
     z_new = torch.empty((B, m), dtype=torch.float32, device=z.device)
-    with _clock('vqn_neus_upsample'):
-        rc = lib().vqn_neus_upsample(_ptr(rays_o), _ptr(rays_d), _ptr(z), _ptr(sdf), ctypes.c_int64(B), ctypes.c_int(n),
-                                     ctypes.c_float(r_limit), ctypes.c_float(inv_s), _ptr(u), ctypes.c_int(m),
-                                     _ptr(z_new), _stream())
-    _check(rc, 'vqn_neus_upsample')
+    _call('vqn_neus_upsample', _ptr(rays_o), _ptr(rays_d), _ptr(z), _ptr(sdf), B, n, r_limit, inv_s, _ptr(u), m, _ptr(z_new))
     return z_new
 
 
@@ -612,11 +574,8 @@ def neus_merge(z, sdf, z_new, sdf_new):
     if sdf is not None and sdf_new is not None:
         _f32c(sdf, 'sdf'); _f32c(sdf_new, 'sdf_new')
         sdf_out = torch.empty((B, n + m), dtype=torch.float32, device=z.device)
-    with _clock('vqn_neus_merge'):
-        rc = lib().vqn_neus_merge(_ptr(z), _ptr(sdf if sdf_out is not None else None), _ptr(z_new),
-                                  _ptr(sdf_new if sdf_out is not None else None), ctypes.c_int64(B), ctypes.c_int(n),
-                                  ctypes.c_int(m), _ptr(z_out), _ptr(sdf_out), _stream())
-    _check(rc, 'vqn_neus_merge')
+    _call('vqn_neus_merge', _ptr(z), _ptr(sdf if sdf_out is not None else None), _ptr(z_new), _ptr(sdf_new if sdf_out is not None else None),
+          B, n, m, _ptr(z_out), _ptr(sdf_out))
     return z_out, sdf_out
 
 
@@ -627,10 +586,7 @@ def neus_section_mids(z, sample_dist, sample_dist_per_ray=None):
     dists = torch.empty_like(z)
     if sample_dist_per_ray is not None:
         sample_dist_per_ray = _f32c(sample_dist_per_ray.reshape(-1).contiguous(), 'sample_dist_per_ray')
-    with _clock('vqn_neus_section_mids'):
-        rc = lib().vqn_neus_section_mids(_ptr(z), ctypes.c_int64(B), ctypes.c_int(n), ctypes.c_float(float(sample_dist)),
-                                         _ptr(sample_dist_per_ray), _ptr(mid), _ptr(dists), _stream())
-    _check(rc, 'vqn_neus_section_mids')
+    _call('vqn_neus_section_mids', _ptr(z), B, n, float(sample_dist), _ptr(sample_dist_per_ray), _ptr(mid), _ptr(dists))
     return mid, dists
 
 
@@ -647,15 +603,8 @@ def neus_composite_fwd(rays_o, rays_d, mid_z, dists, sdf, grad, rgb, inv_s, back
     alpha = f(B, n) if want_alpha else None
     if background_rgb is not None:
         background_rgb = _f32c(background_rgb.reshape(-1)[:3].contiguous(), 'background_rgb')
-    with _clock('vqn_neus_composite_fwd'):
-        rc = lib().vqn_neus_composite_fwd(_ptr(rays_o), _ptr(rays_d), _ptr(mid_z), _ptr(dists), _ptr(sdf), _ptr(grad),
-                                          _ptr(rgb), _ptr(inv_s), _ptr(background_rgb), ctypes.c_int64(B), ctypes.c_int(n),
-                                          ctypes.c_float(float(radius)), ctypes.c_float(float(cos_anneal_ratio)),
-                                          _ptr(out['color']), _ptr(out['weights']), _ptr(out['cdf']),
-                                          _ptr(out['inside_sphere']), _ptr(out['surf']), _ptr(out['depth']),
-                                          _ptr(out['weight_sum']), _ptr(out['weight_max']), _ptr(out['gerr']),
-                                          _ptr(alpha), _stream())
-    _check(rc, 'vqn_neus_composite_fwd')
+    _call('vqn_neus_composite_fwd', _ptr(rays_o), _ptr(rays_d), _ptr(mid_z), _ptr(dists), _ptr(sdf), _ptr(grad), _ptr(rgb), _ptr(inv_s),
+          _ptr(background_rgb), B, n, float(radius), float(cos_anneal_ratio), *[_ptr(t) for t in out.values()], _ptr(alpha))
     if want_alpha:
         out['alpha'] = alpha
     return out
@@ -675,13 +624,8 @@ def mlp_chain_fwd(desc, wbuf, x, out_widths, mode='f32'):
     outs = [torch.empty((N, w), dtype=torch.float32, device=x.device) for w in out_widths]
     args = []
     for i in range(4):
-        if i < len(outs):
-            args += [_ptr(outs[i]), ctypes.c_int(out_widths[i])]
-        else:
-            args += [ctypes.c_void_p(0), ctypes.c_int(0)]
-    with _clock(entry):
-        rc = getattr(lib(), entry)(dp, _ptr(wbuf), _ptr(x), ctypes.c_int64(N), *args, _stream())
-    _check(rc, entry)
+        args += [_ptr(outs[i]), out_widths[i]] if i < len(outs) else [None, 0]
+    _call(entry, dp, _ptr(wbuf), _ptr(x), N, *args)
     return outs
 
 
@@ -690,9 +634,7 @@ def linear2srgb(x):
     x = x.contiguous()
     _f32c(x, 'x')
     y = torch.empty_like(x)
-    with _clock('vqn_linear2srgb'):
-        rc = lib().vqn_linear2srgb(_ptr(x), ctypes.c_int64(x.numel()), _ptr(y), _stream())
-    _check(rc, 'vqn_linear2srgb')
+    _call('vqn_linear2srgb', _ptr(x), x.numel(), _ptr(y))
     return y
 
 
@@ -701,9 +643,7 @@ def vq_codebook_frags(codebook):
     _f32c(codebook, 'codebook')
     D, K = codebook.shape
     frags = torch.empty(((1 if K <= 16 else (2 if K <= 32 else 4)) * (16 * 64 * 4 + 16),), dtype=torch.float32, device=codebook.device)
-    with _clock('vqn_vq_codebook_frags'):
-        rc = lib().vqn_vq_codebook_frags(_ptr(codebook), ctypes.c_int(D), ctypes.c_int(K), _ptr(frags), _stream())
-    _check(rc, 'vqn_vq_codebook_frags')
+    _call('vqn_vq_codebook_frags', _ptr(codebook), D, K, _ptr(frags))
     return frags
 
 
@@ -712,26 +652,21 @@ def mlp_chain_vq_fwd(desc_a, wbuf_a, widths_a, desc_b, wbuf_b, widths_b, x, frag
     launch (vqn_mlp_chain_vq_fwd).  Returns (outs_a, outs_b, idx, ste, loss, counts); outs_a[0] (z) is None unless want_z, ste
     (the straight-through rows [N, 256]) None unless want_ste."""
     _f32c(wbuf_a, 'wbuf_a'); _f32c(wbuf_b, 'wbuf_b'); _f32c(x, 'x'); _f32c(frags, 'frags')
-    da, dpa = _i32(desc_a)
-    db, dpb = _i32(desc_b)
     N = x.shape[0]
     dev = x.device
+    da, dpa = _i32(desc_a)
     assert x.shape[1] == int(da[8]), (x.shape, int(da[8]))
     outs_a = [torch.empty((N, w), dtype=torch.float32, device=dev) if (i > 0 or want_z) else None for i, w in enumerate(widths_a)]
     outs_b = [torch.empty((N, w), dtype=torch.float32, device=dev) for w in widths_b]
-    tab = lambda ts: (ctypes.c_void_p * 4)(*[(0 if (i >= len(ts) or ts[i] is None) else ts[i].data_ptr()) for i in range(4)])
-    lds = lambda ws: (ctypes.c_int32 * 4)(*[(ws[i] if i < len(ws) else 0) for i in range(4)])
     idx = torch.empty((N,), dtype=torch.int64, device=dev)
     ste = torch.empty((N, 256), dtype=torch.float32, device=dev) if want_ste else None
     loss = torch.empty((), dtype=torch.float32, device=dev)
     counts = torch.empty((K,), dtype=torch.float32, device=dev)
     ws = torch.empty((4096,), dtype=torch.float32, device=dev)
     n = N * 256
-    with _clock('vqn_mlp_chain_vq_fwd'):
-        rc = lib().vqn_mlp_chain_vq_fwd(dpa, _ptr(wbuf_a), dpb, _ptr(wbuf_b), _ptr(x), ctypes.c_int64(N), tab(outs_a), lds(widths_a),
-                                        tab(outs_b), lds(widths_b), _ptr(frags), ctypes.c_int(K), ctypes.c_float(eps),
-                                        ctypes.c_float(1.0 / n if n else 0.0), _ptr(idx), _ptr(ste), _ptr(loss), _ptr(counts), _ptr(ws), _stream())
-    _check(rc, 'vqn_mlp_chain_vq_fwd')
+    _call('vqn_mlp_chain_vq_fwd', dpa, _ptr(wbuf_a), _host(desc_b), _ptr(wbuf_b), _ptr(x), N, _ptrs(outs_a, 4), (ctypes.c_int32 * 4)(*widths_a),
+          _ptrs(outs_b, 4), (ctypes.c_int32 * 4)(*widths_b), _ptr(frags), K, eps, 1.0 / n if n else 0.0, _ptr(idx), _ptr(ste), _ptr(loss),
+          _ptr(counts), _ptr(ws))
     return outs_a, outs_b, idx, ste, loss, counts
 
 
@@ -773,13 +708,9 @@ def brdf_shade_fwd(xyz, normal, rayo, lvis, lxyz, lareas, light, materials, gamm
         probes = _f32c(probes.reshape(-1, L, 3).contiguous(), 'probes')
         n_probes = probes.shape[0]
         rgb_probes = f(N, n_probes, 3)
-    with _clock('vqn_brdf_shade_fwd'):
-        rc = lib().vqn_brdf_shade_fwd_rows(_ptr(rows), _ptr(xyz), _ptr(normal), _ptr(rayo), _ptr(lvis), _ptr(lxyz), _ptr(lareas),
-                                           _ptr(light), ctypes.c_int64(N), ctypes.c_int(L), ctypes.c_int(len(materials)),
-                                           *[_ptr(m) for m in mats], _ptr(gamma), _ptr(nout), _ptr(rgb[0]),
-                                           _ptr(rgb[1] if len(rgb) > 1 else None), _ptr(rd), _ptr(rs), ctypes.c_int(int(raw)),
-                                           _ptr(probes), ctypes.c_int(n_probes), _ptr(rgb_probes), _stream())
-    _check(rc, 'vqn_brdf_shade_fwd_rows')
+    _call('vqn_brdf_shade_fwd_rows', _ptr(rows), _ptr(xyz), _ptr(normal), _ptr(rayo), _ptr(lvis), _ptr(lxyz), _ptr(lareas), _ptr(light), N, L,
+          len(materials), *[_ptr(m) for m in mats], _ptr(gamma), _ptr(nout), _ptr(rgb[0]), _ptr(rgb[1] if len(rgb) > 1 else None), _ptr(rd),
+          _ptr(rs), int(raw), _ptr(probes), n_probes, _ptr(rgb_probes), clock='vqn_brdf_shade_fwd')
     return dict(rgb=rgb, normal=nout, rgb_diff=rd, rgb_spec=rs, rgb_probes=rgb_probes)
 
 
@@ -798,13 +729,9 @@ def neus_composite_bwd(rays_o, rays_d, mid_z, dists, sdf, grad, rgb, inv_s, back
     g_gradient_error, gerr_den = opt(g_gradient_error, 'g_gradient_error'), opt(gerr_den, 'gerr_den')
     if background_rgb is not None:
         background_rgb = _f32c(background_rgb.reshape(-1)[:3].contiguous(), 'background_rgb')
-    with _clock('vqn_neus_composite_bwd'):
-        rc = lib().vqn_neus_composite_bwd(_ptr(rays_o), _ptr(rays_d), _ptr(mid_z), _ptr(dists), _ptr(sdf), _ptr(grad), _ptr(rgb),
-                                          _ptr(inv_s), _ptr(background_rgb), ctypes.c_int64(B), ctypes.c_int(n),
-                                          ctypes.c_float(float(radius)), ctypes.c_float(float(cos_anneal_ratio)), _ptr(g_color),
-                                          _ptr(g_weight_sum), _ptr(g_weights), _ptr(g_gradient_error), _ptr(gerr_den),
-                                          _ptr(g_sdf), _ptr(g_grad), _ptr(g_rgb), _ptr(g_inv_s), _stream())
-    _check(rc, 'vqn_neus_composite_bwd')
+    _call('vqn_neus_composite_bwd', _ptr(rays_o), _ptr(rays_d), _ptr(mid_z), _ptr(dists), _ptr(sdf), _ptr(grad), _ptr(rgb), _ptr(inv_s),
+          _ptr(background_rgb), B, n, float(radius), float(cos_anneal_ratio), _ptr(g_color), _ptr(g_weight_sum), _ptr(g_weights),
+          _ptr(g_gradient_error), _ptr(gerr_den), _ptr(g_sdf), _ptr(g_grad), _ptr(g_rgb), _ptr(g_inv_s))
     return g_sdf, g_grad, g_rgb, g_inv_s
 
 
@@ -825,15 +752,9 @@ def brdf_shade_bwd(xyz, normal, rayo, lvis, lxyz, lareas, light, materials, g_su
     flat_out = [t for o in outs for t in o]
     while len(flat_out) < 6:
         flat_out.append(None)
-    L_ = lib()
-    L_.vqn_brdf_shade_bwd_partials.restype = ctypes.c_int64
-    n_part = int(L_.vqn_brdf_shade_bwd_partials(ctypes.c_int64(N)))
-    part = f(n_part, L, 3)
-    with _clock('vqn_brdf_shade_bwd'):
-        rc = L_.vqn_brdf_shade_bwd(_ptr(xyz), _ptr(normal), _ptr(rayo), _ptr(lvis), _ptr(lxyz), _ptr(lareas), _ptr(light),
-                                   ctypes.c_int64(N), ctypes.c_int(L), ctypes.c_int(len(materials)), *[_ptr(t) for t in args_m],
-                                   *[_ptr(t) for t in flat_out], _ptr(part), _stream())
-    _check(rc, 'vqn_brdf_shade_bwd')
+    part = f(lib().vqn_brdf_shade_bwd_partials(N), L, 3)
+    _call('vqn_brdf_shade_bwd', _ptr(xyz), _ptr(normal), _ptr(rayo), _ptr(lvis), _ptr(lxyz), _ptr(lareas), _ptr(light), N, L, len(materials),
+          *[_ptr(t) for t in args_m], *[_ptr(t) for t in flat_out], _ptr(part))
     return outs, part.sum(0)
 
 
@@ -846,21 +767,15 @@ def refl_train_fwd_x3(desc, wbuf_pieces, wbuf_f32, pts, z_rows, P, saved, z_rows
     _f32c(wbuf_f32, 'wbuf_f32')
     for t in [t for t in saved if t is not None] + list(head_out) + [t for t in (pts, z_rows, z_rows_out, zx_rows, zx_tiles_out) if t is not None]:
         _f32c(t, 'tensor')
-    d, dp = _i32(desc)
-    sp = (ctypes.c_void_p * len(saved))(*[0 if t is None else t.data_ptr() for t in saved])
-    hp = (ctypes.c_void_p * max(1, len(head_out)))(*[t.data_ptr() for t in head_out])
-    with _clock('vqn_refl_train_fwd_x3'):
-        if zx_rows is None:
-            rc = lib().vqn_refl_train_fwd_x3(dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), _ptr(pts), _ptr(z_rows), ctypes.c_int64(P), sp,
-                                             ctypes.c_int(len(saved)), _ptr(z_rows_out), hp, ctypes.c_int(int(split_heads)), ctypes.c_int(int(save)),
-                                             _stream())
-        else:
-            if zx_rows.shape[0] != P:
-                raise VqnError('refl_train_fwd_x3: zx_rows must have one row per point')
-            rc = lib().vqn_refl_train_fwd_x3_zx(dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), _ptr(pts), _ptr(z_rows), _ptr(zx_rows), ctypes.c_int64(P), sp,
-                                                ctypes.c_int(len(saved)), _ptr(z_rows_out), _ptr(zx_tiles_out), hp, ctypes.c_int(int(split_heads)),
-                                                ctypes.c_int(int(save)), _stream())
-    _check(rc, 'vqn_refl_train_fwd_x3')
+    dp, sp, hp = _host(desc), _ptrs(saved), _ptrs(head_out)
+    if zx_rows is None:
+        _call('vqn_refl_train_fwd_x3', dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), _ptr(pts), _ptr(z_rows), P, sp, len(saved), _ptr(z_rows_out), hp,
+              int(split_heads), int(save))
+        return
+    if zx_rows.shape[0] != P:
+        raise VqnError('refl_train_fwd_x3: zx_rows must have one row per point')
+    _call('vqn_refl_train_fwd_x3_zx', dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), _ptr(pts), _ptr(z_rows), _ptr(zx_rows), P, sp, len(saved),
+          _ptr(z_rows_out), _ptr(zx_tiles_out), hp, int(split_heads), int(save), clock='vqn_refl_train_fwd_x3')
 
 
 def refl_train_bwd_x3(desc, wbuf_pieces, wbuf_f32, P, g_out, head_out, g_z_rows, saved, outs, gz_rows_out, run_heads=True, run_enc=True,
@@ -872,28 +787,11 @@ def refl_train_bwd_x3(desc, wbuf_pieces, wbuf_f32, P, g_out, head_out, g_z_rows,
     g_z_rows = [t for t in (g_z_rows or []) if t is not None]
     for t in list(saved) + list(outs) + list(g_out) + list(head_out) + g_z_rows + [t for t in (gz_rows_out,) if t is not None]:
         _f32c(t, 'tensor')
-    d, dp = _i32(desc)
-    dev = wbuf_f32.device
-    L = lib()
-    L.vqn_refl_train_bwd_x3_scratch_bytes.restype = ctypes.c_int64
-    need = int(L.vqn_refl_train_bwd_x3_scratch_bytes(dp))
-    if need <= 0:
-        raise VqnError('vqn_refl_train_bwd_x3_scratch_bytes: invalid descriptor')
-    # one buffer per (device, stream, size), never replaced: a captured training step (Trainer(graph=True)) holds this pointer for as long
-    # as its graph is replayed, so a later, larger request on the same stream must not free it
-    key = (str(dev), torch.cuda.current_stream().cuda_stream, 'refl_bwd', need)
-    buf = _scratch.get(key)
-    if buf is None:
-        buf = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _scratch[key] = buf
-    arr = lambda ts: (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
-    with _clock('vqn_refl_train_bwd_x3'):
-        rc = L.vqn_refl_train_bwd_x3(dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), ctypes.c_int64(P), arr(g_out), arr(head_out), arr(g_z_rows),
-                                     ctypes.c_int(len(g_z_rows)), arr(saved), ctypes.c_int(len(saved)), arr(outs), ctypes.c_int(len(outs)),
-                                     _ptr(gz_rows_out), None if d2_row0 is None else (ctypes.c_int32 * len(d2_row0))(*[int(v) for v in d2_row0]),
-                                     ctypes.c_int(int(run_heads)), ctypes.c_int(int(run_enc)), ctypes.c_int(int(split_heads)),
-                                     _ptr(buf), ctypes.c_int64(buf.numel()), _stream())
-    _check(rc, 'vqn_refl_train_bwd_x3')
+    dp = _host(desc)
+    buf = _scratch('refl_bwd', _scratch_bytes('vqn_refl_train_bwd_x3_scratch_bytes', dp), wbuf_f32.device)
+    _call('vqn_refl_train_bwd_x3', dp, _ptr(wbuf_pieces), _ptr(wbuf_f32), P, _ptrs(g_out), _ptrs(head_out), _ptrs(g_z_rows), len(g_z_rows),
+          _ptrs(saved), len(saved), _ptrs(outs), len(outs), _ptr(gz_rows_out), None if d2_row0 is None else _host(d2_row0),
+          int(run_heads), int(run_enc), int(split_heads), _ptr(buf), buf.numel())
 
 
 # -------------------------------------------------------------------------------------- element-wise pieces (round 4)
@@ -901,19 +799,14 @@ def clip_preserve(x, lo, hi):
     """x + (clip(x) - x) in one launch (vqn_clip_preserve)."""
     _f32c(x, 'x')
     y = torch.empty_like(x)
-    with _clock('vqn_clip_preserve'):
-        rc = lib().vqn_clip_preserve(_ptr(x), ctypes.c_int64(x.numel()), ctypes.c_float(lo), ctypes.c_float(hi), _ptr(y), _stream())
-    _check(rc, 'vqn_clip_preserve')
+    _call('vqn_clip_preserve', _ptr(x), x.numel(), lo, hi, _ptr(y))
     return y
 
 
 def ks_split_fwd(basecolor, ks):
     _f32c(basecolor, 'basecolor'); _f32c(ks, 'ks')
     albedo, spec = torch.empty_like(basecolor), torch.empty_like(basecolor)
-    with _clock('vqn_ks_split_fwd'):
-        rc = lib().vqn_ks_split_fwd(_ptr(basecolor), _ptr(ks), ctypes.c_int(ks.shape[1]), ctypes.c_int64(basecolor.shape[0]), _ptr(albedo),
-                                    _ptr(spec), _stream())
-    _check(rc, 'vqn_ks_split_fwd')
+    _call('vqn_ks_split_fwd', _ptr(basecolor), _ptr(ks), ks.shape[1], basecolor.shape[0], _ptr(albedo), _ptr(spec))
     return albedo, spec
 
 
@@ -922,10 +815,7 @@ def ks_split_bwd(basecolor, ks, g_albedo, g_spec):
         if t is not None:
             _f32c(t, 'gradient')
     g_bc, g_ks = torch.empty_like(basecolor), torch.empty_like(ks)
-    with _clock('vqn_ks_split_bwd'):
-        rc = lib().vqn_ks_split_bwd(_ptr(basecolor), _ptr(ks), ctypes.c_int(ks.shape[1]), ctypes.c_int64(basecolor.shape[0]), _ptr(g_albedo),
-                                    _ptr(g_spec), _ptr(g_bc), _ptr(g_ks), _stream())
-    _check(rc, 'vqn_ks_split_bwd')
+    _call('vqn_ks_split_bwd', _ptr(basecolor), _ptr(ks), ks.shape[1], basecolor.shape[0], _ptr(g_albedo), _ptr(g_spec), _ptr(g_bc), _ptr(g_ks))
     return g_bc, g_ks
 
 
@@ -934,8 +824,88 @@ def loss_total(terms, vqloss, sim, use_chr, use_smooth, use_lambert):
     if sim is not None:
         _f32c(sim, 'sim')
     out = torch.empty((terms.shape[0],), dtype=torch.float32, device=terms.device)
-    with _clock('vqn_loss_total'):
-        rc = lib().vqn_loss_total(_ptr(terms), ctypes.c_int64(terms.shape[0]), _ptr(vqloss), _ptr(sim), ctypes.c_int(int(use_chr)),
-                                  ctypes.c_int(int(use_smooth)), ctypes.c_int(int(use_lambert)), _ptr(out), _stream())
-    _check(rc, 'vqn_loss_total')
+    _call('vqn_loss_total', _ptr(terms), terms.shape[0], _ptr(vqloss), _ptr(sim), int(use_chr), int(use_smooth), int(use_lambert), _ptr(out))
     return out
+
+
+# -------------------------------------------------------------------------------------- training engines (csrc/tile_vm.hip, wgrad*.hip)
+def tfmt_pack(x, N, F, ldx, out, tiles_f):
+    """rows x [N, F] (row stride ldx) -> the tile format `out` with tiles_f feature tiles, zero padded (vqn_tfmt_pack; not clocked)"""
+    _call('vqn_tfmt_pack', _ptr(x), N, F, ldx, _ptr(out), tiles_f, clock=False)
+
+
+def tfmt_pack_delta(g, N, F, ldg, y_tfmt, act, out, tiles_f):
+    """out (tile format) = g act'(y_tfmt), g [N, F] rows of stride ldg or None (vqn_tfmt_pack_delta)"""
+    _call('vqn_tfmt_pack_delta', _ptr(g), N, F, ldg, _ptr(y_tfmt), act, _ptr(out), tiles_f)
+
+
+def tfmt_unpack(t, tiles_f, N, F, out, ldx):
+    """the tile format t -> rows out [N, F] of stride ldx (vqn_tfmt_unpack; not clocked)"""
+    _call('vqn_tfmt_unpack', _ptr(t), tiles_f, N, F, _ptr(out), ldx, clock=False)
+
+
+def tile_program(which, desc_dev, desc_host, wbuf, tensors, tensor_ld, N):
+    """Run a tile program over N points (vqn_tile_program, clocked as 'vqn_tile_program:' + which); tensors: one tensor (or None) per
+    tensor slot of the program, tensor_ld their leading dimensions."""
+    _call('vqn_tile_program', _ptr(desc_dev), _host(desc_host), _ptr(wbuf), _ptrs(tensors), _host(tensor_ld), len(tensors), N,
+          clock='vqn_tile_program:' + which)
+
+
+def tile_program_grid(desc_host, N):
+    """workgroups vqn_tile_program launches for this program over N points"""
+    return lib().vqn_tile_program_grid(_host(desc_host), N)
+
+
+def wgrad_partials(A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws, rowsum_ws=None, x3=False):
+    """Split-over-points partial blocks of sum_p A[o][p] B[i][p] (vqn_wgrad_partials, x3: vqn_wgrad_partials_x3) -> their number."""
+    return _call('vqn_wgrad_partials_x3' if x3 else 'vqn_wgrad_partials', _ptr(A), a_tiles, a_t0, a_nt, _ptr(B), b_tiles, b_t0, b_nt,
+                 n_point_tiles, n_split, _ptr(ws), _ptr(rowsum_ws), count=True)
+
+
+def reduce_partials(ws, n, rows, cols, out, out_ld, accumulate=0, rowsum=None):
+    """out[r][c] (+)= the ordered sum of the n partial blocks [rows, cols] at ws (vqn_reduce_partials; out: a tensor whose first
+    element is (0, 0), row stride out_ld).  rowsum = (ws, out, out_ld): also the [1, rows] row-sum partials, in the same clock bracket."""
+    with _clock('vqn_reduce_partials'):
+        _call('vqn_reduce_partials', _ptr(ws), n, rows, cols, _ptr(out), out_ld, accumulate, clock=False)
+        if rowsum is not None:
+            _call('vqn_reduce_partials', _ptr(rowsum[0]), n, 1, rows, _ptr(rowsum[1]), rowsum[2], 0, clock=False)
+
+
+def wgrad_partials_batched(A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws, rowsum_ws, x3):
+    """vqn_wgrad_partials_batched over the problem lists (clocked as the per-problem entry) -> partial blocks per problem"""
+    return _call('vqn_wgrad_partials_batched', len(A), _ptrs(A), _host(a_tiles), _host(a_t0), _host(a_nt), _ptrs(B), _host(b_tiles),
+                 _host(b_t0), _host(b_nt), n_point_tiles, n_split, _ptrs(ws), _ptrs(rowsum_ws), int(x3), count=True,
+                 clock='vqn_wgrad_partials_x3' if x3 else 'vqn_wgrad_partials')
+
+
+def wgrad_thin_batched(A, a_tiles, a_t0, a_row0, a_rows, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws, rowsum_ws):
+    """vqn_wgrad_thin_batched over the problem lists -> partial blocks per problem"""
+    return _call('vqn_wgrad_thin_batched', len(A), _ptrs(A), _host(a_tiles), _host(a_t0), _host(a_row0), _host(a_rows), _ptrs(B),
+                 _host(b_tiles), _host(b_t0), _host(b_nt), n_point_tiles, n_split, _ptrs(ws), _ptrs(rowsum_ws), count=True)
+
+
+def wgrad_finalize(ws, n, ws2, n2, src_rows, src_cols, rows_valid, col_first, cols_valid, dst, dst_row_stride, dst_col_stride, scale):
+    """vqn_wgrad_finalize over the entry lists (one entry per result window)"""
+    _call('vqn_wgrad_finalize', len(ws), _ptrs(ws), _host(n), _ptrs(ws2), _host(n2), _host(src_rows), _host(src_cols), _host(rows_valid),
+          _host(col_first), _host(cols_valid), _ptrs(dst), _host(dst_row_stride, np.int64), _host(dst_col_stride, np.int64),
+          _host(scale, np.float32))
+
+
+def weight_norm_fwd(v, g, w):
+    """w_l = g_l v_l / ||v_l||_row for every layer l in one launch (vqn_weight_norm_fwd; not clocked)"""
+    _call('vqn_weight_norm_fwd', len(v), _ptrs(v), _ptrs(g), _ptrs(w), _host([t.shape[0] for t in v]), _host([t.shape[1] for t in v]),
+          clock=False)
+
+
+def weight_norm_bwd(v, g, dw, dv, dg):
+    """its backward: dv_l, dg_l from dw_l (vqn_weight_norm_bwd; not clocked)"""
+    _call('vqn_weight_norm_bwd', len(v), _ptrs(v), _ptrs(g), _ptrs(dw), _ptrs(dv), _ptrs(dg), _host([t.shape[0] for t in v]),
+          _host([t.shape[1] for t in v]), clock=False)
+
+
+def adam_step(params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, maximize, eps_mode):
+    """vqn_adam_step over the tensor lists (max_exp_avg_sq None without AMSGrad); lr a float or a device scalar tensor"""
+    lr_dev = lr if torch.is_tensor(lr) else None
+    _call('vqn_adam_step', len(params), _ptrs(params), _ptrs(grads), _ptrs(exp_avg), _ptrs(exp_avg_sq),
+          None if max_exp_avg_sq is None else _ptrs(max_exp_avg_sq), _ptrs(steps), _host([p.numel() for p in params], np.int64), _ptr(lr_dev),
+          0.0 if lr_dev is not None else float(lr), beta1, beta2, eps, weight_decay, int(maximize), eps_mode)

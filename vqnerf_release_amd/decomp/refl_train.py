@@ -16,7 +16,6 @@ frozen stage-2 encoder's output) is the heads' SECOND input (`zx`): a second ima
 heads' first GEMM, a third row-dot share in their last layer; the backward kernel is the same (no adjoint flows into z_xyz), the weight
 gradients of the Dense kernels' z_xyz rows are two more contractions per head.  Stacks this engine does not cover keep
 decomp/train_programs.py's interpreter."""
-import ctypes
 
 import numpy as np
 import torch

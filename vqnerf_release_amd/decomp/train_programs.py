@@ -6,14 +6,11 @@ Two engines, each with a forward program that saves every activation in TFMT and
   HeadsEngine   : z -> {diff, spec, rough} heads (skip-concat of z into the last layer) (weights' gradients and d/dz)
 Weights keep the Keras layout (kernel [in, out]); sigmoid' / relu' of the LAST layer of a stack is applied by the caller
 in torch before the reverse program (one elementwise op on [N, <=256])."""
-import ctypes
-
-import numpy as np
 import torch
 
 from vqnerf_release_amd import _C
 from vqnerf_release_amd.geo.train_programs import (Program, _ident, _f2i, DESC_INTS, K_LD_POSENC, K_LD_T, EPI_ACT, EPI_MUL_DACT,
-                                                   ACT_NONE, ACT_RELU, ACT_SIGMOID, FlatLayout, build_static_packs, WGRAD_ENTRY, wgrad_mode,
+                                                   ACT_NONE, ACT_RELU, ACT_SIGMOID, FlatLayout, build_static_packs, wgrad_mode,
                                                    WgradBatch, BATCHED_WGRAD)
 
 ACTS = {None: ACT_NONE, 'relu': ACT_RELU, 'sigmoid': ACT_SIGMOID}
@@ -30,9 +27,7 @@ def to_tfmt(x, tiles=None, out=None):
         out = torch.empty((nt, ft, 32, 32), dtype=torch.float32, device=x.device)
     assert tuple(out.shape) == (nt, ft, 32, 32) and out.is_contiguous()
     _C.require_device(x, 'to_tfmt')
-    rc = _C.lib().vqn_tfmt_pack(_C._ptr(x), ctypes.c_int64(N), ctypes.c_int(F), ctypes.c_int64(x.stride(0) if N > 1 else F),
-                                _C._ptr(out), ctypes.c_int(ft), _C._stream())
-    _C._check(rc, 'vqn_tfmt_pack')
+    _C.tfmt_pack(x, N, F, x.stride(0) if N > 1 else F, out, ft)
     return out
 
 
@@ -45,10 +40,7 @@ def pack_delta(g, y_tfmt, act, N, F, out):
             g = g.float().contiguous()
         _C.require_device(g, 'pack_delta')
     assert out.is_contiguous() and y_tfmt.is_contiguous() and out.shape == y_tfmt.shape
-    with _C._clock('vqn_tfmt_pack_delta'):
-        rc = _C.lib().vqn_tfmt_pack_delta(_C._ptr(g), ctypes.c_int64(N), ctypes.c_int(F), ctypes.c_int64((g.stride(0) if N > 1 else F) if g is not None else F),
-                                          _C._ptr(y_tfmt), ctypes.c_int(act), _C._ptr(out), ctypes.c_int(out.shape[1]), _C._stream())
-    _C._check(rc, 'vqn_tfmt_pack_delta')
+    _C.tfmt_pack_delta(g, N, F, (g.stride(0) if N > 1 else F) if g is not None else F, y_tfmt, act, out, out.shape[1])
     return out
 
 
@@ -57,9 +49,7 @@ def from_tfmt(t, N, F):
     nt, ft = t.shape[0], t.shape[1]
     assert t.is_contiguous() and nt * 32 >= N and ft * 32 >= F
     out = torch.empty((N, F), dtype=torch.float32, device=t.device)
-    rc = _C.lib().vqn_tfmt_unpack(_C._ptr(t), ctypes.c_int(ft), ctypes.c_int64(N), ctypes.c_int(F), _C._ptr(out), ctypes.c_int64(F),
-                                  _C._stream())
-    _C._check(rc, 'vqn_tfmt_unpack')
+    _C.tfmt_unpack(t, ft, N, F, out, F)
     return out
 
 
@@ -94,13 +84,7 @@ class _Engine:
         prog = getattr(self, which)
         d_host, d_dev = descs[which]
         names = list(prog.tn.keys())
-        ptrs = (ctypes.c_void_p * len(names))(*[tensors[n].data_ptr() if n in tensors else 0 for n in names])
-        lds = np.array([specs[n][1] for n in names], np.int32)
-        with _C._clock('vqn_tile_program:' + type(self).__name__ + '.' + which):
-            rc = _C.lib().vqn_tile_program(ctypes.c_void_p(d_dev.data_ptr()), d_host.ctypes.data_as(ctypes.c_void_p), _C._ptr(wbuf),
-                                           ptrs, lds.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(len(names)), ctypes.c_int64(N),
-                                           _C._stream())
-        _C._check(rc, 'vqn_tile_program')
+        _C.tile_program(type(self).__name__ + '.' + which, d_dev, d_host, wbuf, [tensors.get(n) for n in names], [specs[n][1] for n in names], N)
 
     def wgrad(self, A, B, a_rows, b_cols, ws, rowsum=False):
         """sum_p A[o][p] B[i][p] -> [a_rows, b_cols]; rowsum=True: also sum_p A[o][p] (bias gradient) from the same pass."""
@@ -109,25 +93,12 @@ class _Engine:
         assert an <= 8 and bn <= 8
         if rowsum and (getattr(self, '_rs_ws', None) is None or self._rs_ws.device != A.device):
             self._rs_ws = torch.empty(self.n_split * 256, dtype=torch.float32, device=A.device)
-        lib = _C.lib()
-        with _C._clock(WGRAD_ENTRY[wgrad_mode()]):
-            n = getattr(lib, WGRAD_ENTRY[wgrad_mode()])(_C._ptr(A), ctypes.c_int(at), ctypes.c_int(0), ctypes.c_int(an), _C._ptr(B), ctypes.c_int(bt),
-                                       ctypes.c_int(0), ctypes.c_int(bn), ctypes.c_int64(nt), ctypes.c_int(self.n_split),
-                                       _C._ptr(ws), _C._ptr(self._rs_ws if rowsum else None), _C._stream())
-        if n <= 0:
-            _C._check(n if n < 0 else -3, 'vqn_wgrad_partials')
+        n = _C.wgrad_partials(A, at, 0, an, B, bt, 0, bn, nt, self.n_split, ws, self._rs_ws if rowsum else None, x3=wgrad_mode() == 'bf16x3')
         out = torch.empty((an * 32, bn * 32), dtype=torch.float32, device=A.device)
-        with _C._clock('vqn_reduce_partials'):                        # ordered sum of the split-over-points partial blocks
-            rc = lib.vqn_reduce_partials(_C._ptr(ws), ctypes.c_int(n), ctypes.c_int(an * 32), ctypes.c_int(bn * 32), _C._ptr(out),
-                                         ctypes.c_int64(bn * 32), ctypes.c_int(0), _C._stream())
-            _C._check(rc, 'vqn_reduce_partials')
-            if rowsum:
-                rs = torch.empty((an * 32,), dtype=torch.float32, device=A.device)
-                rc = lib.vqn_reduce_partials(_C._ptr(self._rs_ws), ctypes.c_int(n), ctypes.c_int(1), ctypes.c_int(an * 32), _C._ptr(rs),
-                                             ctypes.c_int64(an * 32), ctypes.c_int(0), _C._stream())
-                _C._check(rc, 'vqn_reduce_partials')
-                return out[:a_rows, :b_cols], rs[:a_rows]
-        return out[:a_rows, :b_cols]
+        rs = torch.empty((an * 32,), dtype=torch.float32, device=A.device) if rowsum else None
+        # ordered sum of the split-over-points partial blocks
+        _C.reduce_partials(ws, n, an * 32, bn * 32, out, bn * 32, rowsum=(self._rs_ws, rs, an * 32) if rowsum else None)
+        return (out[:a_rows, :b_cols], rs[:a_rows]) if rowsum else out[:a_rows, :b_cols]
 
     @staticmethod
     def alloc(specs, N, device, only=None):

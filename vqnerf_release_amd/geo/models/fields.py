@@ -58,40 +58,23 @@ class _WeightNormAll(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, n, *gv):
-        import ctypes
-        import numpy as np
         from vqnerf_release_amd import _C
         gs, vs = gv[:n], gv[n:]
         ws = [torch.empty_like(v) for v in vs]
-        rows = np.array([v.shape[0] for v in vs], np.int32)
-        cols = np.array([v.shape[1] for v in vs], np.int32)
-        P = ctypes.c_void_p * n
-        rc = _C.lib().vqn_weight_norm_fwd(ctypes.c_int(n), P(*[v.data_ptr() for v in vs]), P(*[g.data_ptr() for g in gs]),
-                                          P(*[w.data_ptr() for w in ws]), rows.ctypes.data_as(ctypes.c_void_p),
-                                          cols.ctypes.data_as(ctypes.c_void_p), _C._stream())
-        _C._check(rc, 'vqn_weight_norm_fwd')
+        _C.weight_norm_fwd(vs, gs, ws)
         ctx.n = n
         ctx.save_for_backward(*gv)
         return tuple(ws)
 
     @staticmethod
     def backward(ctx, *dws):
-        import ctypes
-        import numpy as np
         from vqnerf_release_amd import _C
         n = ctx.n
         gs, vs = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
         dws = [torch.zeros_like(v) if d is None else d.contiguous() for d, v in zip(dws, vs)]
         dvs = [torch.empty_like(v) for v in vs]
         dgs = [torch.empty_like(g) for g in gs]
-        rows = np.array([v.shape[0] for v in vs], np.int32)
-        cols = np.array([v.shape[1] for v in vs], np.int32)
-        P = ctypes.c_void_p * n
-        rc = _C.lib().vqn_weight_norm_bwd(ctypes.c_int(n), P(*[v.data_ptr() for v in vs]), P(*[g.data_ptr() for g in gs]),
-                                          P(*[d.data_ptr() for d in dws]), P(*[d.data_ptr() for d in dvs]),
-                                          P(*[d.data_ptr() for d in dgs]), rows.ctypes.data_as(ctypes.c_void_p),
-                                          cols.ctypes.data_as(ctypes.c_void_p), _C._stream())
-        _C._check(rc, 'vqn_weight_norm_bwd')
+        _C.weight_norm_bwd(vs, gs, dws, dvs, dgs)
         return (None,) + tuple(dgs) + tuple(dvs)
 
 

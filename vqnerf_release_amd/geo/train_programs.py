@@ -14,7 +14,6 @@ so that the eikonal term and the normal-dependent colour differentiate through d
   weights   dW_l = a_bar_l (x) in_l + g^_l (x) in'_l   (contractions over points: csrc/wgrad.hip),  db_l = sum a_bar_l
 (the adjoint of the tangent stream IS the forward's reverse sweep, which is why g^_l is saved rather than recomputed).
 """
-import ctypes
 import os
 import math
 
@@ -152,43 +151,18 @@ class WgradBatch:
             assert base % 16 == 0
             at = lambda off: 0 if off is None else base + 4 * off
             n = min(self.n_split, self.nt)
-        if mt:
-            tpt = lambda j: (ctypes.c_void_p * mt)(*[x[j].data_ptr() for x in qt])
-            opt = lambda j: (ctypes.c_void_p * mt)(*[at(x[j]) for x in qt])
-            iat = [np.array([x[j] for x in qt], np.int32) for j in (1, 2, 3, 4, 6, 7, 8)]
-            ipt = [a.ctypes.data_as(ctypes.c_void_p) for a in iat]
-            with _C._clock('vqn_wgrad_thin_batched'):
-                nthin = _C.lib().vqn_wgrad_thin_batched(ctypes.c_int(mt), tpt(0), ipt[0], ipt[1], ipt[2], ipt[3], tpt(5), ipt[4], ipt[5], ipt[6],
-                                                        ctypes.c_int64(self.nt), ctypes.c_int(self.n_split), opt(9), opt(10), _C._stream())
-            if nthin <= 0:
-                _C._check(nthin if nthin < 0 else -3, 'vqn_wgrad_thin_batched')
+        if mt:             # columns of the problem tuples: A, a_tiles, a_t0, a_row0, a_rows, B, b_tiles, b_t0, b_nt, ws, rs
+            c = list(zip(*qt))
+            nthin = _C.wgrad_thin_batched(*c[:9], self.nt, self.n_split, [at(o) for o in c[9]], [at(o) for o in c[10]])
             assert nthin == n
-        if m:
-            tp = lambda j: (ctypes.c_void_p * m)(*[x[j].data_ptr() for x in q])
-            op = lambda j: (ctypes.c_void_p * m)(*[at(x[j]) for x in q])
-            ia = [np.array([x[j] for x in q], np.int32) for j in (1, 2, 3, 5, 6, 7)]
-            ip = [a.ctypes.data_as(ctypes.c_void_p) for a in ia]
-            x3 = wgrad_mode() == 'bf16x3'
-            with _C._clock(WGRAD_ENTRY[wgrad_mode()]):
-                n = _C.lib().vqn_wgrad_partials_batched(ctypes.c_int(m), tp(0), ip[0], ip[1], ip[2], tp(4), ip[3], ip[4], ip[5],
-                                                        ctypes.c_int64(self.nt), ctypes.c_int(self.n_split), op(8), op(9), ctypes.c_int(int(x3)),
-                                                        _C._stream())
-            if n <= 0:
-                _C._check(n if n < 0 else -3, 'vqn_wgrad_partials_batched')
+        if m:              # A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, ws, rs
+            c = list(zip(*q))
+            n = _C.wgrad_partials_batched(*c[:8], self.nt, self.n_split, [at(o) for o in c[8]], [at(o) for o in c[9]], wgrad_mode() == 'bf16x3')
             assert n == min(self.n_split, self.nt)
         if m or mt:
-            vp = lambda key: (ctypes.c_void_p * k)(*[at(x[key]) for x in e])
-            dp = (ctypes.c_void_p * k)(*[x['dst'] for x in e])
-            i32 = lambda key: np.array([x[key] for x in e], np.int32)
-            i64 = lambda key: np.array([x[key] for x in e], np.int64)
-            nn = np.full(k, n, np.int32)
-            arrs = [nn, nn, i32('src_rows'), i32('src_cols'), i32('rows_valid'), i32('col_first'), i32('cols_valid'),
-                    i64('sr'), i64('sc'), np.array([x['scale'] for x in e], np.float32)]
-            p = [a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
-            with _C._clock('vqn_wgrad_finalize'):
-                rc = _C.lib().vqn_wgrad_finalize(ctypes.c_int(k), vp('ws'), p[0], vp('ws2'), p[1], p[2], p[3], p[4], p[5], p[6], dp, p[7],
-                                                 p[8], p[9], _C._stream())
-            _C._check(rc, 'vqn_wgrad_finalize')
+            col = lambda key: [x[key] for x in e]
+            _C.wgrad_finalize([at(o) for o in col('ws')], [n] * k, [at(o) for o in col('ws2')], [n] * k, col('src_rows'), col('src_cols'),
+                              col('rows_valid'), col('col_first'), col('cols_valid'), col('dst'), col('sr'), col('sc'), col('scale'))
         self.e, self.keep, self.p, self.nt, self.ws_floats, self.pt = [], [], [], None, 0, []
 
 
@@ -641,12 +615,9 @@ class NeusTrainEngine:
 
     def alloc_tensors(self, P, device):
         nt = (P + 31) // 32
-        L = _C.lib()
-        L.vqn_tile_program_grid.restype = ctypes.c_int64
         scratch, n_wg = self._scratch_names(), nt
         if scratch:
-            d_host = self._static(device)[2]['prog_sbwd'][0]
-            n_wg = int(L.vqn_tile_program_grid(d_host.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(P)))
+            n_wg = _C.tile_program_grid(self._static(device)[2]['prog_sbwd'][0], P)
         out = {}
         for name, (kind, w) in self._tensor_specs().items():
             out[name] = torch.empty((P, w), dtype=torch.float32, device=device) if kind == 'vec' \
@@ -658,14 +629,8 @@ class NeusTrainEngine:
         prog = getattr(self, which)
         d_host, d_dev = descs[which]
         names = list(prog.tn.keys())
-        ptrs = (ctypes.c_void_p * len(names))(*[tensors[n].data_ptr() for n in names])
         specs, scratch = self._tensor_specs(), self._scratch_names()
-        lds = np.array([-specs[n][1] if n in scratch else specs[n][1] for n in names], np.int32)
-        with _C._clock('vqn_tile_program:' + which):
-            rc = _C.lib().vqn_tile_program(ctypes.c_void_p(d_dev.data_ptr()), d_host.ctypes.data_as(ctypes.c_void_p),
-                                           _C._ptr(wbuf), ptrs, lds.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(len(names)),
-                                           ctypes.c_int64(P), _C._stream())
-        _C._check(rc, 'vqn_tile_program')
+        _C.tile_program(which, d_dev, d_host, wbuf, [tensors[n] for n in names], [-specs[n][1] if n in scratch else specs[n][1] for n in names], P)
 
     # the forward on the render kernel ---------------------------------------------------------------
     def fused_forward(self):
@@ -933,7 +898,6 @@ class NeusTrainEngine:
         rs_out = torch.empty((1, a_nt_all * 32), dtype=torch.float32, device=A.device) if rowsum else None
         if rowsum and (self._rs_ws is None or self._rs_ws.device != A.device):
             self._rs_ws = torch.empty(self.n_split * 256, dtype=torch.float32, device=A.device)
-        lib = _C.lib()
         for pi, (A_, B_) in enumerate(((A, B), (A2, B2))):
             if A_ is None:
                 continue
@@ -942,24 +906,10 @@ class NeusTrainEngine:
                 for b0 in range(0, b_nt_all, 8):
                     bn = min(8, b_nt_all - b0)
                     want_rs = rowsum and pi == 0 and b0 == 0
-                    with _C._clock(WGRAD_ENTRY[wgrad_mode()]):
-                        n = getattr(lib, WGRAD_ENTRY[wgrad_mode()])(_C._ptr(A_), ctypes.c_int(at), ctypes.c_int(a0), ctypes.c_int(an), _C._ptr(B_),
-                                                   ctypes.c_int(bt), ctypes.c_int(b0), ctypes.c_int(bn), ctypes.c_int64(nt),
-                                                   ctypes.c_int(self.n_split), _C._ptr(ws), _C._ptr(self._rs_ws if want_rs else None),
-                                                   _C._stream())
-                    if n <= 0:
-                        _C._check(n if n < 0 else -3, 'vqn_wgrad_partials')
-                    blk = out[a0 * 32:(a0 + an) * 32, b0 * 32:(b0 + bn) * 32]
-                    with _C._clock('vqn_reduce_partials'):
-                        rc = lib.vqn_reduce_partials(_C._ptr(ws), ctypes.c_int(n), ctypes.c_int(an * 32), ctypes.c_int(bn * 32),
-                                                     ctypes.c_void_p(blk.data_ptr()), ctypes.c_int64(out.stride(0)), ctypes.c_int(pi),
-                                                     _C._stream())
-                        _C._check(rc, 'vqn_reduce_partials')
-                        if want_rs:
-                            rc = lib.vqn_reduce_partials(_C._ptr(self._rs_ws), ctypes.c_int(n), ctypes.c_int(1), ctypes.c_int(an * 32),
-                                                         ctypes.c_void_p(rs_out[:, a0 * 32:].data_ptr()), ctypes.c_int64(a_nt_all * 32),
-                                                         ctypes.c_int(0), _C._stream())
-                            _C._check(rc, 'vqn_reduce_partials')
+                    n = _C.wgrad_partials(A_, at, a0, an, B_, bt, b0, bn, nt, self.n_split, ws, self._rs_ws if want_rs else None,
+                                          x3=wgrad_mode() == 'bf16x3')
+                    _C.reduce_partials(ws, n, an * 32, bn * 32, out[a0 * 32:, b0 * 32:], out.stride(0), pi,
+                                       rowsum=(self._rs_ws, rs_out[:, a0 * 32:], a_nt_all * 32) if want_rs else None)
         if rowsum:
             return out[:a_rows, :b_cols], rs_out[0, :a_rows]
         return out[:a_rows, :b_cols]

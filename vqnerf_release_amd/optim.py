@@ -11,10 +11,8 @@ counters and the learning rate back on the device after a state written by an ea
 launch for the ~1 M reflectance parameters, two launches), this one 1,024.  Eligibility is decided for ALL groups before any is touched;
 when some tensor is not a contiguous f32 device tensor (CPU parameters in the gloo tests, a host-side lr) the whole step takes the
 framework statement of the same update -- torch's own for eps_mode 'torch', `_keras_statement` for 'keras'."""
-import ctypes
 import math
 
-import numpy as np
 import torch
 
 from vqnerf_release_amd import _C
@@ -104,19 +102,9 @@ class HipAdam(torch.optim.Adam):
             if not ps:
                 continue
             torch._foreach_add_(steps, 1)
-            k = len(ps)
-            arr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
-            n = np.array([p.numel() for p in ps], np.int64)
-            lr = group['lr']
             b1, b2 = group['betas']
-            with _C._clock('vqn_adam_step'):
-                rc = _C.lib().vqn_adam_step(ctypes.c_int(k), arr(ps), arr(gs), arr(ms), arr(vs), arr(vmaxs) if group['amsgrad'] else None,
-                                            arr(steps), n.ctypes.data_as(ctypes.c_void_p),
-                                            _C._ptr(lr) if torch.is_tensor(lr) else None,
-                                            ctypes.c_double(0.0 if torch.is_tensor(lr) else float(lr)), ctypes.c_double(b1), ctypes.c_double(b2),
-                                            ctypes.c_double(group['eps']), ctypes.c_double(group['weight_decay']),
-                                            ctypes.c_int(int(group['maximize'])), ctypes.c_int(EPS_MODES[self.eps_mode]), _C._stream())
-            _C._check(rc, 'vqn_adam_step')
+            _C.adam_step(ps, gs, ms, vs, vmaxs if group['amsgrad'] else None, steps, group['lr'], b1, b2, group['eps'], group['weight_decay'],
+                         group['maximize'], EPS_MODES[self.eps_mode])
         import vqnerf_release_amd
         vqnerf_release_amd.weights_changed()           # (the global optimiser hook covers step(); kept explicit for direct callers)
         return loss
