@@ -338,12 +338,13 @@ def displayed(rgb, data_type):
     return linear2srgb(rgb) if data_type == 'nerf' else rgb
 
 
-def _vq_step(p, specs, z_enc, mode, thres, roll, commitment_cost=0.1):
+def _vq_step(p, specs, z_enc, mode, thres, roll, commitment_cost=0.1, ema=None):
     """The quantiser block every inference entry point repeats (vq_nfr.py:226-233, :300-308, :425-433, :495-504):
     thres -> (1, K); z_norm = safe_l2_normalize(z_enc, 1); vq_layer(z_norm, get_codebook(), is_training=(mode == 'train')).
     `roll` stands in for the layer's tf.random.uniform((1, K)) (vq_layers.py:287); for thresholds in {0, 1} -- what the
     drop-ranking validation feeds (train_nfr.py:292-301, test.py:285) -- any draw of U[0, 1) gives the same mask, so
-    `roll=None` then means a constant 0.5."""
+    `roll=None` then means a constant 0.5.  mode 'train' (the entry points' default) also moves the layer's moving averages:
+    `ema` = (EMA of the cluster sizes, EMA of dw), advanced once (vq_layers.py:314-320); the codebook itself stays put."""
     K = p['codebook_raw'].shape[1]
     if thres is not None:
         thres = torch.as_tensor(np.asarray(thres), dtype=torch.float32).reshape(1, K)
@@ -352,7 +353,9 @@ def _vq_step(p, specs, z_enc, mode, thres, roll, commitment_cost=0.1):
             roll = torch.full((1, K), 0.5)
     C = get_codebook(p['codebook_raw'])
     z_norm = safe_l2_normalize(z_enc, 1)
-    assert mode != 'train', 'inference entry points only (no EMA state here)'
+    if mode == 'train':
+        assert ema is not None, "mode 'train' moves the EMA state: pass ema=(EMA(decay, (K,)), EMA(decay, (z_dim, K)))"
+        return vq_ema_call(z_norm, C, ema[0], ema[1], is_training=True, thres=thres, roll=roll, commitment_cost=commitment_cost)
     return vq_ema_call(z_norm, C, None, None, is_training=False, thres=thres, roll=roll, commitment_cost=commitment_cost)
 
 
@@ -363,7 +366,7 @@ def update_material(src, mask, update):
 
 def fast_render(p, specs, batch, lxyz, lareas, data_type='nerf', gamma=None, probes=(), dst_env=None, opt_scale=None,
                 vis_scale=False, edit_mask=None, edit_material=None, gen_embed=False, thres=None, roll=None, mode='test',
-                relight_olat=False, olat_maps=()):
+                relight_olat=False, olat_maps=(), ema=None):
     """vq_nfr.Model.fast_render (vq_nfr.py:262-398) on already-masked foreground points: main heads only, optional material
     edit under a mask (:289-291, :320-326), optional albedo / spec scale (:332-335), one render under the model light or
     `dst_env` (:340-343, :694-699) and one per probe (:724-733), optional code indices (`gen_embed`, :300-308, :373-375).
@@ -381,7 +384,7 @@ def fast_render(p, specs, batch, lxyz, lareas, data_type='nerf', gamma=None, pro
     z_enc = pred_enc(p, specs, xyz)
     out = {}
     if gen_embed:
-        out['embed'] = _vq_step(p, specs, z_enc, mode, thres, roll)['encoding_indices'] + 1
+        out['embed'] = _vq_step(p, specs, z_enc, mode, thres, roll, ema=ema)['encoding_indices'] + 1
     basecolor, ks, rough = heads(p, specs, z_enc, vq=False)
     spec = ks * basecolor
     albedo = (1 - ks) * basecolor
@@ -437,18 +440,18 @@ def init_mat(p, specs, z_pred):
     return torch.cat([(1 - ks) * basecolor, ks * basecolor, rough], -1)
 
 
-def fast_embed(p, specs, batch, mode='vali', thres=None, roll=None):
+def fast_embed(p, specs, batch, mode='vali', thres=None, roll=None, ema=None):
     """vq_nfr.Model.fast_embed (vq_nfr.py:209-256) on foreground points -> `embed` = encoding_indices + 1 (0 is what the
     scatter leaves on background rows, :247) and the xyz rows it scatters back."""
     z_enc = pred_enc(p, specs, batch['xyz'])
-    return dict(embed=_vq_step(p, specs, z_enc, mode, thres, roll)['encoding_indices'] + 1, xyz=batch['xyz'])
+    return dict(embed=_vq_step(p, specs, z_enc, mode, thres, roll, ema=ema)['encoding_indices'] + 1, xyz=batch['xyz'])
 
 
-def vis_mat(p, specs, batch, mode='vali', thres=None, roll=None):
+def vis_mat(p, specs, batch, mode='vali', thres=None, roll=None, ema=None):
     """vq_nfr.Model.vis_mat (vq_nfr.py:400-465) on foreground points: code indices + the CONTINUOUS-branch materials
     (`_pred_*_at(z_enc)`, :436-441 -- not the VQ heads)."""
     z_enc = pred_enc(p, specs, batch['xyz'])
-    embed = _vq_step(p, specs, z_enc, mode, thres, roll)['encoding_indices'] + 1
+    embed = _vq_step(p, specs, z_enc, mode, thres, roll, ema=ema)['encoding_indices'] + 1
     basecolor, ks, rough = heads(p, specs, z_enc, vq=False)
     return dict(albedo=(1 - ks) * basecolor, spec=ks * basecolor, rough=rough, embed=embed)
 

@@ -272,3 +272,62 @@ def test_call_with_code_dropout_vs_oracle(data_type, K):
     with torch.no_grad():
         pred0, _, _, _ = model.call(batch, mode='vali')
     assert len(np.unique(_np(pred0['embed'])[keep])) > len(np.unique(got))
+
+
+@pytest.mark.parametrize('data_type,K', [('nerf', 8), ('hw', 64)])
+def test_entry_points_at_their_default_mode_vs_oracle(data_type, K):
+    """`fast_embed(batch)`, `vis_mat(batch)` and `fast_render(batch, gen_embed=True)` without `mode`: the default is 'train', as in the
+    reference (vq_nfr.py:209, :262, :400).  There the quantiser runs with `is_training=True` (vq_layers.py:314-320): the code map is the
+    same nearest-code argmin as in 'vali', and every call ALSO advances the layer's two moving averages once (cluster sizes and dw, zero
+    debiased) -- while the codebook itself stays where it is: only `call` copies `update` into it (vq_nfr.py:582-583).  Checked against
+    oracle.decomp's `fast_embed` / `vis_mat` / `fast_render` in mode 'train', whose EMA objects advance in step with the model's."""
+    od, pt, specs, model, gamma, lxyz, lareas = _build(data_type, K)
+    pts, batch, keep, ob = _points(od, data_type, 700, 12)
+    z_enc = od.pred_enc(pt, specs, ob['xyz'])
+    want_vq = od._vq_step(pt, specs, z_enc, 'vali', None, None)
+    ema = (od.EMA(0.999, (K,)), od.EMA(0.999, (256, K)))
+    cb0 = model._codebook.detach().clone()
+    vql = model.vq_layer
+
+    def check_ema(calls, clear):
+        want_cs, want_dw = ema[0].hidden.numpy(), ema[1].hidden.numpy()
+        assert int(vql.ema_cluster_size.counter) == calls and int(vql.ema_dw.counter) == calls
+        got_cs, got_dw = _np(vql.ema_cluster_size.hidden), _np(vql.ema_dw.hidden)
+        # a near-tie row may sit in the other of its two nearest codes: each such row moves one count (times the decay weights)
+        n_amb = int((~clear).sum())
+        assert np.abs(got_cs - want_cs).sum() <= 2 * n_amb * (1 - 0.999) * calls + 1e-4, (got_cs, want_cs)
+        if n_amb == 0:
+            np.testing.assert_allclose(got_cs, want_cs, rtol=1e-5, atol=1e-6)
+            np.testing.assert_allclose(got_dw, want_dw, rtol=0, atol=2e-5 * max(1.0, float(np.abs(want_dw).max())))
+        assert float(vql.ema_cluster_size.hidden.sum()) > 0                                       # the state really moved
+        assert torch.equal(model._codebook.detach(), cb0)                                         # no codebook move outside `call`
+
+    # fast_embed
+    want = od.fast_embed(pt, specs, ob, mode='train', ema=ema)
+    with torch.no_grad():
+        pred, gt, lk, to_vis = model.fast_embed(batch)
+    assert lk == {'mode': 'train'} and set(pred) == {'alpha'}
+    emb = _np(to_vis['embed'])
+    np.testing.assert_array_equal(emb[~keep], 0)
+    clear = _check_indices(emb[keep, 0], want_vq, K)
+    np.testing.assert_array_equal(want['embed'].numpy(), want_vq['encoding_indices'].numpy() + 1)  # same argmin as 'vali'
+    check_ema(1, clear)
+    # vis_mat
+    wm = od.vis_mat(pt, specs, ob, mode='train', ema=ema)
+    with torch.no_grad():
+        pred, gt, lk, to_vis = model.vis_mat(batch)
+    assert lk == {'mode': 'train'}
+    _check_indices(_np(pred['embed'])[keep, 0], want_vq, K)
+    for k in ('albedo', 'spec', 'rough'):
+        np.testing.assert_allclose(_np(pred[k])[keep], wm[k].numpy(), rtol=0, atol=5e-6, err_msg=k)
+    check_ema(2, clear)
+    # fast_render(gen_embed=True)
+    wf = od.fast_render(pt, specs, ob, lxyz, lareas, data_type=data_type, gamma=gamma, gen_embed=True, mode='train', ema=ema)
+    with torch.no_grad():
+        pred, gt, lk, to_vis = model.fast_render(batch, gen_embed=True)
+    assert lk['mode'] == 'train' and set(pred) == {'alpha', 'basecolor', 'albedo', 'spec', 'rough', 'embed'}
+    _check_indices(_np(pred['embed'])[keep, 0], want_vq, K)
+    np.testing.assert_array_equal(_np(pred['embed'])[~keep], 0)
+    for k in ('albedo', 'spec', 'rough', 'basecolor'):
+        np.testing.assert_allclose(_np(pred[k])[keep], wf[k].numpy(), rtol=0, atol=5e-6, err_msg=k)
+    check_ema(3, clear)

@@ -1,7 +1,8 @@
 """CPU, world_size 2 over gloo: the data-parallel plumbing (vqnerf_release_amd/parallel.py).
   * one flat bucket [grads || extras] -> one all-reduce; replicas stay bit-identical;
   * DP over two half-batches == single process over the full batch (loss normalised by the GLOBAL batch);
-  * VQ EMA statistics reduced across ranks give the same codebook update as one process would."""
+  * VQ EMA statistics reduced across ranks give the same codebook update as one process would;
+  * `broadcast_module` invalidates the weight-pack caches built before it (the collective writes `t.data`, which bumps no `_version`)."""
 import os
 import socket
 
@@ -145,3 +146,55 @@ def test_single_process_paths_are_noops():
     assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(b.params, b.views))     # backward wrote into the bucket
     c, d = parallel.VQStatsReducer()(torch.ones(3), torch.ones(2, 3))
     assert c.sum() == 3 and d.sum() == 6
+
+
+def _cache_worker(rank, world, port, q):
+    """Rank 1 builds a pack of ITS OWN initial weights in both `_PackCache` classes (trained and frozen parameters), then takes rank 0's
+    weights by `broadcast_module`: the next `get` must rebuild from the broadcast values."""
+    from vqnerf_release_amd.decomp.nerfactor.models import nfr_unit
+    from vqnerf_release_amd.geo.models import fields
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        out = {}
+        for frozen in (False, True):
+            net = _net(seed=10 + rank)
+            params = list(net.parameters())
+            for p in params:
+                p.requires_grad_(not frozen)
+            pack = lambda: torch.cat([p.detach().reshape(-1) for p in params]).clone()
+            geo_cache, refl_cache = fields._PackCache(), nfr_unit._PackCache()
+            before = pack()
+            assert torch.equal(geo_cache.get(params, 'cpu', pack), before) and torch.equal(refl_cache.get(params, pack), before)
+            parallel.broadcast_module(net, src=0)
+            after = pack()
+            assert rank == 0 or not torch.equal(after, before)                # rank 1's weights really were replaced
+            out[frozen] = (geo_cache.get(params, 'cpu', pack).numpy().copy(), refl_cache.get(params, pack).numpy().copy(),
+                           after.numpy().copy())
+        q.put((rank, out))
+    except BaseException as e:                                                 # (the parent waits on the queue: always answer)
+        q.put((rank, repr(e)))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+def test_broadcast_module_invalidates_weight_packs():
+    ctx = mp.get_context('spawn')
+    q = ctx.SimpleQueue()
+    port = _free_port()
+    procs = [ctx.Process(target=_cache_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = dict(q.get() for _ in procs)
+    for p in procs:
+        p.join(timeout=120)
+    assert all(isinstance(v, dict) for v in got.values()), got
+    assert all(p.exitcode == 0 for p in procs)
+    for frozen in (False, True):
+        src = got[0][frozen][2]
+        for rank in (0, 1):
+            geo, refl, weights = got[rank][frozen]
+            np.testing.assert_array_equal(weights, src)
+            np.testing.assert_array_equal(geo, src, err_msg=f'geo pack, rank {rank}, frozen={frozen}')
+            np.testing.assert_array_equal(refl, src, err_msg=f'reflectance pack, rank {rank}, frozen={frozen}')

@@ -16,24 +16,60 @@ __version__ = '0.1.0'
 # (`torch._fused_adam_`) leaves it untouched, so does a replayed HIP graph, so does any raw-pointer writer behind the C ABI.
 # Every pack cache therefore also keys on this process-wide counter.  It advances after every `optimizer.step()` of any torch
 # optimiser (global post-step hook below), after every graph replay of the package's trainers, and on request.
+# A second counter, the REWRITE epoch, advances on request only (`weights_changed()`, `parallel.broadcast_module`): packs of
+# FROZEN parameters -- moved by no optimiser and no replay -- key on it instead, so that a training step of the other nets does
+# not rebuild them (a rebuild reads biases back to the host, which a captured step cannot record).
 _weights_epoch = [0]
+_rewrite_epoch = [0]
 
 
 def weights_epoch():
     return _weights_epoch[0]
 
 
+def rewrite_epoch():
+    return _rewrite_epoch[0]
+
+
 def weights_changed():
-    """Invalidate every cached weight pack / codebook-fragment image of the process.  Call it after rewriting parameters in a
-    way torch cannot see (replaying a captured graph of your own, a ctypes kernel or DLPack peer writing into a parameter)."""
+    """Invalidate every cached weight pack / codebook-fragment image of the process, frozen parameters' included.  Call it after
+    rewriting parameters in a way torch cannot see (replaying a captured graph of your own, a ctypes kernel or DLPack peer writing
+    into a parameter, `p.data.copy_`)."""
     _weights_epoch[0] += 1
+    _rewrite_epoch[0] += 1
+
+
+def weights_stepped():
+    """An optimiser step or a graph replay of a training step moved the TRAINABLE parameters: invalidate the packs keyed on them
+    (not those of frozen parameters)."""
+    _weights_epoch[0] += 1
+
+
+class WeightsStamp:
+    """What a weight-derived cache was built from: the tensor objects themselves (held weakly: the `id()` or `data_ptr()` of a
+    freed tensor is recycled by the next one), their `_version`s and devices, and `extra` (the epochs).  Equal stamps: same
+    objects, alive, same versions, same extra."""
+    __slots__ = ('refs', 'key')
+    __hash__ = None
+
+    def __init__(self, tensors, extra=()):
+        import weakref
+        self.refs = tuple(weakref.ref(t) for t in tensors)
+        self.key = tuple(extra) + tuple((t._version, str(t.device)) for t in tensors)
+
+    def __eq__(self, other):
+        return (isinstance(other, WeightsStamp) and self.key == other.key and len(self.refs) == len(other.refs)
+                and all(a() is not None and a() is b() for a, b in zip(self.refs, other.refs)))
+
+    def __reduce__(self):                 # a copied / pickled cache matches nothing: it rebuilds on first use
+        return WeightsStamp, ((), ('copied',))
 
 
 def _install_optimizer_hook():
     try:
         from torch.optim.optimizer import register_optimizer_step_post_hook
-        register_optimizer_step_post_hook(lambda *_a, **_k: weights_changed())
-    except Exception:                     # noqa: BLE001  (an older torch: trainers of this package still call weights_changed())
+        register_optimizer_step_post_hook(lambda *_a, **_k: weights_stepped())
+    except Exception:                     # noqa: BLE001  (an older torch: trainers of this package still call weights_stepped())
         pass
 
 

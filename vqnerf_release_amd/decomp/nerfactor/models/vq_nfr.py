@@ -161,7 +161,7 @@ class Model(BrdfModel):
 
     fuse_quantise = True       # inference without a graph: normalise + assign + straight-through + loss + usage in one kernel
 
-    def _quantise(self, z_enc, mode, thres, roll=None):
+    def _quantise(self, z_enc, mode, thres, roll=None, want_indices=True):
         """vq_nfr.py:575-578: z_norm = l2_normalize(z_enc), vq_layer(z_norm, codebook).  Two device paths with bit-identical
         `quantize` / indices: the fused kernel when neither a graph nor the EMA statistics are needed, else the sequence
         vqn_l2_normalize_rows -> vqn_vq_assign -> vqn_vq_ste_loss (-> vqn_vq_ema_stats)."""
@@ -176,14 +176,16 @@ class Model(BrdfModel):
         else:
             z_norm = l2_normalize_rows(z_enc) if on_kernels else mathutil.safe_l2_normalize(z_enc, axis=1)
             vq = self.vq_layer(z_norm, codebook, is_training=(mode == 'train'), thres=th, roll=roll)
-        # (the 1-based code map is an output of the inference modes only: in a training step the int64 addition was one launch nobody read)
-        return vq, vq['quantize'], vq['loss'], (None if mode == 'train' else vq['encoding_indices'] + 1)
+        # (the 1-based code map: `call` turns it off in a training step, where the int64 addition was one launch nobody read; the other
+        #  entry points read it in every mode)
+        return vq, vq['quantize'], vq['loss'], (vq['encoding_indices'] + 1 if want_indices else None)
 
     fuse_front = True          # inference, K <= 64, no code dropout: encoder -> heads -> VQ step -> VQ heads in ONE launch
 
     def _cb_frags(self, cb):
         """MFMA fragments + |c|^2 of the (clipped) codebook for the fused front kernel, rebuilt when the parameter changes."""
-        key = (self._codebook.data_ptr(), self._codebook._version, cb.device, vqnerf_release_amd.weights_epoch())
+        # (the parameter object by identity: set_codebook installs a new one, whose storage may land where a freed one's was)
+        key = vqnerf_release_amd.WeightsStamp([self._codebook], (str(cb.device), vqnerf_release_amd.weights_epoch()))
         if getattr(self, '_frags_key', None) != key:
             self._frags, self._frags_key = _C.vq_codebook_frags(cb), key
         return self._frags
@@ -312,7 +314,7 @@ class Model(BrdfModel):
             z_enc, basecolor, ks, rough, vq, z_vq, vq_loss, embed_ind, (vq_albedo, vq_spec, vq_rough), redo = front
         else:
             z_enc, basecolor, ks, rough = self.enc_and_heads(xyz_m, 'main')       # (one launch on the inference path)
-            vq, z_vq, vq_loss, embed_ind = self._quantise(z_enc, mode, thres, roll=roll)
+            vq, z_vq, vq_loss, embed_ind = self._quantise(z_enc, mode, thres, roll=roll, want_indices=(mode != 'train'))
             if mode == 'train':                               # codebook is moved by the EMA, outside the optimiser (:582-583)
                 with torch.no_grad():
                     self._codebook.copy_(vq['update'])

@@ -102,8 +102,9 @@ class _PackCache:
         self.value = None
 
     def get(self, params, device, build):
-        # (the process-wide weights epoch: writes `_version` does not see -- fused Adam, graph replays; vqnerf_release_amd/__init__.py)
-        key = (str(device), vqnerf_release_amd.weights_epoch()) + tuple((id(p), p._version) for p in params)
+        # (the process-wide weights epoch: writes `_version` does not see -- fused Adam, graph replays; vqnerf_release_amd/__init__.py;
+        #  the parameter objects by identity, not by a recyclable id())
+        key = vqnerf_release_amd.WeightsStamp(params, (str(device), vqnerf_release_amd.weights_epoch()))
         if key != self.key:
             with torch.no_grad():
                 self.value = build()

@@ -188,7 +188,7 @@ class Runner:
         self._static_data.copy_(data)
         self._cap.replay()
         import vqnerf_release_amd
-        vqnerf_release_amd.weights_changed()              # a replay moves the weights without bumping any tensor `_version`
+        vqnerf_release_amd.weights_stepped()              # a replay moves the weights without bumping any tensor `_version`
         self._finish_step(self._static_extra)
         return self.last_stats
 

@@ -675,7 +675,8 @@ class NeusTrainEngine:
     def _weights_key(self):
         """what the x3 packs were built from: the process-wide weights epoch (optimiser steps, graph replays) + every parameter's version"""
         import vqnerf_release_amd
-        return (vqnerf_release_amd.weights_epoch(),) + tuple((id(p), p._version) for m in (self.sdf_net, self.col_net) for p in m.parameters())
+        return vqnerf_release_amd.WeightsStamp([p for m in (self.sdf_net, self.col_net) for p in m.parameters()],
+                                               (vqnerf_release_amd.weights_epoch(),))
 
     def run_fused_forward_x3(self, W, b, Wc, bc, T, P):
         """the forward on the exact-split engine: packs by the library's own builder (one gather + split launch per network)"""

@@ -106,7 +106,7 @@ class HipAdam(torch.optim.Adam):
             _C.adam_step(ps, gs, ms, vs, vmaxs if group['amsgrad'] else None, steps, group['lr'], b1, b2, group['eps'], group['weight_decay'],
                          group['maximize'], EPS_MODES[self.eps_mode])
         import vqnerf_release_amd
-        vqnerf_release_amd.weights_changed()           # (the global optimiser hook covers step(); kept explicit for direct callers)
+        vqnerf_release_amd.weights_stepped()           # (the global optimiser hook covers step(); kept explicit for direct callers)
         return loss
 
     @staticmethod

@@ -333,6 +333,8 @@ def broadcast_module(module, src=0):
         return
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src=src)
+    import vqnerf_release_amd
+    vqnerf_release_amd.weights_changed()      # (a collective into `t.data` bumps no `_version`: the weight packs must not survive it)
 
 
 def assert_replicas_identical(tensors, what='parameters'):
