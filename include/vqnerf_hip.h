@@ -195,7 +195,8 @@ int vqn_brdf_shade_fwd_rows(const int64_t* lvis_rows, const float* xyz, const fl
  * vq_nfr.py:694-723): given g_sum_s = d loss / d (plain sum over lights) [N,3] per material set, returns
  * d loss / d albedo_s, spec_s [N,3], rough_s [N], and per-wave partials of d loss / d light
  * [vqn_brdf_shade_bwd_partials(N)][L][3] which the caller sums in order (deterministic, no float atomics).
- * Geometry (xyz, normal, rayo, lvis) is data and gets no gradient. */
+ * Geometry (xyz, normal, rayo, lvis) is data and gets no gradient.  N = 0 (a batch without a foreground point, which the forward
+ * accepts too): nothing per point, the vqn_brdf_shade_bwd_partials(0) partial rows are zeroed. */
 int64_t vqn_brdf_shade_bwd_partials(int64_t N);
 int vqn_brdf_shade_bwd(const float* xyz, const float* normal, const float* rayo, const float* lvis, const float* lxyz,
                        const float* lareas, const float* light, int64_t N, int L, int n_sets, const float* albedo0,

@@ -76,8 +76,9 @@ def make_model_params(seed=0, K=15, **kw):
     return p, specs
 
 
-def make_points(n, seed=1, lvis=True):
-    """SURVEY 8(d) synthetic surface points."""
+def make_points(n, seed=1, lvis=True, n_lights=512):
+    """SURVEY 8(d) synthetic surface points.  n_lights: width of the visibility rows (drawn last: every other array, and the rows
+    themselves at the default 512, are the same draws whatever the width)."""
     rng = np.random.default_rng(seed)
     xyz = rng.uniform(-1, 1, (n, 3))
     xyz = xyz / np.linalg.norm(xyz, axis=1, keepdims=True) * rng.uniform(0.5, 1.0, (n, 1))
@@ -88,7 +89,7 @@ def make_points(n, seed=1, lvis=True):
     out = dict(xyz=xyz.astype(np.float32), normal=normal.astype(np.float32), rayo=rayo.astype(np.float32),
                rgb=rgb.astype(np.float32))
     if lvis:
-        out['lvis'] = (rng.uniform(size=(n, 512)) < 0.7).astype(np.float32)
+        out['lvis'] = (rng.uniform(size=(n, n_lights)) < 0.7).astype(np.float32)
     return out
 
 
@@ -249,14 +250,17 @@ def normal_correct(normal, surf2c):
     return torch.where(cos >= 0, normal, -normal)
 
 
-def render_integrate(brdf, l, n, lareas, light, lvis=None, gamma=None):
-    """vq_nfr.py:694-723.  light [16,32,3] (already clipped >= 0).  gamma=(bias, index) for non-nerf data."""
+def render_integrate(brdf, l, n, lareas, light, lvis=None, gamma=None, clip=True):
+    """vq_nfr.py:694-723.  light [16,32,3] (already clipped >= 0).  gamma=(bias, index) for non-nerf data.
+    clip=False: the plain sum over the lights, before the gamma curve and the [0, 1] clip (what the kernels' raw = 1 writes)."""
     cos = torch.einsum('ijk,ik->ij', l, n)
     front = (cos > 0).to(cos.dtype)
     vis = front if lvis is None else front * lvis
     L = light.reshape(-1, 3)
     contrib = brdf * (vis[:, :, None] * L[None]) * cos[:, :, None] * lareas.reshape(1, -1, 1)
     rgb = contrib.sum(1)
+    if not clip:
+        return rgb
     if gamma is not None:
         rgb = (rgb * gamma[0]) ** gamma[1]
     return _clip01_pg(rgb)

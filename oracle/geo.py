@@ -183,6 +183,28 @@ def make_upsample_edge_inputs(n, seed=30):
     return o, d, z.astype(np.float32), sdf.astype(np.float32)
 
 
+def make_upsample_profiles(n, seed=40):
+    """The eight SDF profiles of `make_upsample_edge_inputs` for ANY n >= 2 (that function keeps 64 regular depths and so needs
+    n >= 64; its draws pin tests/golden/geo_upsample_edge.npz and are left alone): 8 rays x n sorted uniform depths in [2, 6];
+    profile 3 crosses zero after sample min(5, (n - 1) // 2)."""
+    rng = np.random.default_rng(seed + n)
+    o = np.tile(np.array([[0.0, 0.0, 4.0]], np.float32), (8, 1))
+    d = np.tile(np.array([[0.0, 0.0, -1.0]], np.float32), (8, 1))
+    d[0] = np.array([np.sin(1.0), 0.0, -np.cos(1.0)], np.float32)
+    z = np.sort(rng.uniform(2.0, 6.0, (8, n)).astype(np.float32), 1)
+    t = (z - 2.0) / 4.0
+    sdf = np.zeros((8, n), np.float32)
+    sdf[0] = rng.normal(0.0, 0.3, n)
+    sdf[1] = 5.0
+    sdf[2] = -5.0
+    sdf[3] = np.where(np.arange(n) <= min(5, (n - 1) // 2), 0.5, -0.5)
+    sdf[4] = 0.4 - 0.8 * t[4]
+    sdf[5] = np.where(np.arange(n) < n - 1, 0.3, -0.3)
+    sdf[6] = 0.25 * np.cos(4 * np.pi * t[6])
+    sdf[7] = np.convolve(rng.normal(0.0, 0.2, n + 8), np.ones(9) / 9.0, 'valid')
+    return o, d, z.astype(np.float32), sdf.astype(np.float32)
+
+
 def to_torch(params, dtype=torch.float32):
     return {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in params.items()}
 
@@ -338,6 +360,52 @@ def cat_z_vals(p_sdf, cfg, rays_o, rays_d, z_vals, new_z, sdf, last):
     return z_sorted, sdf, ties
 
 
+def composite(sdf, grads, rgb, inv_s, mid_z, dists, rays_o, rays_d, radius, cos_anneal_ratio=0.0, background_rgb=None):
+    """renderer.py:229-282, the compositing part of `render_core` on its own: alpha from the SDF and its gradient at the section
+    mid-points, transmittance, colour / surface point / depth and the eikonal term.  sdf [B*n,1] or [B,n], grads [B*n,3] or [B,n,3],
+    rgb [B,n,3], inv_s a scalar tensor (clipped to [1e-6, 1e6] here as at :229; the clip is idempotent, `render_core` hands over an
+    already clipped value), mid_z / dists [B,n].  dtype follows the inputs; differentiable in sdf, grads, rgb and inv_s.
+    Besides the quantities `render_core` returns: `true_cos`, `pts_r` (the arguments of the statement's kinks), `relax`, and the
+    per-ray numerator / denominator `gerr_num`, `gerr_den` [B] of `gradient_error`."""
+    B, n = mid_z.shape
+    pts = (rays_o[:, None, :] + rays_d[:, None, :] * mid_z[..., None]).reshape(-1, 3)
+    dirs = rays_d[:, None, :].expand(B, n, 3).reshape(-1, 3)
+    sdf = sdf.reshape(-1, 1)
+    grads = grads.reshape(-1, 3)
+    inv_s = inv_s.clip(1e-6, 1e6).reshape(1, 1)
+    true_cos = (dirs * grads).sum(-1, keepdim=True)
+    iter_cos = -(F.relu(-true_cos * 0.5 + 0.5) * (1.0 - cos_anneal_ratio)
+                 + F.relu(-true_cos) * cos_anneal_ratio)
+    d = dists.reshape(-1, 1)
+    est_next = sdf + iter_cos * d * 0.5
+    est_prev = sdf - iter_cos * d * 0.5
+    prev_cdf = torch.sigmoid(est_prev * inv_s)
+    next_cdf = torch.sigmoid(est_next * inv_s)
+    raw_alpha = ((prev_cdf - next_cdf + 1e-5) / (prev_cdf + 1e-5)).reshape(B, n)
+    alpha = raw_alpha.clip(0.0, 1.0)
+
+    pts_r = torch.linalg.norm(pts, ord=2, dim=-1).reshape(B, n)
+    inside = (pts_r < radius).to(sdf.dtype)
+    relax = (pts_r < radius * 1.1).to(sdf.dtype)
+
+    trans = torch.cumprod(torch.cat([torch.ones(B, 1, dtype=alpha.dtype), 1.0 - alpha + 1e-7], -1), -1)[:, :-1]
+    weights = alpha * trans
+    wsum = weights.sum(-1, keepdim=True)
+    color = (rgb * weights[..., None]).sum(1)
+    surf = (pts.reshape(B, n, 3) * weights[..., None]).sum(1)
+    depth = torch.linalg.norm(surf - rays_o, ord=2, dim=-1, keepdim=True)
+    if background_rgb is not None:
+        color = color + background_rgb * (1.0 - wsum)
+    g3 = grads.reshape(B, n, 3)
+    gerr = (torch.linalg.norm(g3, ord=2, dim=-1) - 1.0) ** 2
+    gerr_num, gerr_den = (relax * gerr).sum(-1), relax.sum(-1)
+    gerr = (relax * gerr).sum() / (relax.sum() + 1e-5)
+    return dict(color=color, weights=weights, weight_sum=wsum, weight_max=weights.max(-1, keepdim=True)[0], alpha=alpha,
+                raw_alpha=raw_alpha, cdf=prev_cdf.reshape(B, n), inside_sphere=inside, relax=relax, surf=surf, depth=depth,
+                gradients=g3, gradient_error=gerr, gerr_num=gerr_num, gerr_den=gerr_den, inv_s=inv_s,
+                true_cos=true_cos.reshape(B, n), pts_r=pts_r)
+
+
 def render_core(p_sdf, p_col, variance, cfg, rays_o, rays_d, z_vals, sample_dist, radius,
                 background_rgb=None, cos_anneal_ratio=0.0, create_graph=False, to_light=False):
     """renderer.py:193-297 (n_outside == 0 branch).  to_light: `sample_dist` is the per-ray [B,1] tensor of :302 (:211)."""
@@ -354,35 +422,13 @@ def render_core(p_sdf, p_col, variance, cfg, rays_o, rays_d, z_vals, sample_dist
     grads = sdf_gradient(p_sdf, cfg, pts, create_graph=create_graph)
     rgb = color_forward(p_col, cfg, pts, grads, dirs, feat).reshape(B, n, 3)
 
-    inv_s = inv_s_from_variance(variance).to(sdf.dtype).reshape(1, 1)
-    true_cos = (dirs * grads).sum(-1, keepdim=True)
-    iter_cos = -(F.relu(-true_cos * 0.5 + 0.5) * (1.0 - cos_anneal_ratio)
-                 + F.relu(-true_cos) * cos_anneal_ratio)
-    d = dists.reshape(-1, 1)
-    est_next = sdf + iter_cos * d * 0.5
-    est_prev = sdf - iter_cos * d * 0.5
-    prev_cdf = torch.sigmoid(est_prev * inv_s)
-    next_cdf = torch.sigmoid(est_next * inv_s)
-    alpha = ((prev_cdf - next_cdf + 1e-5) / (prev_cdf + 1e-5)).reshape(B, n).clip(0.0, 1.0)
-
-    pts_r = torch.linalg.norm(pts, ord=2, dim=-1).reshape(B, n)
-    inside = (pts_r < radius).to(sdf.dtype)
-    relax = (pts_r < radius * 1.1).to(sdf.dtype)
-
-    trans = torch.cumprod(torch.cat([torch.ones(B, 1, dtype=alpha.dtype), 1.0 - alpha + 1e-7], -1), -1)[:, :-1]
-    weights = alpha * trans
-    wsum = weights.sum(-1, keepdim=True)
-    color = (rgb * weights[..., None]).sum(1)
-    surf = (pts.reshape(B, n, 3) * weights[..., None]).sum(1)
-    depth = torch.linalg.norm(surf - rays_o, ord=2, dim=-1, keepdim=True)
-    if background_rgb is not None:
-        color = color + background_rgb * (1.0 - wsum)
-    g3 = grads.reshape(B, n, 3)
-    gerr = (torch.linalg.norm(g3, ord=2, dim=-1) - 1.0) ** 2
-    gerr = (relax * gerr).sum() / (relax.sum() + 1e-5)
+    c = composite(sdf, grads, rgb, inv_s_from_variance(variance).to(sdf.dtype), mid_z, dists, rays_o, rays_d, radius,
+                  cos_anneal_ratio, background_rgb)
+    inv_s, prev_cdf, alpha, inside, weights = c['inv_s'], c['cdf'], c['alpha'], c['inside_sphere'], c['weights']
+    color, surf, depth, g3, gerr = c['color'], c['surf'], c['depth'], c['gradients'], c['gradient_error']
     return dict(color=color, sdf=sdf, dists=dists, gradients=g3,
                 s_val=(1.0 / inv_s).expand(B * n, 1), mid_z_vals=mid_z, weights=weights,
-                cdf=prev_cdf.reshape(B, n), gradient_error=gerr, inside_sphere=inside,
+                cdf=prev_cdf, gradient_error=gerr, inside_sphere=inside,
                 surf=surf, depth=depth, sampled_color=rgb, alpha=alpha)
 
 

@@ -588,7 +588,15 @@ extern "C" int vqn_brdf_shade_bwd(const float* xyz, const float* normal, const f
                                   const float* g_sum1, float* g_albedo0, float* g_spec0, float* g_rough0,
                                   float* g_albedo1, float* g_spec1, float* g_rough1, float* g_light_partials,
                                   void* stream) {
-  VQN_CHECK_ARG(N >= 1, "N >= 1");
+  VQN_CHECK_ARG(N >= 0, "N >= 0");
+  if (N == 0) {
+    // a batch without a foreground point (the forward accepts it): no per-point adjoint to write, and the
+    // vqn_brdf_shade_bwd_partials(0) = 4 partial rows of g_light are zeros
+    VQN_CHECK_ARG(g_light_partials != nullptr, "null g_light_partials");
+    VQN_CHECK_SHAPE(L == 256 || L == 512 || L == 1024, "L must be 256, 512 or 1024 lights");
+    VQN_HIP(hipMemsetAsync(g_light_partials, 0, (size_t)vqn_brdf_shade_bwd_partials(0) * L * 3 * sizeof(float), (hipStream_t)stream));
+    return VQN_OK;
+  }
   VQN_CHECK_ARG(xyz && normal && rayo && lxyz && lareas && light && g_light_partials, "null geometry / light pointer");
   VQN_CHECK_ARG(n_sets == 1 || n_sets == 2, "n_sets must be 1 or 2");
   VQN_CHECK_ARG(albedo0 && spec0 && rough0 && g_sum0 && g_albedo0 && g_spec0 && g_rough0, "material set 0 pointers");
