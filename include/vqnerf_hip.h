@@ -346,6 +346,9 @@ int64_t vqn_neus_sdf_pack_plan(const int32_t* dims, int n_lin, int skip, int mul
 int64_t vqn_neus_col_pack_plan(int d_feature, int mode, int d_hidden, int n_layers, int d_out, int multires_view, int squeeze_out,
                                int feat_tiles, int f16s, int32_t* desc_out, int32_t* words_out, int64_t words_cap);
 
+/* The folded colour pack of the f32 inference path (vqn_neus_fold_pack: the SDF feature layer multiplied into the first colour
+ * layer, handed to vqn_neus_fine_points in place of the colour pack) is declared in its own header, include/vqn_neus_fold.h. */
+
 /* The whole inference path of vq_nfr.Model.call up to the shading (vq_nfr.py:534-692: encoder -> z -> continuous heads; l2-normalise
  * -> nearest code -> straight-through rows -> VQ heads) in ONE launch for K <= 64, z_dim = 256: program A (desc_a / wbuf_a: positional
  * encoding -> fine_enc -> bottleneck -> heads, z through output slot 0) leaves z in LDS, the VQ step runs on it with the arithmetic

@@ -1,8 +1,8 @@
-"""ctypes binding of libvqnerf_hip.so (include/vqnerf_hip.h).
+"""ctypes binding of libvqnerf_hip.so (include/vqnerf_hip.h, include/vqn_neus_fold.h).
 
 There is NO fallback: if the library is missing or a call fails this raises.  Tensors are passed as
 raw device pointers (tensor.data_ptr()) plus sizes; work is enqueued on torch's current HIP stream.
-This is the package's only door to the library: every entry point is declared in ABI and launched through _call.
+This is the package's only door to the library: every entry point is declared in ABI (ABI_FOLD) and launched through _call.
 """
 import contextlib
 import ctypes
@@ -49,6 +49,8 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
+# ... and the one function of include/vqn_neus_fold.h, in the same code (tests/test_neus_fold_binding.py holds it to that header)
+ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -72,7 +74,7 @@ def lib():
             raise VqnError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                            '(or `make -C vqnerf_release_amd/csrc`). There is no non-HIP fallback.')
         L = ctypes.CDLL(LIB_PATH)
-        for name, (ret, args) in ABI.items():
+        for name, (ret, args) in list(ABI.items()) + list(ABI_FOLD.items()):
             f = getattr(L, name)
             f.restype, f.argtypes = _CTYPES[ret], [_CTYPES[a] for a in args]
         _lib = L
@@ -457,6 +459,22 @@ def neus_fine_points(sdf_desc, wbuf_sdf, col_desc, wbuf_col, rays_o=None, rays_d
     _call(entry, sdp, _ptr(wbuf_sdf), cdp, _ptr(wbuf_col), _ptr(rays_o), _ptr(rays_d), _ptr(z), _ptr(pts), _ptr(dirs), P, S, _ptr(buf),
           buf.numel(), _ptr(sdf), _ptr(grad), _ptr(rgb))
     return sdf, grad, rgb
+
+
+def neus_fold_pack(sdf_desc, col_desc, wbuf_col, sdf_w_last, sdf_b_last, col_w0, col_b0):
+    """Folded colour pack of the f32 fine kernel (csrc/neus_fold.hip): (wbuf, desc) to hand to neus_fine_points in place of
+    (wbuf_col, col_desc).  sdf_w_last [1 + F, H] / sdf_b_last and col_w0 [C, extras + F] / col_b0: the effective weights the packs
+    were gathered from."""
+    for t in (wbuf_col, sdf_w_last, sdf_b_last, col_w0, col_b0):
+        _f32c(t, 'weight / bias')
+    (F1, H), C = sdf_w_last.shape, col_w0.shape[0]
+    sdp, cdp = _host(sdf_desc), _host(col_desc)
+    desc = np.zeros(len(col_desc), np.int32)
+    args = (sdp, cdp, _ptr(wbuf_col), wbuf_col.numel(), _ptr(sdf_w_last), _ptr(sdf_b_last), H, F1 - 1, _ptr(col_w0), _ptr(col_b0), C)
+    n = _call('vqn_neus_fold_pack', *args, None, 0, None, clock=False, count=True)
+    out = torch.empty((n,), dtype=torch.float32, device=wbuf_col.device)
+    _call('vqn_neus_fold_pack', *args, _ptr(out), n, desc.ctypes.data_as(ctypes.c_void_p), count=True)
+    return out, desc
 
 
 class NeusPackHandle:

@@ -414,7 +414,7 @@ __device__ __forceinline__ void tfmt_store_quad(float* __restrict__ T, const lon
   for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v[j], base + 64 * j);     // written once, read by later launches: past the L2-resident packs
 }
 
-template <bool FINE, bool TRAIN = false>
+template <bool FINE, bool TRAIN = false, bool FOLD = false>
 __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     const SdfDesc sd, const ColDesc cd, const f32x4* __restrict__ wsdf, const f32x4* __restrict__ wcol,
     const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ zv,
@@ -441,6 +441,11 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
   f32x4* save0 = FINE ? scratch + (size_t)blockIdx.x * 2 * per_img : nullptr;
 #endif
   const int feat_slot = (n_lin - 2) * 4 * MT;
+  // Folded colour input (csrc/neus_fold.hip, inference only): the GEMM at the feature layer's position runs on Wfold = Wc0[:, feat] . W8f
+  // and leaves P = Wfold . h + bfold in the stash slot of the features; colour layer 0 is then a K = extras GEMM on top of P.
+  // FOLD is chosen by the host from the descriptor (ColDesc::reserved1..3 != 0); the unfolded instance is the kernel as it was.
+  constexpr bool fold = FOLD;
+  static_assert(!FOLD || (FINE && !TRAIN), "the fold is an inference path: the backward and the weight gradients read OUTF");
   f32x4 pre[4];
   f32x4 nopre[4];
 
@@ -528,8 +533,9 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     rowdot<1>(ldsi, cur, hid_rows, wsdf + sd.last_w_off, sm->part[img], w4, lane);
     if (FINE && sd.layers[n_lin - 1].n_out_tiles > 0) {
       const LayerDesc L = sd.layers[n_lin - 1];
-      const f32x4* bp = wsdf + L.b_off;
-      gemm_tiles2<8>(lds, IS, KSegs{cur, hid_rows, 0, 0}, wsdf + L.w_off, L.n_out_tiles, wave, lane, nopre, false, nullptr,
+      const f32x4* bp = fold ? wcol + cd.reserved2 : wsdf + L.b_off;
+      gemm_tiles2<8>(lds, IS, KSegs{cur, hid_rows, 0, 0}, fold ? wcol + cd.reserved1 : wsdf + L.w_off,
+                     fold ? cd.layers[0].n_out_tiles : L.n_out_tiles, wave, lane, nopre, false, nullptr,
                      [&](int ot, int, f32x16& acc) { init_bias(bp, ot, lane, acc); },
                      [&](int ot, int im, int rq, const f32x16& acc) {
                        f32x4* sv = save0 + (size_t)im * per_img + (size_t)feat_slot * 64;
@@ -663,7 +669,7 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
       }
       const f32x4* sv = save0 + (size_t)img * per_img + (size_t)feat_slot * 64;
       const int feat_rows = 4 * sd.layers[n_lin - 1].n_out_tiles;
-      for (int r0 = w4; r0 < feat_rows; r0 += 32) {
+      for (int r0 = w4; r0 < (fold ? 0 : feat_rows); r0 += 32) {         // (unfolded) the feature rows back from the stash
         f32x4 v[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) v[c] = ld_stream(sv + min(r0 + 4 * c, feat_rows - 1) * 64 + lane);
@@ -675,7 +681,30 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
       FS(10)
       cur = X0; oth = Y0;
       int in_rows = feat_rows;
-      for (int l = 0; l < cd.n_lin - 1; ++l) {
+      if (fold) {                                   // colour layer 0 = relu(P + Wc0[:, extras] . extras): K = the extras rows only
+        const LayerDesc L = cd.layers[0];
+        const int dst = oth;
+        gemm_tiles2<8>(lds, IS, KSegs{E0, cd.extra_rows, 0, 0}, wcol + cd.reserved3, L.n_out_tiles, wave, lane, nopre, false, nullptr,
+                       [&](int ot, int im, f32x16& acc) {
+                         const f32x4* pp = save0 + (size_t)im * per_img + (size_t)feat_slot * 64 + ot * 256 + lane;
+#pragma unroll
+                         for (int rq = 0; rq < 4; ++rq) {
+                           const f32x4 v = ld_stream(pp + rq * 64);
+                           acc[4 * rq + 0] = v[0]; acc[4 * rq + 1] = v[1]; acc[4 * rq + 2] = v[2]; acc[4 * rq + 3] = v[3];
+                         }
+                       },
+                       [&](int ot, int im, int rq, const f32x16& acc) {
+                         f32x4* li = lds + (size_t)im * IS;
+                         f32x4 v = {acc[4 * rq], acc[4 * rq + 1], acc[4 * rq + 2], acc[4 * rq + 3]};
+#pragma unroll
+                         for (int j = 0; j < 4; ++j) v[j] = act_fwd<ACT_RELU>(v[j]);
+                         li[(dst + ot * 4 + rq) * 64 + lane] = v;
+                       });
+        __syncthreads();
+        const int t = cur; cur = oth; oth = t;
+        in_rows = 4 * L.n_out_tiles;
+      }
+      for (int l = fold ? 1 : 0; l < cd.n_lin - 1; ++l) {
         const LayerDesc L = cd.layers[l];
         const KSegs ks{cur, in_rows, E0, l == 0 ? cd.extra_rows : 0};
         const f32x4* bp = wcol + L.b_off;
@@ -857,12 +886,17 @@ extern "C" int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_s
     VQN_CHECK_SHAPE(cd.extra_feats >= 3 && cd.extra_feats <= 64 && cd.extra_rows >= 1 && cd.extra_rows <= 8, "colour net extras");
     for (int l = 0; l < cd.n_lin - 1; ++l)
       VQN_CHECK_SHAPE(cd.layers[l].n_out_tiles >= 1 && cd.layers[l].n_out_tiles <= sd.max_tiles, "colour layer wider than max_tiles");
+    // a folded colour pack (vqn_neus_fold_pack) announces its three blocks together; 0 = not folded
+    VQN_CHECK_ARG((cd.reserved1 > 0 && cd.reserved2 > cd.reserved1 && cd.reserved3 > cd.reserved2) ||
+                  (cd.reserved1 == 0 && cd.reserved2 == 0 && cd.reserved3 == 0), "col_desc: fold offsets (reserved1..3) inconsistent");
   }
   const long n_tiles = (P + 31) / 32;
   const int64_t per_wg = (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
   if (use_two_images(sd.max_tiles)) {
     const size_t lds2 = lds_bytes2(sd.max_tiles);
-    VQN_HIP(hipFuncSetAttribute((const void*)neus_points2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    const bool fold = cd.n_lin != 0 && cd.reserved1 > 0;
+    const auto kernel = fold ? neus_points2_kernel<true, false, true> : neus_points2_kernel<true>;
+    VQN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
     long grid = (long)vqn_num_cus();
     if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
 #ifdef VQN_DIAG_STASH_ROT
@@ -871,7 +905,7 @@ extern "C" int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_s
     if ((int64_t)grid * 2 * per_wg > scratch_bytes) grid = (long)(scratch_bytes / (2 * per_wg));
 #endif
     VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-    hipLaunchKernelGGL(neus_points2_kernel<true>, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
                        reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d,
                        z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb, TrainOut{});
     VQN_LAUNCH_CHECK();

@@ -15,6 +15,7 @@ take the torch-autograd statement of render_core instead -- loudly: a RuntimeWar
 The one random draw of the reference (`torch.rand([B,1]) - 0.5`, renderer.py:318) can be injected as
 `t_rand` so that fixtures and data-parallel ranks are reproducible.
 """
+import os
 import warnings
 
 import numpy as np
@@ -120,6 +121,7 @@ class NeuSRenderer:
         self.perturb = perturb
         self._u = {}
         self._engines = {}
+        self._fold = None                 # (wbuf_sdf, wbuf_col, folded colour buffer, folded descriptor): see _packs
         self._step_pack = None            # x3 packs of the training render in flight (NeusTrainEngine.prepare_step)
         self.weights_only = False         # True: no-graph renders skip the colour net (weights / weight_sum / surf stay exact)
         self.matrix_mode = 'f32'          # 'f16s': no-graph renders on the split-precision kernels (f16 hi/lo MFMA; ~1e-6 relative, opt-in)
@@ -127,10 +129,24 @@ class NeuSRenderer:
         self.last_train_backend = None    # path of the last graph-building render_core: 'hip' (tile programs) | 'torch'
 
     # ---- packs shared by all kernels --------------------------------------------------------
-    def _packs(self):
+    def _packs(self, fold=False):
+        """(wbuf_sdf, sdf_desc, wbuf_col, col_desc) of the current matrix mode.  fold=True (the no-graph f32 render): the colour pair is
+        the FOLDED one (csrc/neus_fold.hip: the SDF feature layer multiplied into the first colour layer, once per weight version).
+        The fold is derived from the two pack tensors it was built beside and rebuilt whenever either is -- so it goes stale with
+        exactly the events that invalidate them, no key of its own.  VQN_NEUS_FOLD=0: the unfolded pair (A/B runs)."""
         mt, mode = self.color_network.max_tiles(), self.matrix_mode
         wb_s, d_s = self.sdf_network.packs(max_tiles=mt, mode=mode)
         wb_c, d_c = self.color_network.packs(feat_tiles=self.sdf_network.plan(mode=mode).tiles[-1], mode=mode)
+        if fold and mode == 'f32' and os.environ.get('VQN_NEUS_FOLD', '1') != '0':
+            f = self._fold
+            if f is None or f[0] is not wb_s or f[1] is not wb_c:
+                sl = getattr(self.sdf_network, 'lin%d' % (self.sdf_network.num_layers - 2))
+                cl = self.color_network.lin0
+                with torch.no_grad():
+                    fw, fd = _C.neus_fold_pack(d_s, d_c, wb_c, sl.effective_weight().float().contiguous(), sl.bias.float().contiguous(),
+                                               cl.effective_weight().float().contiguous(), cl.bias.float().contiguous())
+                self._fold = f = (wb_s, wb_c, fw, fd)      # (the pack tensors themselves: an `is` on a live object cannot be recycled)
+            wb_c, d_c = f[2], f[3]
         return wb_s, d_s, wb_c, d_c
 
     def _quantiles(self, m, device):
@@ -215,7 +231,7 @@ class NeuSRenderer:
         B, n = z_vals.shape
         per_ray = sample_dist.reshape(-1).float().contiguous() if to_light else None
         mid_z, dists = _C.neus_section_mids(z_vals.contiguous(), 0.0 if to_light else float(sample_dist), per_ray)
-        wb_s, d_s, wb_c, d_c = self._packs()
+        wb_s, d_s, wb_c, d_c = self._packs(fold=not self.weights_only)
         if self.weights_only:
             # occupancy queries (gen_geo.py:231-242 uses nothing but weight_sum): the colour network is skipped
             no_col = np.zeros(packing.COL_DESC_INTS, np.int32)
