@@ -49,8 +49,9 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the one function of include/vqn_neus_fold.h, in the same code (tests/test_neus_fold_binding.py holds it to that header)
-ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp')}
+# ... and the functions of include/vqn_neus_fold.h (the fold pack and the mesh export), in the same code
+# (tests/test_neus_fold_binding.py holds them to that header)
+ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -626,6 +627,39 @@ def neus_composite_fwd(rays_o, rays_d, mid_z, dists, sdf, grad, rgb, inv_s, back
     if want_alpha:
         out['alpha'] = alpha
     return out
+
+
+# --------------------------------------------------------------------------------------
+# mesh export (csrc/marching_cubes.hip; geo/mesh.py)
+def _mc_field(u):
+    _f32c(u, 'u')
+    if u.dim() != 3:
+        raise VqnError(f'marching cubes: expected a field [nx, ny, nz], got shape {tuple(u.shape)}')
+    return tuple(int(s) for s in u.shape)
+
+
+def mc_classify(u, threshold):
+    """u [nx,ny,nz] -> (vert_count, tri_count) int32 [nx*ny*nz]: owned crossing edges per grid point, triangles per cell."""
+    nx, ny, nz = _mc_field(u)
+    vcount = torch.empty((u.numel(),), dtype=torch.int32, device=u.device)
+    tcount = torch.empty((u.numel(),), dtype=torch.int32, device=u.device)
+    _call('vqn_mc_classify', _ptr(u), nx, ny, nz, float(threshold), _ptr(vcount), _ptr(tcount))
+    return vcount, tcount
+
+
+def mc_emit(u, threshold, vert_offset, tri_offset, n_verts, n_tris, origin=None, step=None):
+    """The mesh of u = threshold from the exclusive prefix sums of mc_classify's counts and their totals -> (verts [V,3] f32,
+    tris [T,3] int32).  origin / step: three floats each (host), applied as index * step + origin on write."""
+    nx, ny, nz = _mc_field(u)
+    for t in (vert_offset, tri_offset):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != u.device or t.numel() != u.numel():
+            raise VqnError('mc_emit: offsets must be contiguous int32 tensors on the device of u, one entry per grid point')
+    verts = torch.empty((n_verts, 3), dtype=torch.float32, device=u.device)
+    tris = torch.empty((n_tris, 3), dtype=torch.int32, device=u.device)
+    _call('vqn_mc_emit', _ptr(u), nx, ny, nz, float(threshold), _ptr(vert_offset), _ptr(tri_offset), n_verts, n_tris,
+          None if origin is None else _host(origin, np.float32), None if step is None else _host(step, np.float32),
+          _ptr(verts) if n_verts else None, _ptr(tris) if n_tris else None)
+    return verts, tris
 
 
 # --------------------------------------------------------------------------------------

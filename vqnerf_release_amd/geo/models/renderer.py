@@ -1,5 +1,5 @@
 """NeuSRenderer on MI355X: host-side mirror of geo/NeuS-ours2/models/renderer.py:72-408 (same
-constructor, same `render(...)` keyword arguments, same 11 result keys, `extract_geometry`).
+constructor, same `render(...)` keyword arguments, same 11 result keys, `extract_geometry`: on the device, geo/mesh.py).
 
 Render / inference (no graph needed) is HIP end to end:
     vqn_neus_sdf_points  -> coarse SDF (renderer.py:337-338) and the SDF of each batch of new samples (:185)
@@ -412,5 +412,13 @@ class NeuSRenderer:
         }
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0):
+        """-> (vertices [V,3] in world coordinates, triangles [T,3]) as NumPy arrays (renderer.py:405-410 of the reference).  With the SDF
+        network on the GPU and a shape the fused SDF kernel covers, field and marching cubes run on the device (geo/mesh.py: f32
+        vertices, int32 triangles, one host read before the final copy); otherwise the reference's own route through `mcubes`."""
+        net = self.sdf_network
+        if next(net.parameters()).is_cuda and net._hip_supported():
+            from vqnerf_release_amd.geo import mesh
+            vertices, triangles = mesh.extract_geometry_device(bound_min, bound_max, resolution, threshold, net)
+            return vertices.cpu().numpy(), triangles.cpu().numpy()
         return extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold,
                                 query_func=lambda pts: -self.sdf_network.sdf(pts))

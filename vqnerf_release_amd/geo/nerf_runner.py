@@ -2,7 +2,7 @@
 `train` :99-175, cosine LR with warm-up :186-195, cos-anneal :180-184, checkpoint keys :210-232) on the MI355X
 classes, plus rank-sharded data parallelism (the reference trains on one GPU).
 
-Out of scope here: TensorBoard, mesh export.  The dataset is any object with the reference's
+Out of scope here: TensorBoard.  Mesh export: `validate_mesh` (geo/mesh.py).  The dataset is any object with the reference's
 dataset contract -- `n_images`, `max_radius`, `gen_random_rays_at(img_idx, batch_size) -> [B,10]` (o, d, rgb, mask) and
 `near_far_from_sphere(rays_o, rays_d)`: `models.nerfset.Dataset` when the conf's `dataset.data_dir` holds a Blender-format
 image set (as nerf_runner.py:36 does), `models.dtuset.Dataset` for a world_mat / scale_mat set (dtu_runner.py:36), `SyntheticDataset` (tests, bench) otherwise.
@@ -34,6 +34,8 @@ class SyntheticDataset:
         ang = torch.arange(self.n_images, dtype=torch.float32) * (2 * math.pi / max(self.n_images, 1))
         self.cam_o = torch.stack([4 * torch.sin(ang), torch.zeros_like(ang), 4 * torch.cos(ang)], -1).to(self.device)
         self.max_radius = 2.0
+        self.object_bbox_min = np.array([-1.1, -1.1, -1.1]) * self.max_radius      # as models/nerfset.py
+        self.object_bbox_max = np.array([1.1, 1.1, 1.1]) * self.max_radius
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
 
@@ -263,6 +265,8 @@ class Runner:
                 self.save_checkpoint()
             if self.val_freq > 0 and self.iter_step % self.val_freq == 0 and parallel.rank() == 0 and hasattr(self.dataset, 'gen_rays_at'):
                 self.validate_image()                         # nerf_runner.py:152-153
+            if self.val_mesh_freq > 0 and self.iter_step % self.val_mesh_freq == 0 and parallel.rank() == 0:
+                self.validate_mesh(world_space=True, resolution=512)       # nerf_runner.py:169-170
             if self.iter_step % len(perm) == 0:
                 perm = self.get_image_perm()
 
@@ -314,6 +318,21 @@ class Runner:
             a = arr[..., ::-1] if arr.ndim == 3 else arr         # (B, G, R) array -> RGB file, what cv.imwrite does
             Image.fromarray(np.ascontiguousarray(a)).save(os.path.join(base, name, '{:0>8d}_{}_{}.png'.format(self.iter_step, 0, idx)))
         return imgs
+
+    # ---- mesh export (nerf_runner.py:381-395) ----
+    @torch.no_grad()
+    def validate_mesh(self, world_space=False, resolution=64, threshold=0.0):
+        """The surface sdf = -threshold inside the dataset's object box on a resolution^3 grid, written to
+        `meshes/{iter:08d}.ply` under base_exp_dir (binary PLY, geo/mesh.py).  `world_space` is accepted and ignored: the reference
+        has that branch commented out.  Returns the path."""
+        from vqnerf_release_amd.geo import mesh
+        bound_min = torch.tensor(np.asarray(self.dataset.object_bbox_min), dtype=torch.float32)
+        bound_max = torch.tensor(np.asarray(self.dataset.object_bbox_max), dtype=torch.float32)
+        vertices, triangles = self.renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+        os.makedirs(os.path.join(self.base_exp_dir, 'meshes'), exist_ok=True)
+        path = os.path.join(self.base_exp_dir, 'meshes', '{:0>8d}.ply'.format(self.iter_step))
+        mesh.write_ply(path, vertices, triangles)
+        return path
 
     # ---- checkpoints: same keys / file names as nerf_runner.py:210-232 ----
     def save_checkpoint(self):
