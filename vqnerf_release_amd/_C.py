@@ -51,7 +51,8 @@ i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
 # ... and the functions of include/vqn_neus_fold.h (the fold pack and the mesh export), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
-ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp')}
+ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
+            'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -660,6 +661,39 @@ def mc_emit(u, threshold, vert_offset, tri_offset, n_verts, n_tris, origin=None,
           None if origin is None else _host(origin, np.float32), None if step is None else _host(step, np.float32),
           _ptr(verts) if n_verts else None, _ptr(tris) if n_tris else None)
     return verts, tris
+
+
+def _mesh_tris(triangles, what):
+    if triangles.dtype != torch.int32 or not triangles.is_contiguous() or not triangles.is_cuda or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise VqnError(f'{what}: expected contiguous int32 device triangles [T, 3], got {triangles.dtype} {tuple(triangles.shape)} '
+                       f'contiguous={triangles.is_contiguous()} device={triangles.device}')
+    return triangles.shape[0]
+
+
+def mesh_components(triangles, n_verts):
+    """triangles [T,3] int32 -> labels [n_verts] int32, labels[v] = the smallest vertex index of v's component (csrc/mesh_components.hip)."""
+    T = _mesh_tris(triangles, 'mesh_components')
+    labels = torch.empty((n_verts,), dtype=torch.int32, device=triangles.device)
+    _call('vqn_mesh_components', _ptr(triangles) if T else None, T, n_verts, _ptr(labels) if n_verts else None)
+    return labels
+
+
+def mesh_remap_tris(triangles, keep_tri, tri_offset, new_index, n_out):
+    """The triangles with keep_tri (bool / uint8 [T]) set, in order, at rows tri_offset (int32 [T], the exclusive prefix sum of
+    keep_tri; n_out its total), vertex ids rewritten through new_index (int32 [V]) -> [n_out, 3] int32."""
+    T = _mesh_tris(triangles, 'mesh_remap_tris')
+    keep_tri = keep_tri.view(torch.uint8) if keep_tri.dtype == torch.bool else keep_tri
+    for t, dt, n in ((keep_tri, torch.uint8, T), (tri_offset, torch.int32, T), (new_index, torch.int32, new_index.numel())):
+        if t.dtype != dt or not t.is_contiguous() or t.device != triangles.device or t.dim() != 1 or t.numel() != n:
+            raise VqnError('mesh_remap_tris: keep_tri (uint8) and tri_offset (int32) need one entry per triangle, new_index (int32) one '
+                           'per vertex, contiguous and on the device of the triangles')
+    if not 0 <= n_out <= T:
+        raise VqnError(f'mesh_remap_tris: n_out = {n_out} is not the size of a subset of {T} triangles')
+    out = torch.empty((n_out, 3), dtype=torch.int32, device=triangles.device)
+    if T and n_out:
+        _call('vqn_mesh_remap_tris', _ptr(triangles), T, _ptr(keep_tri), _ptr(tri_offset), _ptr(new_index) if new_index.numel() else None,
+              new_index.numel(), _ptr(out), n_out)
+    return out
 
 
 # --------------------------------------------------------------------------------------
