@@ -49,10 +49,12 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack and the mesh export), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack and the mesh export, dense and on bricks), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
-            'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp')}
+            'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
+            'vqn_mc_brick_points': ('i', 'pppiiiplllpp'), 'vqn_mc_brick_classify': ('i', 'pplpiiifppppp'),
+            'vqn_mc_brick_emit': ('i', 'pplpiiifppllppppp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -694,6 +696,82 @@ def mesh_remap_tris(triangles, keep_tri, tri_offset, new_index, n_out):
         _call('vqn_mesh_remap_tris', _ptr(triangles), T, _ptr(keep_tri), _ptr(tri_offset), _ptr(new_index) if new_index.numel() else None,
               new_index.numel(), _ptr(out), n_out)
     return out
+
+
+# mesh export on a sparse set of bricks (csrc/marching_cubes_bricks.hip; geo/mesh.py)
+BRICK_POINTS = 729            # stored points of a brick: 9^3
+
+
+def _mc_bricks(ub, brick_ijk, slot, dims):
+    """checks of the brick arguments -> (n_bricks, nx, ny, nz)"""
+    nx, ny, nz = (int(d) for d in dims)
+    n = brick_ijk.shape[0]
+    if brick_ijk.dtype != torch.int32 or not brick_ijk.is_contiguous() or not brick_ijk.is_cuda or tuple(brick_ijk.shape) != (n, 3):
+        raise VqnError(f'marching cubes on bricks: brick_ijk must be a contiguous int32 device tensor [n, 3], got {brick_ijk.dtype} '
+                       f'{tuple(brick_ijk.shape)} on {brick_ijk.device}')
+    if ub is not None:
+        _f32c(ub, 'ub')
+        if ub.numel() != n * BRICK_POINTS or ub.device != brick_ijk.device:
+            raise VqnError(f'marching cubes on bricks: ub must hold [n, 9, 9, 9] values for n = {n} bricks on the device of brick_ijk, '
+                           f'got shape {tuple(ub.shape)}')
+    if slot is not None:
+        n_slots = 1
+        for d in (nx, ny, nz):
+            n_slots *= max(1, -(-(d - 1) // 8))                          # (a dimension < 2 is the library's to refuse)
+        if slot.dtype != torch.int32 or not slot.is_contiguous() or slot.device != brick_ijk.device or slot.numel() != n_slots:
+            raise VqnError(f'marching cubes on bricks: slot must be a contiguous int32 tensor with one entry per brick of the grid '
+                           f'({n_slots}) on the device of brick_ijk')
+    return n, nx, ny, nz
+
+
+def mc_brick_points(axes, dims, brick_ijk, first, count):
+    """The stored points [first, first + count) of the bricks brick_ijk [n,3] (729 per brick, padding repeats the brick's last
+    point) as rows [count, 3] of the three device axis arrays `axes`."""
+    n, nx, ny, nz = _mc_bricks(None, brick_ijk, None, dims)
+    for a, d in zip(axes, (nx, ny, nz)):
+        _f32c(a, 'axis')
+        if a.numel() != d or a.device != brick_ijk.device:
+            raise VqnError('mc_brick_points: one contiguous f32 axis array of the grid\'s length per dimension, on the device of brick_ijk')
+    pts = torch.empty((count, 3), dtype=torch.float32, device=brick_ijk.device)
+    _call('vqn_mc_brick_points', _ptr(axes[0]), _ptr(axes[1]), _ptr(axes[2]), nx, ny, nz, _ptr(brick_ijk) if n else None, n, first, count,
+          _ptr(pts) if count else None)
+    return pts
+
+
+def mc_brick_classify(ub, brick_ijk, slot, dims, threshold):
+    """-> (vert_count, tri_count int32 [n * 729], keys int64 [n * 729]: the dense linear index of every owned point, INT64_MAX
+    elsewhere, leaks int32 [1]: (brick, face) pairs where the surface runs into a brick that is not in the list)."""
+    n, nx, ny, nz = _mc_bricks(ub, brick_ijk, slot, dims)
+    dev = brick_ijk.device
+    vcount = torch.empty((n * BRICK_POINTS,), dtype=torch.int32, device=dev)
+    tcount = torch.empty((n * BRICK_POINTS,), dtype=torch.int32, device=dev)
+    keys = torch.empty((n * BRICK_POINTS,), dtype=torch.int64, device=dev)
+    leaks = torch.empty((1,), dtype=torch.int32, device=dev)
+    _call('vqn_mc_brick_classify', _ptr(ub) if n else None, _ptr(brick_ijk) if n else None, n, _ptr(slot), nx, ny, nz, float(threshold),
+          _ptr(vcount) if n else None, _ptr(tcount) if n else None, _ptr(keys) if n else None, _ptr(leaks))
+    return vcount, tcount, keys, leaks
+
+
+def mc_brick_emit(ub, brick_ijk, slot, dims, threshold, vert_offset, tri_offset, n_verts, n_tris, origin=None, step=None, out=None):
+    """The mesh from the offsets (int32 [n * 729]: exclusive prefix sums of mc_brick_classify's counts taken in the order of its keys)
+    and their totals -> (verts [V,3] f32, tris [T,3] int32).  out = (verts, tris): write into these (at least that large) instead."""
+    n, nx, ny, nz = _mc_bricks(ub, brick_ijk, slot, dims)
+    for t in (vert_offset, tri_offset):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != ub.device or t.numel() != n * BRICK_POINTS:
+            raise VqnError('mc_brick_emit: offsets must be contiguous int32 tensors on the device of ub, 729 entries per brick')
+    if out is None:
+        verts = torch.empty((n_verts, 3), dtype=torch.float32, device=ub.device)
+        tris = torch.empty((n_tris, 3), dtype=torch.int32, device=ub.device)
+    else:
+        verts, tris = out
+        if (verts.dtype != torch.float32 or tris.dtype != torch.int32 or not verts.is_contiguous() or not tris.is_contiguous()
+                or verts.device != ub.device or tris.device != ub.device or verts.numel() < 3 * n_verts or tris.numel() < 3 * n_tris):
+            raise VqnError('mc_brick_emit: out = (f32 verts, int32 tris), contiguous, on the device of ub, at least [n_verts, 3] / [n_tris, 3]')
+    _call('vqn_mc_brick_emit', _ptr(ub) if n else None, _ptr(brick_ijk) if n else None, n, _ptr(slot), nx, ny, nz, float(threshold),
+          _ptr(vert_offset) if n else None, _ptr(tri_offset) if n else None, n_verts, n_tris,
+          None if origin is None else _host(origin, np.float32), None if step is None else _host(step, np.float32),
+          _ptr(verts) if n_verts else None, _ptr(tris) if n_tris else None)
+    return verts, tris
 
 
 # --------------------------------------------------------------------------------------

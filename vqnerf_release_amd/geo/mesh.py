@@ -7,6 +7,10 @@ An extraction reads the host once (the vertex and triangle totals, to size the o
 Clean-up and attributes, also on the device: connected components through csrc/mesh_components.hip
 (`components`, `filter_components`: one more host read), per-vertex normals and colours through the fused NeuS kernel
 (`vertex_normals`, `vertex_colors`), written by `write_ply` as nx ny nz / red green blue.
+
+The sparse route (`plan_bricks`, `marching_cubes_bricks`, `extract_geometry_sparse`; csrc/marching_cubes_bricks.hip) evaluates the
+network only on the 8^3-cell bricks the surface can pass through and returns the same bytes, also at resolutions the dense route
+refuses; it reads the host twice.
 """
 import numpy as np
 import torch
@@ -67,6 +71,168 @@ def extract_geometry_device(bound_min, bound_max, resolution, threshold, sdf_net
     b_min = bound_min.detach().cpu().numpy().astype(np.float64)
     b_max = bound_max.detach().cpu().numpy().astype(np.float64)
     return marching_cubes(u, threshold, origin=b_min, step=(b_max - b_min) / (resolution - 1.0))
+
+
+# ---- the sparse route: only the bricks the surface can pass through (csrc/marching_cubes_bricks.hip) --------
+BRICK = 8                     # cells per brick and axis; a brick stores (BRICK + 1)^3 points, its faces on both sides
+
+
+def plan_bricks(resolution, brick=BRICK, axes=None):
+    """How a grid of `resolution` points per axis (an int, or (nx, ny, nz)) is cut into bricks of `brick` cells.  Per axis a, as
+    integer NumPy arrays: nb[a] = ceil((n - 1) / brick) bricks; brick b stores the points lo[a][b] .. hi[a][b] = brick * b ..
+    min(brick * b + brick, n - 1) (the last brick is clipped to 1..brick cells; faces are stored on both sides); grid point i belongs
+    to brick owner[a][i] = min(i // brick, nb - 1), a cell to the brick of its minimum corner, so every point has one owner and every
+    cell lies in one brick with all 8 corners stored there; centre[a][b] = lo + (hi - lo) // 2 is the grid index of the brick's centre.
+    With axes (the three coordinate arrays of the grid, as _axes builds them on the host): h [nbx,nby,nbz] float32, the largest
+    distance from a brick's centre point to a stored corner of it, formed in float64 from those coordinates and rounded up."""
+    from types import SimpleNamespace
+    dims = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(d) for d in resolution)
+    brick = int(brick)
+    if len(dims) != 3 or min(dims) < 2 or brick < 1:
+        raise ValueError(f'plan_bricks: three dimensions >= 2 and brick >= 1, got {dims}, {brick}')
+    nb, lo, hi, centre, owner = [], [], [], [], []
+    for n in dims:
+        k = -(-(n - 1) // brick)
+        l = np.arange(k, dtype=np.int64) * brick
+        u = np.minimum(l + brick, n - 1)
+        nb.append(k); lo.append(l); hi.append(u); centre.append(l + (u - l) // 2)
+        owner.append(np.minimum(np.arange(n, dtype=np.int64) // brick, k - 1))
+    plan = SimpleNamespace(dims=dims, brick=brick, nb=tuple(nb), lo=lo, hi=hi, centre=centre, owner=owner, h=None)
+    if axes is not None:
+        d2 = []
+        for a in range(3):
+            x = np.asarray(axes[a], dtype=np.float64)
+            d2.append(np.maximum(np.abs(x[lo[a]] - x[centre[a]]), np.abs(x[hi[a]] - x[centre[a]])) ** 2)
+        h64 = np.sqrt(d2[0][:, None, None] + d2[1][None, :, None] + d2[2][None, None, :])
+        h32 = h64.astype(np.float32)
+        # up: one float32 step wherever the rounded value is not already above (which also covers the roundings of the float64 sum)
+        plan.h = np.where(h32.astype(np.float64) > h64, h32, np.nextafter(h32, np.float32(np.inf)))
+    return plan
+
+
+def _brick_grid(dims):
+    """-> (dims, bricks per axis); dimensions < 2 are left to the library to refuse (they count as one brick here)"""
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3:
+        raise _C.VqnError(f'marching cubes on bricks: three dimensions, got {dims}')
+    nb = tuple(max(1, -(-(d - 1) // BRICK)) for d in dims)
+    if nb[0] * nb[1] * nb[2] >= 1 << 31:
+        raise _C.VqnError(f'marching cubes on bricks: the brick grid {nb} must have < 2^31 entries')
+    return dims, nb
+
+
+def _mark(marks, name):
+    """stage boundary for scripts/probe_mesh_sparse.py: (name of the stage that ends here, a recorded HIP event)"""
+    if marks is not None:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        marks.append((name, e))
+
+
+def brick_offsets(ub, brick_ijk, dims, threshold, marks=None):
+    """The classify half of marching_cubes_bricks -> (slot, vert_offset, tri_offset, n_verts, n_tris, leaks): the slot map of the
+    list, the exclusive prefix sums of the counts in the dense order (int32 [n * 729], stored at the brick entries), both totals and
+    the leak count.  One device sort of the owned points' int64 keys, two prefix sums, ONE host read."""
+    dims, nb = _brick_grid(dims)
+    n = brick_ijk.shape[0]
+    if n * _C.BRICK_POINTS >= 1 << 31:
+        raise _C.VqnError(f'marching cubes on bricks: {n} bricks: n * 729 must be < 2^31')
+    dev = ub.device
+    b = brick_ijk.long()
+    lin = ((b[:, 0] * nb[1] + b[:, 1]) * nb[2] + b[:, 2]).clamp_(0, nb[0] * nb[1] * nb[2] - 1)     # (a row outside the grid: caller error)
+    slot = torch.full((nb[0] * nb[1] * nb[2],), -1, dtype=torch.int32, device=dev)
+    slot[lin] = torch.arange(n, dtype=torch.int32, device=dev)
+    vcount, tcount, keys, leaks = _C.mc_brick_classify(ub, brick_ijk, slot, dims, threshold)
+    _mark(marks, 'classify')
+    # the dense order: owned points by linear index (entries that are no owned point sort last and count nothing)
+    order = torch.argsort(keys)
+    del keys
+    vs, ts = vcount[order].long(), tcount[order].long()
+    vinc, tinc = torch.cumsum(vs, 0), torch.cumsum(ts, 0)
+    n_verts, n_tris, n_leaks = torch.stack([vinc[-1], tinc[-1], leaks[0].long()]).tolist()      # the one host read
+    if n_verts >= 1 << 31 or 3 * n_tris >= 1 << 31:
+        raise _C.VqnError(f'marching cubes on bricks: {n_verts} vertices / {n_tris} triangles do not fit int32 indices')
+    voff, toff = vcount, tcount                                                                   # (reused) back in brick order
+    voff[order] = vinc.sub_(vs).to(torch.int32)
+    toff[order] = tinc.sub_(ts).to(torch.int32)
+    _mark(marks, 'sort_and_sums')
+    return slot, voff, toff, n_verts, n_tris, n_leaks
+
+
+def marching_cubes_bricks(ub, brick_ijk, dims, threshold, origin=None, step=None, marks=None):
+    """marching_cubes of the field on a grid of dims = (nx, ny, nz) points, from its values on a list of bricks alone ->
+    (verts, tris, leaks).  brick_ijk [n,3] int32 (device): brick coordinates, sorted by brick linear index, each once; ub [n,9,9,9]
+    f32: the field on each brick's stored points (plan_bricks; entries past a clipped brick's extent are never read).  If every
+    cell the surface passes through lies in a listed brick, verts and tris equal marching_cubes(u, threshold, origin, step) of the
+    dense field bit for bit, in its order.  leaks (an int) counts the (brick, face) pairs where the surface runs into a brick that is
+    not listed; with leaks > 0 the mesh is not the dense one (triangles at such a face hold index 0 in place of the missing vertex).
+    One host read (both totals and leaks, in one copy).  marks: a list that receives (stage, HIP event) at every stage boundary."""
+    _C.require_device(ub, 'marching_cubes_bricks')
+    ub = ub.detach()
+    if (origin is None) != (step is None):
+        raise _C.VqnError('marching_cubes_bricks: origin and step come together')
+    if brick_ijk.shape[0] == 0:
+        _brick_grid(dims)
+        return (torch.empty((0, 3), dtype=torch.float32, device=ub.device), torch.empty((0, 3), dtype=torch.int32, device=ub.device), 0)
+    slot, voff, toff, n_verts, n_tris, leaks = brick_offsets(ub, brick_ijk, dims, threshold, marks)
+    verts, tris = _C.mc_brick_emit(ub, brick_ijk, slot, dims, threshold, voff, toff, n_verts, n_tris, origin, step)
+    _mark(marks, 'emit')
+    return verts, tris, leaks
+
+
+@torch.no_grad()
+def extract_geometry_sparse(bound_min, bound_max, resolution, threshold, sdf_network, lipschitz=2.0, marks=None):
+    """extract_geometry_device through the bricks the surface can pass through alone -> (vertices, triangles, info), the same bytes.
+
+    u = -sdf is evaluated at every brick's centre point c; a brick is active iff |u(c) - threshold| <= lipschitz * h, h the largest
+    distance from c to a stored point of the brick (plan_bricks).  If |sdf(x) - sdf(y)| <= lipschitz |x - y| an inactive brick has all
+    its points on one side and owns no vertex and no triangle, so meshing the active bricks gives the dense mesh.  The field is then
+    evaluated on the active bricks' points only.  Should the bound not hold -- the surface runs from an active brick into an inactive
+    one -- VqnError is raised and no mesh returned; what cannot be seen is a closed piece lying wholly inside inactive bricks, which the
+    premise excludes.  info = dict(bricks_total, bricks_active, points_evaluated, leaks).  Host reads: the active count, then the
+    totals with the leak count.  marks: as marching_cubes_bricks."""
+    device = next(sdf_network.parameters()).device
+    R = int(resolution)
+    _mark(marks, 'start')
+    axes_host = [torch.linspace(bound_min[a], bound_max[a], R) for a in range(3)]                # as _axes
+    X, Y, Z = [a.to(device) for a in axes_host]
+    plan = plan_bricks(R, BRICK, axes=[a.numpy() for a in axes_host])
+    dims, nb = _brick_grid(plan.dims)
+    n_total = nb[0] * nb[1] * nb[2]
+    cx, cy, cz = [torch.from_numpy(c).to(device) for c in plan.centre]
+    uc = torch.empty((n_total,), dtype=torch.float32, device=device)
+    for s in range(0, n_total, FIELD_SLAB):
+        lin = torch.arange(s, min(s + FIELD_SLAB, n_total), device=device)
+        bij = torch.div(lin, nb[2], rounding_mode='floor')
+        pts = torch.stack([X[cx[torch.div(bij, nb[1], rounding_mode='floor')]], Y[cy[bij % nb[1]]], Z[cz[lin % nb[2]]]], -1)
+        uc[s: s + pts.shape[0]] = sdf_network.sdf(pts).reshape(-1)
+    uc.neg_()
+    h = torch.from_numpy(plan.h).to(device).reshape(-1)
+    active = (uc.double() - float(threshold)).abs() <= float(lipschitz) * h.double()
+    lin = torch.nonzero(active).reshape(-1)                                                       # host read: the active count
+    n = lin.shape[0]
+    _mark(marks, 'centres')
+    info = dict(bricks_total=n_total, bricks_active=n, points_evaluated=n_total + n * _C.BRICK_POINTS, leaks=0)
+    if n * _C.BRICK_POINTS >= 1 << 31:
+        raise _C.VqnError(f'extract_geometry_sparse: {n} active bricks: n * 729 must be < 2^31; lower lipschitz = {lipschitz} or the resolution')
+    bij = torch.div(lin, nb[2], rounding_mode='floor')
+    brick_ijk = torch.stack([torch.div(bij, nb[1], rounding_mode='floor'), bij % nb[1], lin % nb[2]], -1).to(torch.int32).contiguous()
+    ub = torch.empty((n * _C.BRICK_POINTS,), dtype=torch.float32, device=device)
+    _mark(marks, 'brick_list')
+    for s in range(0, n * _C.BRICK_POINTS, FIELD_SLAB):
+        pts = _C.mc_brick_points((X, Y, Z), dims, brick_ijk, s, min(FIELD_SLAB, n * _C.BRICK_POINTS - s))
+        ub[s: s + pts.shape[0]] = sdf_network.sdf(pts).reshape(-1)
+    _mark(marks, 'brick_field')
+    ub = ub.neg_().reshape(n, BRICK + 1, BRICK + 1, BRICK + 1)
+    b_min = bound_min.detach().cpu().numpy().astype(np.float64)
+    b_max = bound_max.detach().cpu().numpy().astype(np.float64)
+    vertices, triangles, leaks = marching_cubes_bricks(ub, brick_ijk, dims, threshold, origin=b_min, step=(b_max - b_min) / (R - 1.0),
+                                                       marks=marks)
+    info['leaks'] = leaks
+    if leaks:
+        raise _C.VqnError(f'extract_geometry_sparse: the surface runs into a skipped brick at {leaks} brick faces: the field changes '
+                          f'faster than lipschitz = {lipschitz} allows; raise lipschitz')
+    return vertices, triangles, info
 
 
 # ---- clean-up: connected components ----------------------------------------------------------------------------------------------

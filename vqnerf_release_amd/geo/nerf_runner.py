@@ -322,25 +322,29 @@ class Runner:
     # ---- mesh export (nerf_runner.py:381-395) ----
     @torch.no_grad()
     def validate_mesh(self, world_space=False, resolution=64, threshold=0.0, keep_largest=None, min_faces=None, normals=False,
-                      colors=False):
+                      colors=False, sparse=False, lipschitz=2.0):
         """The surface sdf = -threshold inside the dataset's object box on a resolution^3 grid, written to
         `meshes/{iter:08d}.ply` under base_exp_dir (binary PLY, geo/mesh.py).  `world_space` is accepted and ignored: the reference
         has that branch commented out.  keep_largest / min_faces drop small connected pieces (mesh.filter_components); normals /
-        colors add per-vertex nx ny nz / red green blue (mesh.vertex_normals, mesh.vertex_colors).  All four run on the device and
-        raise VqnError where the mesh would come from `mcubes` (a CPU network, an unsupported shape).  Returns the path."""
+        colors add per-vertex nx ny nz / red green blue (mesh.vertex_normals, mesh.vertex_colors); sparse evaluates the network only
+        on the bricks the surface can pass through, given |grad sdf| <= lipschitz (mesh.extract_geometry_sparse: the same file).  All
+        five run on the device and raise VqnError where the mesh would come from `mcubes` (a CPU network, an unsupported shape).
+        Returns the path."""
         from vqnerf_release_amd.geo import mesh
         bound_min = torch.tensor(np.asarray(self.dataset.object_bbox_min), dtype=torch.float32)
         bound_max = torch.tensor(np.asarray(self.dataset.object_bbox_max), dtype=torch.float32)
         nrm = col = None
         if normals or colors:
-            vertices, triangles = self.renderer.extract_geometry_device(bound_min, bound_max, resolution, threshold, keep_largest, min_faces)
+            vertices, triangles = self.renderer.extract_geometry_device(bound_min, bound_max, resolution, threshold, keep_largest, min_faces,
+                                                                        sparse=sparse, lipschitz=lipschitz)
             if normals:
                 nrm = mesh.vertex_normals(vertices, self.renderer.sdf_network)
             if colors:
                 col = mesh.vertex_colors(vertices, self.renderer.sdf_network, self.renderer.color_network)
         else:
             vertices, triangles = self.renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold,
-                                                                 keep_largest=keep_largest, min_faces=min_faces)
+                                                                 keep_largest=keep_largest, min_faces=min_faces, sparse=sparse,
+                                                                 lipschitz=lipschitz)
         os.makedirs(os.path.join(self.base_exp_dir, 'meshes'), exist_ok=True)
         path = os.path.join(self.base_exp_dir, 'meshes', '{:0>8d}.ply'.format(self.iter_step))
         mesh.write_ply(path, vertices, triangles, normals=nrm, colors=col)
