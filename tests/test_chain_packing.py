@@ -237,7 +237,7 @@ def test_split_precision_programs_match_oracle():
         want = od.mlp_forward(ptn, specs[n], torch.tensor(z, dtype=torch.float64)).numpy()
         np.testing.assert_allclose(g, want, rtol=0, atol=3e-6 * max(1.0, np.abs(want).max()))
     with pytest.raises(ValueError):
-        pk.split_pack(torch.full((1, 1, 64, 8), 7.0e4))
+        pk.LAYOUTS['f16s'].split(torch.full((1, 1, 64, 8), 7.0e4))
 
 
 # ------------------------------------------------------------------ NeuS pack plans in split-precision mode

@@ -37,9 +37,9 @@ def fold_reference(w8, b8, wc0, bc0, extra):
     C, H = wf.shape
     take = lambda m, ix: np.concatenate([np.asarray(m, np.float64).reshape(-1), [0.0]])[ix].reshape(-1)
     hid_rows = 4 * ((H + 31) // 32)
-    blk_w = take(wf, packing.gemm_index(C, H, [(hid_rows, packing.ident_cols(H))]))
-    blk_b = take(bf, packing.bias_index(C))
-    blk_e = take(wc0, packing.gemm_index(C, wc0.shape[1], [(packing.emb_rows_for(extra), packing.ident_cols(extra))]))
+    blk_w = take(wf, packing.F32.gemm_index(C, H, [(hid_rows, H, 0)]))
+    blk_b = take(bf, packing.F32.bias_index(C))
+    blk_e = take(wc0, packing.F32.gemm_index(C, wc0.shape[1], [(packing.F32.rows_for(extra), extra, 0)]))
     return blk_w, blk_b, blk_e
 
 
@@ -94,7 +94,7 @@ def test_reference_blocks_have_the_pack_layout():
     wc0, bc0 = rng.normal(size=(C, extra + F)).astype(np.float32), rng.normal(size=C).astype(np.float32)
     blk_w, blk_b, blk_e = fold_reference(w8, b8, wc0, bc0, extra)
     wf, bf = fold64(w8, b8, wc0, bc0, extra)
-    nt, hid_rows, er = 2, 12, packing.emb_rows_for(extra)
+    nt, hid_rows, er = 2, 12, packing.F32.rows_for(extra)
     assert blk_w.shape == (nt * hid_rows * 256,) and blk_b.shape == (nt * 32,) and blk_e.shape == (nt * er * 256,)
     W = blk_w.reshape(nt, hid_rows, 64, 4)
     E = blk_e.reshape(nt, er, 64, 4)

@@ -1,9 +1,9 @@
 """Host-side layer programs + weight packs for the generic fused Dense-stack kernel (csrc/mlp_chain.hip,
-descriptor layout include/vqn_chain_desc.h).  Activation-image / A-fragment layouts are those of geo/packing.py.
+descriptor layout include/vqn_chain_desc.h).  Activation-image / A-fragment layouts are the engine layouts of geo/packing.py
+(`LAYOUTS`, described once in that module's docstring): nothing here restates them.
 
-`ChainBuilder(mode='f16s')` builds the same programs for the split-precision kernel (csrc/mlp_chain_f16s.hip, layouts in
-csrc/mlp_prims_f16s.h): K segments advance in 16-feature steps (row pairs hi / lo), weights are packed as f16 hi / lo
-fragments (same bytes, same offsets), biases in accumulator-register order.
+`ChainBuilder(mode='f16s')` builds the same programs for the split-precision kernel (csrc/mlp_chain_f16s.hip): same programs,
+same offsets, the F16S layout instead of the F32 one.
 
 A program is built once per network shape with `ChainBuilder`; `ChainPlan.pack(params)` then gathers the
 current Keras-layout weights (`kernel [in, out]`, `bias [out]`) into one flat device buffer -- a pure index
@@ -12,8 +12,7 @@ gather, cheap enough to redo after every optimiser step.
 import numpy as np
 import torch
 
-from vqnerf_release_amd.geo import packing as geo_packing
-from vqnerf_release_amd.geo.packing import gemm_index, bias_index, ident_cols, _take
+from vqnerf_release_amd.geo.packing import LAYOUTS, _take
 
 MAX_LAYERS = 16
 MAX_OUTS = 4
@@ -24,57 +23,17 @@ LATE_EPILOGUE = 0x100          # ChainLayer.act bit 8: barrier between the K loo
 
 
 class Region:
-    """`feats` features of 32 points held in LDS rows [row0, row0 + rows) (8 features per row); a GEMM output
+    """`feats` features of 32 points held in LDS rows [row0, row0 + rows) (the engine layout's rows for them); a GEMM output
     occupies whole 32-feature tiles (`alloc_rows`), of which only the first `rows` need to be read as K."""
 
     def __init__(self, row0, feats, alloc_rows=None, mode='f32'):
         self.row0, self.feats = row0, feats
-        self.rows = (feats + 7) // 8 if mode == 'f32' else 2 * ((feats + 15) // 16)
+        self.rows = LAYOUTS[mode].rows_for(feats)
         self.alloc_rows = alloc_rows if alloc_rows is not None else self.rows
 
     @property
     def end(self):
         return self.row0 + self.rows
-
-
-def _rowdot_index_segs(n_out, n_cols, segs):
-    """[n_out, sum(rows), 2, 4] gather index into M[n_out, n_cols].flatten() ++ [0]; segs = [(rows, feats, col_base)]."""
-    cols = []
-    for rows, feats, base in segs:
-        r = np.arange(rows)[:, None, None]
-        h = np.arange(2)[None, :, None]
-        j = np.arange(4)[None, None, :]
-        f = 32 * (r >> 2) + 2 * (4 * (r & 3) + j) + h
-        cols.append(np.where(f < feats, f + base, -1))
-    col = np.concatenate(cols, 0)                                     # [R,2,4]
-    o = np.arange(n_out)[:, None, None, None]
-    colb = np.broadcast_to(col[None], (n_out,) + col.shape)
-    return np.where(colb >= 0, o * n_cols + colb, n_out * n_cols).astype(np.int64)
-
-
-def _step_feat(n_rows):
-    return geo_packing.step_features(n_rows)
-
-
-def gemm_index_f16s(n_out, n_cols, segs):
-    """segs = [(rows, feats, col_base)] -> geo.packing.gemm_index_f16s (A operand of v_mfma_f32_32x32x16_f16, whole 4-step blocks)."""
-    return geo_packing.gemm_index_f16s(n_out, n_cols, [(rows, ident_cols(feats, base=base)) for rows, feats, base in segs])
-
-
-bias_index_f16s = geo_packing.bias_index_f16s
-split_pack = geo_packing.split_pack
-
-
-def _rowdot_index_segs_f16s(n_out, n_cols, segs):
-    """[n_out, n_steps, 2, 8] f32 image of M's rows in split-image order."""
-    cols = []
-    for rows, feats, base in segs:
-        f = _step_feat(rows)[:, ::32, :]                              # lanes 0 and 32 -> h = 0, 1
-        cols.append(np.where(f < feats, f + base, -1))
-    col = np.concatenate(cols, 0)                                     # [S,2,8]
-    o = np.arange(n_out)[:, None, None, None]
-    colb = np.broadcast_to(col[None], (n_out,) + col.shape)
-    return np.where(colb >= 0, o * n_cols + colb, n_out * n_cols).astype(np.int64)
 
 
 class ChainBuilder:
@@ -100,7 +59,7 @@ class ChainBuilder:
         with 4 waves).  Saves the rows of one region, which is what lets the head programs keep their input resident."""
         assert 1 <= len(segs) <= 2
         tiles = (out_feats + 31) // 32
-        dst = Region(None, out_feats, alloc_rows=4 * tiles, mode=self.mode)
+        dst = Region(None, out_feats, alloc_rows=LAYOUTS[self.mode].rows_per_tile * tiles, mode=self.mode)
         if over is not None:
             assert any(over is s_ for s_ in segs) and tiles <= 4 and 4 * tiles <= over.alloc_rows and self.mode == 'f32'
         self.layers.append(dict(kind=0, key=key, segs=list(segs), out=out_feats, act=ACT[act] | (LATE_EPILOGUE if over is not None else 0),
@@ -194,6 +153,7 @@ class ChainPlan:
         lds = self.total_rows * 1024 + 8 * 32 * 4 * 4 + 16 * self.small_w4
         assert lds <= 160 * 1024, f'program needs {lds} B of LDS'
         self.n_waves = 4 if 2 * lds <= 160 * 1024 else 8
+        self.layout = LAYOUTS[b.mode]
         self.gather = []
         for L in self.layers:
             in_feats = sum(s.feats for s in L['segs'])
@@ -201,25 +161,15 @@ class ChainPlan:
                 L['k_rows'], L['in_feats'] = [], 0
                 self.gather.append((None, None))
                 continue
-            if L['kind'] == 0 and b.mode == 'f32':
-                segs, base = [], 0
-                for s in L['segs']:
-                    segs.append((s.rows, ident_cols(s.feats, base=base)))
-                    base += s.feats
-                L['k_rows'] = [sg[0] for sg in segs]
-                self.gather.append((gemm_index(L['out'], in_feats, segs), bias_index(L['out'])))
+            segs, base = [], 0
+            for s in L['segs']:                                      # Keras concat order: each segment's columns follow the one before
+                segs.append((s.rows, s.feats, base))
+                base += s.feats
+            L['k_rows'] = [sg[0] for sg in segs]
+            if L['kind'] == 0:
+                self.gather.append((self.layout.gemm_index(L['out'], in_feats, segs), self.layout.bias_index(L['out'])))
             else:
-                segs, base = [], 0
-                for s in L['segs']:
-                    segs.append((s.rows, s.feats, base))
-                    base += s.feats
-                L['k_rows'] = [sg[0] for sg in segs]
-                if L['kind'] == 0:
-                    self.gather.append((gemm_index_f16s(L['out'], in_feats, segs), bias_index_f16s(L['out'])))
-                elif b.mode == 'f16s':
-                    self.gather.append((_rowdot_index_segs_f16s(L['out'], in_feats, segs), None))
-                else:
-                    self.gather.append((_rowdot_index_segs(L['out'], in_feats, segs), None))
+                self.gather.append((self.layout.rowdot_index(L['out'], in_feats, segs), None))
             L['in_feats'] = in_feats
         self._dev = {}
 
@@ -251,8 +201,8 @@ class ChainPlan:
             assert tuple(W.shape) == (L['in_feats'], L['out']), (L['key'], tuple(W.shape), (L['in_feats'], L['out']))
             M = W.t().contiguous()                                  # [out, in]
             c = _take(M, wi)
-            if b.mode == 'f16s' and L['kind'] == 0:
-                c = split_pack(c.reshape(wi.shape))
+            if L['kind'] == 0:
+                c = self.layout.split(c.reshape(wi.shape))
             w_off = off // 4
             chunks.append(c); off += c.numel()
             b_off = -1

@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from vqnerf_release_amd import _C
-from vqnerf_release_amd.geo import packing
-from vqnerf_release_amd.geo.train_programs import FlatLayout, WgradBatch, _ident
+from vqnerf_release_amd.geo.packing import X3, FlatLayout, GatherPack
+from vqnerf_release_amd.geo.train_programs import WgradBatch
 
 ACTS = {None: 0, 'relu': 1, 'sigmoid': 3}
 RT_MAX_L, RT_MAX_H = 8, 3
@@ -124,27 +124,12 @@ class ReflStackEngine:
         if self._dev is not None:
             return self._dev
         L = self.layout()
-        chunks, off, fch, foff = [], [0], [], [0]
-
-        def add(view, idx):                                   # -> float4 offset inside the PIECE pack (192 float4 per tile and K step)
-            src = np.append(np.ascontiguousarray(view).reshape(-1), L.zero)
-            c = src[idx.reshape(-1)]
-            o4 = off[0]
-            chunks.append(c)
-            off[0] += (c.size // 512) * 192
-            return o4
-
-        def addf(view, idx):                                  # -> float4 offset inside the f32 image buffer
-            src = np.append(np.ascontiguousarray(view).reshape(-1), L.zero)
-            c = src[idx.reshape(-1)]
-            assert c.size % 4 == 0
-            o4 = foff[0] // 4
-            fch.append(c)
-            foff[0] += c.size
-            return o4
-
-        gx = packing.gemm_index_x3
-        emb_rows = packing.emb_rows_for_x3(self.E) if self.nE else 0
+        mats, thin = GatherPack(L, pieces=True), GatherPack(L)     # the piece pack of the GEMM matrices, the f32 image buffer
+        # the three kinds of image: an A-fragment matrix, a vector in accumulator order, the rows of a thin matrix in activation order
+        gemm = lambda view, n_out, n_cols, segs=None: mats.add(view, X3.gemm_index(n_out, n_cols, segs))
+        bias = lambda view, n: thin.add(view, X3.bias_index(n))
+        rowdot = lambda view, n_out, n: thin.add(view, X3.rowdot_index(n_out, n))
+        emb_rows = X3.rows_for(self.E) if self.nE else 0
         d = np.zeros(DESC_INTS, np.int32)
         skip = 0
         for l, Ly in enumerate(self.layers):
@@ -157,19 +142,18 @@ class ReflStackEngine:
         for l, Ly in enumerate(self.layers):
             n_in = Ly['in_y'] + (self.E if Ly['skip'] else 0)
             if l == 0:
-                segs = [(emb_rows, _ident(self.E))]
+                segs = [(emb_rows, self.E, 0)]
             elif Ly['skip']:
-                segs = [(6 * _tl(Ly['in_y']), _ident(Ly['in_y'])), (emb_rows, _ident(self.E, base=Ly['in_y']))]
+                segs = [X3.tile_seg(Ly['in_y']), (emb_rows, self.E, Ly['in_y'])]
             else:
-                segs = [(6 * _tl(Ly['in_y']), _ident(Ly['in_y']))]
+                segs = None
             d[o_te + l], d[o_act + l] = _tl(Ly['out']), Ly['act']
-            d[o_w + l] = add(L['W%d' % l].T, gx(Ly['out'], n_in, segs))
-            d[o_b + l] = addf(L['b%d' % l], packing.bias_index_f16s(Ly['out']))
+            d[o_w + l] = gemm(L['W%d' % l].T, Ly['out'], n_in, segs)
+            d[o_b + l] = bias(L['b%d' % l], Ly['out'])
             if l >= 1:                                        # backward: delta_{l-1} = W_l[y part] delta_l  (rows = inputs, K = outputs)
-                d[o_wb + l] = add(L['W%d' % l][:Ly['in_y'], :], gx(Ly['in_y'], Ly['out'], [(6 * _tl(Ly['out']), _ident(Ly['out']))]))
+                d[o_wb + l] = gemm(L['W%d' % l][:Ly['in_y'], :], Ly['in_y'], Ly['out'])
         oh = 16 + 5 * RT_MAX_L
         H = lambda field, k: oh + field * RT_MAX_H + k
-        zrows = 6 * _tl(self.Z)
         for k, net in enumerate(self.heads):
             w0, w1, c = net.widths
             nout = 1 if c == 1 else 3
@@ -179,28 +163,28 @@ class ReflStackEngine:
             if self.zx:
                 # kernel rows [zx (0 .. Z-1) ; z (Z .. 2Z-1)] (ref_nfr's concat order); the GEMM walks K segment X0 = z first, then X1 = zx
                 Z = self.Z
-                d[H(3, k)] = add(W0.T, gx(w0, 2 * Z, [(zrows, _ident(Z, base=Z)), (zrows, _ident(Z))]))
-                d[10 + k] = addf(pad(W2[w1:w1 + Z].T), packing.rowdot_index_x3(nout, zrows, Z))            # offW2zx
+                d[H(3, k)] = gemm(W0.T, w0, 2 * Z, [X3.tile_seg(Z, base=Z), X3.tile_seg(Z)])
+                d[10 + k] = rowdot(pad(W2[w1:w1 + Z].T), nout, Z)                                          # offW2zx
                 W0, W2 = W0[Z:], np.concatenate([W2[:w1], W2[w1 + Z:]], 0)       # from here on: the z part, as without a second input
             else:
-                d[H(3, k)] = add(W0.T, gx(w0, self.Z, [(zrows, _ident(self.Z))]))
-            d[H(4, k)] = add(W1.T, gx(w1, w0, [(6 * _tl(w0), _ident(w0))]))
-            d[H(5, k)] = addf(L['H%d_b0' % k], packing.bias_index_f16s(w0))
-            d[H(6, k)] = addf(L['H%d_b1' % k], packing.bias_index_f16s(w1))
-            d[H(7, k)] = addf(pad(W2[:w1].T), packing.rowdot_index_x3(nout, 6 * _tl(w1), w1))
-            d[H(8, k)] = addf(pad(W2[w1:].T), packing.rowdot_index_x3(nout, zrows, self.Z))
-            d[H(9, k)] = addf(L['H%d_b2' % k], np.where(np.arange(4) < c, np.arange(4), c))
-            d[H(10, k)] = add(W1, gx(w0, w1, [(6 * _tl(w1), _ident(w1))]))
-            d[H(11, k)] = add(W0, gx(self.Z, w0, [(6 * _tl(w0), _ident(w0))]))
-            offs = [addf(W2[:w1, j], packing.bias_index_f16s(w1)) for j in range(c)]
+                d[H(3, k)] = gemm(W0.T, w0, self.Z)
+            d[H(4, k)] = gemm(W1.T, w1, w0)
+            d[H(5, k)] = bias(L['H%d_b0' % k], w0)
+            d[H(6, k)] = bias(L['H%d_b1' % k], w1)
+            d[H(7, k)] = rowdot(pad(W2[:w1].T), nout, w1)
+            d[H(8, k)] = rowdot(pad(W2[w1:].T), nout, self.Z)
+            d[H(9, k)] = thin.add(L['H%d_b2' % k], np.where(np.arange(4) < c, np.arange(4), c))
+            d[H(10, k)] = gemm(W1, w0, w1)
+            d[H(11, k)] = gemm(W0, self.Z, w0)
+            offs = [bias(W2[:w1, j], w1) for j in range(c)]
             d[H(12, k)] = offs[0]
             assert all(o == offs[0] + j * _tl(w1) * 8 for j, o in enumerate(offs))
-            offs = [addf(W2[w1:, j], packing.bias_index_f16s(self.Z)) for j in range(c)]
+            offs = [bias(W2[w1:, j], self.Z) for j in range(c)]
             d[H(13, k)] = offs[0]
-        gidx = np.concatenate(chunks)
+        gidx = mats.index()
         assert gidx.size % 512 == 0 and gidx.max() < 2 ** 31
         dev = self.device
-        self._dev = (L, torch.from_numpy(gidx.astype(np.int32)).to(dev), gidx.size // 512, torch.from_numpy(np.concatenate(fch).astype(np.int32)).to(dev), d)
+        self._dev = (L, torch.from_numpy(gidx.astype(np.int32)).to(dev), gidx.size // 512, torch.from_numpy(thin.index().astype(np.int32)).to(dev), d)
         return self._dev
 
     # ------------------------------------------------------------------ passes

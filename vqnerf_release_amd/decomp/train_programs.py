@@ -9,9 +9,9 @@ in torch before the reverse program (one elementwise op on [N, <=256])."""
 import torch
 
 from vqnerf_release_amd import _C
-from vqnerf_release_amd.geo.train_programs import (Program, _ident, _f2i, DESC_INTS, K_LD_POSENC, K_LD_T, EPI_ACT, EPI_MUL_DACT,
-                                                   ACT_NONE, ACT_RELU, ACT_SIGMOID, FlatLayout, build_static_packs, wgrad_mode,
-                                                   WgradBatch, BATCHED_WGRAD)
+from vqnerf_release_amd.geo.packing import FlatLayout
+from vqnerf_release_amd.geo.train_programs import (Program, _f2i, DESC_INTS, K_LD_POSENC, K_LD_T, EPI_ACT, EPI_MUL_DACT, ACT_NONE, ACT_RELU,
+                                                   ACT_SIGMOID, build_static_packs, wgrad_mode, WgradBatch, BATCHED_WGRAD)
 
 ACTS = {None: ACT_NONE, 'relu': ACT_RELU, 'sigmoid': ACT_SIGMOID}
 
@@ -143,9 +143,9 @@ class EncoderEngine(_Engine):
         prev = rE
         for k, L in enumerate(self.layers):
             if L['skip']:
-                segs, cols, shape = [prev, rE], [_ident(L['in_y']), _ident(self.E, base=L['in_y'])], (L['out'], L['in_y'] + self.E)
+                segs, cols, shape = [prev, rE], [(L['in_y'], 0), (self.E, L['in_y'])], (L['out'], L['in_y'] + self.E)
             else:
-                segs, cols, shape = [prev], [_ident(L['in_y'])], (L['out'], L['in_y'])
+                segs, cols, shape = [prev], [(L['in_y'], 0)], (L['out'], L['in_y'])
             prev = P.gemm(('Wt', k), shape, segs, cols, L['out'], live=[rE], act=L['act'], bias_key=('b', k), store='Y%d' % k)
         return P.finalize()
 
@@ -156,7 +156,7 @@ class EncoderEngine(_Engine):
         P.op(K_LD_T, P.t('GZ'), P.row(r), r.rows)                       # = delta_top (act' of the top layer applied by the caller)
         for k in range(top, 0, -1):                                   # delta_{k-1} = (W_k[y-part] delta_k) * act'_{k-1}(Y_{k-1})
             L, Lp = self.layers[k], self.layers[k - 1]
-            r = P.gemm(('Wy', k), (L['in_y'], L['out']), [r], [_ident(L['out'])], L['in_y'], live=[], epi=EPI_MUL_DACT, act=Lp['act'],
+            r = P.gemm(('Wy', k), (L['in_y'], L['out']), [r], [(L['out'], 0)], L['in_y'], live=[], epi=EPI_MUL_DACT, act=Lp['act'],
                        aux1='Y%d' % (k - 1), store='D%d' % (k - 1))
         return P.finalize()
 
@@ -267,9 +267,9 @@ class HeadsEngine(_Engine):
         P.op(K_LD_T, P.t('Z'), P.row(rZ), rZ.rows)
         for h, net in enumerate(self.nets):
             w0, w1, c = net.widths
-            y0 = P.gemm(('Wt', h, 0), (w0, self.Z), [rZ], [_ident(self.Z)], w0, live=[rZ], act=ACT_RELU, bias_key=('b', h, 0), store='Y%d_0' % h)
-            y1 = P.gemm(('Wt', h, 1), (w1, w0), [y0], [_ident(w0)], w1, live=[rZ], act=ACT_RELU, bias_key=('b', h, 1), store='Y%d_1' % h)
-            P.gemm(('Wt', h, 2), (c, w1 + self.Z), [y1, rZ], [_ident(w1), _ident(self.Z, base=w1)], c, live=[rZ], act=ACT_SIGMOID,
+            y0 = P.gemm(('Wt', h, 0), (w0, self.Z), [rZ], [(self.Z, 0)], w0, live=[rZ], act=ACT_RELU, bias_key=('b', h, 0), store='Y%d_0' % h)
+            y1 = P.gemm(('Wt', h, 1), (w1, w0), [y0], [(w0, 0)], w1, live=[rZ], act=ACT_RELU, bias_key=('b', h, 1), store='Y%d_1' % h)
+            P.gemm(('Wt', h, 2), (c, w1 + self.Z), [y1, rZ], [(w1, 0), (self.Z, w1)], c, live=[rZ], act=ACT_SIGMOID,
                    bias_key=('b', h, 2), store='Y%d_2' % h, want_dst=False)
         return P.finalize()
 
@@ -284,14 +284,14 @@ class HeadsEngine(_Engine):
             keep = [rGZ] if rGZ else []
             # z-part of the last layer's input: GZ (+)= W2[w1:, :] delta_2
             if rGZ is None:
-                rGZ = P.gemm(('W2z', h), (self.Z, c), [r2], [_ident(c)], self.Z, live=[r2])
+                rGZ = P.gemm(('W2z', h), (self.Z, c), [r2], [(c, 0)], self.Z, live=[r2])
             else:
-                P.gemm(('W2z', h), (self.Z, c), [r2], [_ident(c)], self.Z, live=[r2], dst=rGZ, accumulate=True)
-            d1 = P.gemm(('W2y', h), (w1, c), [r2], [_ident(c)], w1, live=[rGZ], epi=EPI_MUL_DACT, act=ACT_RELU, aux1='Y%d_1' % h,
+                P.gemm(('W2z', h), (self.Z, c), [r2], [(c, 0)], self.Z, live=[r2], dst=rGZ, accumulate=True)
+            d1 = P.gemm(('W2y', h), (w1, c), [r2], [(c, 0)], w1, live=[rGZ], epi=EPI_MUL_DACT, act=ACT_RELU, aux1='Y%d_1' % h,
                         store='D%d_1' % h)
-            d0 = P.gemm(('W1', h), (w0, w1), [d1], [_ident(w1)], w0, live=[rGZ], epi=EPI_MUL_DACT, act=ACT_RELU, aux1='Y%d_0' % h,
+            d0 = P.gemm(('W1', h), (w0, w1), [d1], [(w1, 0)], w0, live=[rGZ], epi=EPI_MUL_DACT, act=ACT_RELU, aux1='Y%d_0' % h,
                         store='D%d_0' % h)
-            P.gemm(('W0', h), (self.Z, w0), [d0], [_ident(w0)], self.Z, live=[], dst=rGZ, accumulate=True,
+            P.gemm(('W0', h), (self.Z, w0), [d0], [(w0, 0)], self.Z, live=[], dst=rGZ, accumulate=True,
                    store='GZ' if h == last else None)
         return P.finalize()
 

@@ -39,7 +39,7 @@ def wgrad_mode(new=None):
     return _wgrad_mode[0]
 
 from vqnerf_release_amd.geo import packing
-from vqnerf_release_amd.geo.packing import gemm_index, bias_index, _take
+from vqnerf_release_amd.geo.packing import F32, FlatLayout, GatherPack
 
 # forward of the full-size training engine: 'x3' = the exact-split render kernel (bf16 piece triples, products to 2^-24: f32-level
 # saved tensors, 6.4 ms per 2560-ray step), 'fused' = the f32-input MFMA one (8.1 ms), 'prog' = the interpreted program (9.3 ms);
@@ -182,7 +182,7 @@ class Region:
 
     def __init__(self, feats, alloc_rows):
         self.row0, self.feats, self.alloc_rows = None, feats, alloc_rows
-        self.rows = (feats + 7) // 8
+        self.rows = F32.rows_for(feats)
 
 
 class _Row:          # placeholder inside an op: "row0 of this region", resolved when the program is finalized
@@ -205,18 +205,19 @@ class Program:
         return -1 if name is None else self.tn[name]
 
     def alloc(self, feats, live, tiles=None):
-        rows = 4 * tiles if tiles is not None else (feats + 7) // 8
+        rows = F32.rows_per_tile * tiles if tiles is not None else F32.rows_for(feats)
         r = Region(feats, rows)
         self.requests.append((r, [x for x in live if x is not None]))
         return r
 
-    def gemm(self, key, M_shape, segs, col_fns, out_feats, live, epi=EPI_ACT, act=ACT_NONE, bias_key=None, aux1=None, aux2=None,
+    def gemm(self, key, M_shape, segs, cols, out_feats, live, epi=EPI_ACT, act=ACT_NONE, bias_key=None, aux1=None, aux2=None,
              store=None, store2=None, dst=None, accumulate=False, want_dst=True):
-        """segs: Regions forming K; col_fns[i](f) -> column of M for local feature f of segs[i] (or -1)."""
+        """segs: Regions forming K; cols[i] = (n_valid, base): local feature f < n_valid of segs[i] is column base + f of M, the others
+        are padding (geo/packing.py's K segments) -- or a function f -> column (or -1) where the map is not of that form."""
         tiles = (out_feats + 31) // 32
         if dst is None and want_dst:
             dst = self.alloc(out_feats, list(segs) + list(live), tiles=tiles)
-        seg_desc = [(s.rows, fn) for s, fn in zip(segs, col_fns)]
+        seg_desc = [(s.rows, c) if callable(c) else (s.rows,) + tuple(c) for s, c in zip(segs, cols)]
         self.gathers.append((key, (M_shape[0], M_shape[1], seg_desc), bias_key, out_feats if bias_key else None, len(self.ops)))
         kA, kB = segs[0], (segs[1] if len(segs) > 1 else None)
         self.ops.append([K_GEMM, tiles, _Row(kA), kA.rows, _Row(kB) if kB else 0, kB.rows if kB else 0, -1, -1,
@@ -232,7 +233,7 @@ class Program:
 
     def materialize(self):
         """build the (large) gather index arrays"""
-        self.gathers = [(key, gemm_index(*spec), bkey, None if bo is None else bias_index(bo), oi)
+        self.gathers = [(key, F32.gemm_index(*spec), bkey, None if bo is None else F32.bias_index(bo), oi)
                         for key, spec, bkey, bo, oi in self.gathers]
         return self
 
@@ -321,75 +322,29 @@ class Program:
         return self
 
 
-def _ident(n_valid, base=0):
-    return lambda f: np.where(f < n_valid, f + base, -1)
-
-
 def _shift(lo, hi, base):
-    """local features lo..hi-1 -> columns base.., everything else padding"""
+    """local features lo..hi-1 -> columns base.., everything else padding (the one column map that is no (n_valid, base) segment:
+    OUTF = [sdf ; feat] read without its first row)"""
     return lambda f: np.where((f >= lo) & (f < hi), f - lo + base, -1)
-
-
-class FlatLayout:
-    """Positions of named source tensors inside one flat vector (the last slot is a constant zero): any transpose / slice
-    of a source is then just an integer index array, so a whole weight pack is ONE gather from the flat vector."""
-
-    def __init__(self, shapes):
-        self.names = [n for n, _ in shapes]
-        self.views, off = {}, 0
-        for n, shp in shapes:
-            k = int(np.prod(shp))
-            self.views[n] = np.arange(off, off + k, dtype=np.int64).reshape(shp)
-            off += k
-        self.zero = off
-        self.size = off + 1
-        self._offsets, self._zero = None, {}
-
-    def __getitem__(self, name):
-        return self.views[name]
-
-    def flatten(self, tensors):
-        """tensors: dict name -> tensor (same shapes as declared) -> flat vector on their device.  One launch (torch.cat of many
-        contiguous pieces issues a device-to-device copy per piece on this build: 60 of a captured reflectance step's launches)."""
-        first = tensors[self.names[0]]
-        if not first.is_cuda:
-            return torch.cat([tensors[n].reshape(-1).float() for n in self.names] + [first.new_zeros(1, dtype=torch.float32)])
-        from vqnerf_release_amd import parallel
-        if self._offsets is None:
-            self._offsets = np.cumsum([0] + [int(self.views[n].size) for n in self.names])
-        zero = self._zero.get(str(first.device))
-        if zero is None:
-            zero = self._zero[str(first.device)] = torch.zeros(1, dtype=torch.float32, device=first.device)
-        flat = torch.empty(self.size, dtype=torch.float32, device=first.device)
-        srcs = [tensors[n].reshape(-1).float() for n in self.names] + [zero]
-        o = self._offsets
-        parallel.multi_copy([flat[o[i]:o[i + 1]] for i in range(len(self.names))] + [flat[self.zero:]], srcs)
-        return flat
 
 
 def build_static_packs(programs, layout, mat_index):
     """programs: {name: Program (materialized)}.  mat_index(key) -> int64 array (positions in the flat vector, layout.zero for
     structural zeros) shaped like the matrix / bias the gather key denotes.
     Returns (global gather index [wbuf_len] int64 numpy, {name: desc int32 numpy}) -- both independent of the weight values."""
-    chunks, off, descs = [], 0, {}
+    pack, descs = GatherPack(layout), {}
     for name, prog in programs.items():
         ops = [list(o) for o in prog.ops]
         for key, wi, bkey, bi, oi in prog.gathers:
-            src = np.append(np.ascontiguousarray(mat_index(key)).reshape(-1), layout.zero)
-            c = src[wi.reshape(-1)]
-            ops[oi][6] = off // 4
-            chunks.append(c); off += c.size
+            ops[oi][6] = pack.add(mat_index(key), wi)
             if bkey is not None:
-                srcb = np.append(np.ascontiguousarray(mat_index(bkey)).reshape(-1), layout.zero)
-                cb = srcb[bi.reshape(-1)]
-                ops[oi][7] = off // 4
-                chunks.append(cb); off += cb.size
+                ops[oi][7] = pack.add(mat_index(bkey), bi)
         d = np.zeros(DESC_INTS, np.int32)
         d[0:4] = [len(ops), prog.total_rows, prog.n_waves, len(prog.tn)]
         for i, o in enumerate(ops):
             d[16 + 16 * i: 32 + 16 * i] = o
         descs[name] = d
-    return np.concatenate(chunks), descs
+    return pack.index(), descs
 
 
 class NeusTrainEngine:
@@ -457,10 +412,10 @@ class NeusTrainEngine:
     def _sdf_fwd_cols(self, l, prev, emb):
         """column maps of W_l for K = [prev (, emb at the skip layer)]"""
         if l == 0:
-            return [emb], [_ident(self.E)]
+            return [emb], [(self.E, 0)]
         if l == self.skip:
-            return [prev, emb], [_ident(self.out[l - 1]), _ident(self.E, base=self.out[l - 1])]
-        return [prev], [_ident(self.inn[l])]
+            return [prev, emb], [(self.out[l - 1], 0), (self.E, self.out[l - 1])]
+        return [prev], [(self.inn[l], 0)]
 
     def _build_forward(self):
         P = Program(self._names())
@@ -473,39 +428,39 @@ class NeusTrainEngine:
             prev = P.gemm(('W', l), (self.out[l], self.inn[l]), segs, cols, self.out[l], live=[rE], act=ACT_SOFTPLUS,
                           bias_key=('b', l), store='U%d' % (l + 1))
         rU = prev
-        rOUT = P.gemm(('W', nL), (self.F, self.inn[nL]), [rU], [_ident(self.inn[nL])], self.F, live=[], bias_key=('b', nL), store='OUTF')
+        rOUT = P.gemm(('W', nL), (self.F, self.inn[nL]), [rU], [(self.inn[nL], 0)], self.F, live=[], bias_key=('b', nL), store='OUTF')
         P.op(K_ST_VEC, P.row(rOUT), 0, 1, P.t('SDF'), ACT_NONE, _f2i(1.0 / self.scale))
         # reverse sweep for n = d sdf / dx.  rOUT is NOT kept in LDS meanwhile (it is re-read from OUTF for the colour net):
         # that keeps the program under 80 KB, i.e. two workgroups per CU.
         rONE = P.alloc(1, [])
         P.op(K_LD_VEC, P.t('ONES'), P.row(rONE), 1, _f2i(1.0), -1, 0)
-        g = P.gemm(('WT_sdfrow',), (self.out[nL - 1], 1), [rONE], [_ident(1)], self.out[nL - 1], live=[],
+        g = P.gemm(('WT_sdfrow',), (self.out[nL - 1], 1), [rONE], [(1, 0)], self.out[nL - 1], live=[],
                    epi=EPI_MUL_DACT, act=ACT_SOFTPLUS, aux1='U%d' % nL, store='GH%d' % (nL - 1))
         rEB, have_eb = None, False
         for l in range(nL - 1, 0, -1):
             # adjoint of in_l = W_l^T g^_l ; its u-part times softplus'(a_{l-1}) is g^_{l-1}
             if l == self.skip:
-                rEB = P.gemm(('WT_e', l), (self.E, self.out[l]), [g], [_ident(self.out[l])], self.E, live=[g])
+                rEB = P.gemm(('WT_e', l), (self.E, self.out[l]), [g], [(self.out[l], 0)], self.E, live=[g])
                 have_eb = True
             keep = [g] + ([rEB] if have_eb else [])
-            g = P.gemm(('WT_u', l), (self.out[l - 1], self.out[l]), [g], [_ident(self.out[l])], self.out[l - 1], live=keep,
+            g = P.gemm(('WT_u', l), (self.out[l - 1], self.out[l]), [g], [(self.out[l], 0)], self.out[l - 1], live=keep,
                        epi=EPI_MUL_DACT, act=ACT_SOFTPLUS, aux1='U%d' % l, store='GH%d' % (l - 1))
         if have_eb:
-            P.gemm(('WT_e', 0), (self.E, self.out[0]), [g], [_ident(self.out[0])], self.E, live=[], dst=rEB, accumulate=True)
+            P.gemm(('WT_e', 0), (self.E, self.out[0]), [g], [(self.out[0], 0)], self.E, live=[], dst=rEB, accumulate=True)
         else:
-            rEB = P.gemm(('WT_e', 0), (self.E, self.out[0]), [g], [_ident(self.out[0])], self.E, live=[g])
+            rEB = P.gemm(('WT_e', 0), (self.E, self.out[0]), [g], [(self.out[0], 0)], self.E, live=[g])
         P.op(K_POSENC_VJP, P.row(rEB), P.t('X'), P.t('N'), self.mr, _f2i(self.scale))
         # colour network on [pts, posenc(view), normals, feat]
         rOUT = P.alloc(self.F, [], tiles=self._tiles(self.F))
         P.op(K_LD_T, P.t('OUTF'), P.row(rOUT), rOUT.rows)
         rEX = P.alloc(self.X, [rOUT])
         P.op(K_LD_EXTRAS, P.t('X'), P.t('DIRS'), P.t('N'), P.row(rEX), self.mrv, P.t('EXTR'), self.X)
-        prev = P.gemm(('Wc', 0), (self.cout[0], self.cin[0]), [rOUT, rEX], [_shift(1, self.F, self.X), _ident(self.X)], self.cout[0],
+        prev = P.gemm(('Wc', 0), (self.cout[0], self.cin[0]), [rOUT, rEX], [_shift(1, self.F, self.X), (self.X, 0)], self.cout[0],
                       live=[], act=ACT_RELU, bias_key=('bc', 0), store='C1')
         for l in range(1, nC):
-            prev = P.gemm(('Wc', l), (self.cout[l], self.cin[l]), [prev], [_ident(self.cin[l])], self.cout[l], live=[], act=ACT_RELU,
+            prev = P.gemm(('Wc', l), (self.cout[l], self.cin[l]), [prev], [(self.cin[l], 0)], self.cout[l], live=[], act=ACT_RELU,
                           bias_key=('bc', l), store='C%d' % (l + 1))
-        rRGB = P.gemm(('Wc', nC), (3, self.cin[nC]), [prev], [_ident(self.cin[nC])], 3, live=[],
+        rRGB = P.gemm(('Wc', nC), (3, self.cin[nC]), [prev], [(self.cin[nC], 0)], 3, live=[],
                       act=ACT_SIGMOID if self.squeeze else ACT_NONE, bias_key=('bc', nC))
         P.op(K_ST_VEC, P.row(rRGB), 0, 3, P.t('RGB'), ACT_NONE, _f2i(1.0))
         return P.finalize()
@@ -516,11 +471,11 @@ class NeusTrainEngine:
         rD = P.alloc(3, [], tiles=1)
         P.op(K_LD_VEC, P.t('DOUT'), P.row(rD), 3, _f2i(1.0), P.t('DC%d' % nC), 0)
         for l in range(nC, 0, -1):                            # delta_{l-1} = (Wc_l^T delta_l) * relu'(c_l)
-            rD = P.gemm(('WcT', l), (self.cin[l], self.cout[l]), [rD], [_ident(self.cout[l])], self.cin[l], live=[],
+            rD = P.gemm(('WcT', l), (self.cin[l], self.cout[l]), [rD], [(self.cout[l], 0)], self.cin[l], live=[],
                         epi=EPI_MUL_DACT, act=ACT_RELU, aux1='C%d' % l, store='DC%d' % (l - 1))
         # adjoints of the colour-net inputs: [sdf(=0) ; feat] in OUTF feature order, and the extras (normals at X-3..X-1)
-        P.gemm(('WcT0_feat',), (self.F, self.cout[0]), [rD], [_ident(self.cout[0])], self.F, live=[rD], store='GOUTF', want_dst=False)
-        rGX = P.gemm(('WcT0_extra',), (self.X, self.cout[0]), [rD], [_ident(self.cout[0])], self.X, live=[rD])
+        P.gemm(('WcT0_feat',), (self.F, self.cout[0]), [rD], [(self.cout[0], 0)], self.F, live=[rD], store='GOUTF', want_dst=False)
+        rGX = P.gemm(('WcT0_extra',), (self.X, self.cout[0]), [rD], [(self.cout[0], 0)], self.X, live=[rD])
         P.op(K_ST_VEC, P.row(rGX), self.X - 3, 3, P.t('GNCOL'), ACT_NONE, _f2i(1.0))
         return P.finalize()
 
@@ -539,10 +494,10 @@ class NeusTrainEngine:
         P.op(K_LD_T, P.t('GOUTF'), P.row(rGO), rGO.rows)
         rGS = P.alloc(1, [rGO])
         P.op(K_LD_VEC, P.t('GS'), P.row(rGS), 1, _f2i(1.0 / self.scale), -1, 0)
-        ab = P.gemm(('WT_last',), (self.out[nL - 1], self.F), [rGO, rGS], [_shift(1, self.F, 1), _ident(1)], self.out[nL - 1], live=[],
+        ab = P.gemm(('WT_last',), (self.out[nL - 1], self.F), [rGO, rGS], [_shift(1, self.F, 1), (1, 0)], self.out[nL - 1], live=[],
                     epi=EPI_BWD2, act=ACT_SOFTPLUS, aux1='U%d' % nL, aux2='S%d' % (nL - 1), store='AB%d' % (nL - 1))
         for l in range(nL - 1, 0, -1):
-            ab = P.gemm(('WT_u', l), (self.out[l - 1], self.out[l]), [ab], [_ident(self.out[l])], self.out[l - 1], live=[],
+            ab = P.gemm(('WT_u', l), (self.out[l - 1], self.out[l]), [ab], [(self.out[l], 0)], self.out[l - 1], live=[],
                         epi=EPI_BWD2, act=ACT_SOFTPLUS, aux1='U%d' % l, aux2='S%d' % (l - 1), store='AB%d' % (l - 1))
         return P.finalize()
 
@@ -693,26 +648,19 @@ class NeusTrainEngine:
 
     def _fused_static(self, device):
         """Gather indices of the render kernel's two packs INTO THE FLAT SOURCE VECTOR of pack() (so the forward's packs cost one
-        gather each per step) and their descriptors.  Made by packing index-valued weights: the packs are pure gathers of the
-        effective weights (geo/packing.py), the skip layer's 1/sqrt2 -- already applied in the flat vector -- undone beforehand."""
+        gather each per step) and their descriptors: the plans' own gathers composed with the flat vector's views.  The flat
+        vector already holds the skip layer divided by sqrt2, as SdfPackPlan.pack() gathers it."""
         k = str(device)
         if k not in self._fused_dev:
             L = self._layout()
-            nS, nCc = self.nL + 1, self.nC + 1
-            val = lambda name, mul=1.0: torch.from_numpy((L[name] + 1).astype(np.float64) * mul)
+            views = lambda name, n: [L[name + '%d' % l] for l in range(n)]
             plan = self.sdf_net.plan(max_tiles=self.col_net.max_tiles())
             c = self.col_net
             col_plan = packing.ColPackPlan(c.d_feature, c.mode, c.dims[1], c.num_layers - 2, c.dims[-1], c.multires_view, c.squeeze_out,
                                            plan.tiles[-1])
-            wb_s, d_s = plan.pack([val('W%d' % l, math.sqrt(2.0) if l == self.skip else 1.0) for l in range(nS)],
-                                  [val('b%d' % l) for l in range(nS)])
-            wb_c, d_c = col_plan.pack([val('Wc%d' % l) for l in range(nCc)], [val('bc%d' % l) for l in range(nCc)])
-            out = []
-            for wb in (wb_s, wb_c):
-                gi = torch.round(wb.double()).long()
-                assert float((wb.double() - gi).abs().max()) < 1e-3 and int(gi.min()) >= 0 and int(gi.max()) <= L.zero
-                out.append(torch.where(gi == 0, torch.full_like(gi, L.zero), gi - 1).to(device))
-            self._fused_dev[k] = (out[0], d_s, out[1], d_c)
+            gi_s = plan.gather_index(L, views('W', self.nL + 1), views('b', self.nL + 1))
+            gi_c = col_plan.gather_index(L, views('Wc', self.nC + 1), views('bc', self.nC + 1))
+            self._fused_dev[k] = (torch.from_numpy(gi_s).to(device), plan.desc.copy(), torch.from_numpy(gi_c).to(device), col_plan.desc.copy())
         return self._fused_dev[k]
 
     def run_fused_forward(self, flat, T, P):
@@ -737,75 +685,8 @@ class NeusTrainEngine:
     def fused_backward(self):
         return self.backward_mode() is not None
 
-    def _bwd_static_x3(self, device):
-        """the x3 backward kernel's packs: int32 gather index [steps, 64, 8] of the piece pack (vqn_pack_x3_gather splits what it gathers),
-        int64 gather index of the two thin f32 images, int32 descriptor"""
-        k = str(device)
-        if k in self._bwd_x3_dev:
-            return self._bwd_x3_dev[k]
-        L, nL, nC, M = self._layout(), self.nL, self.nC, self.TB_MAX_L
-        tl = self._tiles
-        emb_rows = packing.emb_rows_for_x3(self.E)
-        chunks, off, fch, foff = [], [0], [], [0]
-
-        def add(view, idx):                                   # idx [T, S, 64, 8] into view.flatten() ++ [zero]; offsets in float4 of the PIECE pack
-            src = np.append(np.ascontiguousarray(view).reshape(-1), L.zero)
-            c = src[idx.reshape(-1)]
-            o4 = off[0]
-            chunks.append(c)
-            off[0] += (c.size // 512) * 192                   # a K step of one tile: 3 pieces x 64 lanes x 16 B = 192 float4
-            return o4
-
-        def addf(view, idx):
-            src = np.append(np.ascontiguousarray(view).reshape(-1), L.zero)
-            c = src[idx.reshape(-1)]
-            assert c.size % 4 == 0
-            o4 = foff[0] // 4
-            fch.append(c)
-            foff[0] += c.size
-            return o4
-
-        gx = packing.gemm_index_x3
-        offT, offB, offCB = [0] * M, [0] * M, [0] * M
-        for l in range(nL):
-            if l == 0:
-                segs = [(emb_rows, _ident(self.E))]
-            elif l == self.skip:
-                segs = [(6 * tl(self.out[l - 1]), _ident(self.out[l - 1])), (emb_rows, _ident(self.E, base=self.out[l - 1]))]
-            else:
-                segs = [(6 * tl(self.inn[l]), _ident(self.inn[l]))]
-            offT[l] = add(L['W%d' % l], gx(self.out[l], self.inn[l], segs))
-        for l in range(1, nL):
-            offB[l] = add(L['W%d' % l][:, :self.out[l - 1]].T, gx(self.out[l - 1], self.out[l], [(6 * tl(self.out[l]), _ident(self.out[l]))]))
-        nf = self.F - 1
-        offBtop = add(L['W%d' % nL][1:].T, gx(self.inn[nL], nf, [(6 * tl(nf), _ident(nf))]))
-        offWrow = addf(L['W%d' % nL][0], packing.bias_index_f16s(self.inn[nL]))
-        for l in range(1, nC + 1):
-            rows = 3 if l == nC else 6 * tl(self.cout[l])
-            offCB[l] = add(L['Wc%d' % l].T, gx(self.cin[l], self.cout[l], [(rows, _ident(self.cout[l]))]))
-        offCBfeat = add(L['Wc0'][:, self.X:].T, gx(nf, self.cout[0], [(6 * tl(self.cout[0]), _ident(self.cout[0]))]))
-        offCBnrm = addf(L['Wc0'][:, self.X - 3:self.X].T, packing.rowdot_index_x3(3, 6 * tl(self.cout[0]), self.cout[0]))
-        mt = max(tl(w) for w in self.out[:nL] + self.cout[:nC] + [nf])
-        desc = np.zeros(16 + 5 * M, np.int32)
-        desc[0:14] = [nL, nC, self.skip, emb_rows, self.E, tl(self.E), mt, tl(nf), tl(self.F), int(self.squeeze), offBtop, offWrow, offCBfeat,
-                      offCBnrm]
-        desc[14] = np.float32(self.scale).view(np.int32)
-        desc[15] = np.float32(1.0 / self.scale).view(np.int32)
-        for l in range(nL):
-            desc[16 + l] = tl(self.out[l])
-        for l in range(nC):
-            desc[16 + M + l] = tl(self.cout[l])
-        desc[16 + 2 * M:16 + 3 * M] = offT
-        desc[16 + 3 * M:16 + 4 * M] = offB
-        desc[16 + 4 * M:16 + 5 * M] = offCB
-        gidx = np.concatenate(chunks)
-        assert gidx.size % 512 == 0 and gidx.max() < 2 ** 31
-        self._bwd_x3_dev[k] = (torch.from_numpy(gidx.astype(np.int32)).to(device), gidx.size // 512,
-                               torch.from_numpy(np.concatenate(fch).astype(np.int32)).to(device), desc)
-        return self._bwd_x3_dev[k]
-
     def run_fused_backward_x3(self, flat, T, P, g_rgb, g_n, g_sdf):
-        gidx, n_steps, fidx, desc = self._bwd_static_x3(flat.device)
+        gidx, n_steps, fidx, desc = self._bwd_static(flat.device, 'x3')
         nL, nC = self.nL, self.nC
         saved = [T['U%d' % (l + 1)] for l in range(nL)] + [T['GH%d' % l] for l in range(nL)] + [T['C%d' % (l + 1)] for l in range(nC)]
         outs = [T['DC%d' % l] for l in range(nC + 1)] + [T['GOUTF'], T['ED']] + [T['UD%d' % (l + 1)] for l in range(nL)] + \
@@ -822,48 +703,49 @@ class NeusTrainEngine:
         mt = max(self._tiles(w) for w in self.out[:self.nL] + self.cout[:self.nC] + [self.F - 1])
         return 5 <= mt <= 8 and self.skip != 0 and self.nL >= 2 and self.nC >= 1 and max(self.nL, self.nC) < self.TB_MAX_L and self.E <= 64 and self.X <= 64
 
-    def _bwd_static(self, device):
-        """Gather index (into the flat source vector of pack()) of the backward kernel's weight pack + its int32 descriptor
-        (csrc/neus_train_bwd.hip: TrainBwdDesc).  Matrices in A-fragment order (geo/packing.py: gemm_index), row-dot images for the
-        two thin ones."""
-        k = str(device)
-        if k in self._bwd_dev:
-            return self._bwd_dev[k]
+    def _bwd_static(self, device, mode='f32'):
+        """The backward kernel's weight packs as gathers from the flat source vector of pack(), and its int32 descriptor (TrainBwdDesc),
+        in the layout of the engine `mode`.  Matrices in A-fragment order, the thin ones as f32 images.
+        'f32' (csrc/neus_train_bwd.hip): ONE buffer -> (int64 gather index, descriptor).
+        'x3' (csrc/neus_train_bwd_x3.hip): the matrices form a piece pack (vqn_pack_x3_gather splits what it gathers), the thin
+        images an f32 buffer of their own -> (int32 index [steps, 64, 8] of the piece pack, its K steps, int32 index of the images,
+        descriptor)."""
+        cache, k = (self._bwd_x3_dev if mode == 'x3' else self._bwd_dev), str(device)
+        if k in cache:
+            return cache[k]
+        lay, x3 = packing.LAYOUTS[mode], mode == 'x3'
         L, nL, nC, M = self._layout(), self.nL, self.nC, self.TB_MAX_L
         tl = self._tiles
-        emb_rows = packing.emb_rows_for(self.E)
-        chunks, off = [], [0]
+        emb_rows = lay.rows_for(self.E)
+        mats = GatherPack(L, pieces=x3)
+        thin = GatherPack(L) if x3 else mats
 
-        def add(view, idx):
-            """view: int64 array of flat positions shaped like the matrix; idx: gather index into view.flatten() ++ [zero]"""
-            src = np.append(np.ascontiguousarray(view).reshape(-1), L.zero)
-            c = src[idx.reshape(-1)]
-            assert c.size % 4 == 0
-            o4 = off[0] // 4
-            chunks.append(c)
-            off[0] += c.size
-            return o4
+        def gemm(view, n_out, n_cols, segs=None):
+            return mats.add(view, lay.gemm_index(n_out, n_cols, segs))
 
         offT, offB, offCB = [0] * M, [0] * M, [0] * M
         for l in range(nL):                                   # W_l over K = [u_{l-1} (, e at the skip layer)] (the 1/sqrt2 is in the flat vector)
             if l == 0:
-                segs = [(emb_rows, _ident(self.E))]
+                segs = [(emb_rows, self.E, 0)]
             elif l == self.skip:
-                segs = [(4 * tl(self.out[l - 1]), _ident(self.out[l - 1])), (emb_rows, _ident(self.E, base=self.out[l - 1]))]
+                prev = self.out[l - 1]
+                segs = [lay.tile_seg(prev), (emb_rows, self.E, prev)]
             else:
-                segs = [(4 * tl(self.inn[l]), _ident(self.inn[l]))]
-            offT[l] = add(L['W%d' % l], gemm_index(self.out[l], self.inn[l], segs))
+                segs = None
+            offT[l] = gemm(L['W%d' % l], self.out[l], self.inn[l], segs)
         for l in range(1, nL):                                # W_l[:, :out_{l-1}]^T
-            view = L['W%d' % l][:, :self.out[l - 1]].T
-            offB[l] = add(view, gemm_index(self.out[l - 1], self.out[l], [(4 * tl(self.out[l]), _ident(self.out[l]))]))
-        nf = self.F - 1
-        offBtop = add(L['W%d' % nL][1:].T, gemm_index(self.inn[nL], nf, [(4 * tl(nf), _ident(nf))]))
-        offWrow = add(L['W%d' % nL][:1], packing.rowdot_index(1, 4 * tl(self.inn[nL]), self.inn[nL]))
-        for l in range(1, nC + 1):                            # Wc_l^T (l = nC: three columns in one K row)
-            rows = 1 if l == nC else 4 * tl(self.cout[l])
-            offCB[l] = add(L['Wc%d' % l].T, gemm_index(self.cin[l], self.cout[l], [(rows, _ident(self.cout[l]))]))
-        offCBfeat = add(L['Wc0'][:, self.X:].T, gemm_index(nf, self.cout[0], [(4 * tl(self.cout[0]), _ident(self.cout[0]))]))
-        offCBnrm = add(L['Wc0'][:, self.X - 3:self.X].T, packing.rowdot_index(3, 4 * tl(self.cout[0]), self.cout[0]))
+            offB[l] = gemm(L['W%d' % l][:, :self.out[l - 1]].T, self.out[l - 1], self.out[l])
+        nf, n_last = self.F - 1, self.inn[nL]
+        offBtop = gemm(L['W%d' % nL][1:].T, n_last, nf)
+        if x3:                                                # the sdf row of W_L: the x3 kernel reads it in accumulator (bias) order,
+            offWrow = thin.add(L['W%d' % nL][0], lay.bias_index(n_last))
+        else:                                                 # the f32 kernel as a row-dot image
+            offWrow = thin.add(L['W%d' % nL][:1], lay.rowdot_index(1, n_last))
+        for l in range(1, nC + 1):                            # Wc_l^T; l = nC: its three columns are ONE K step (1 row for f32, 3 for x3)
+            segs = [(lay.rows_per_step, self.cout[l], 0)] if l == nC else None
+            offCB[l] = gemm(L['Wc%d' % l].T, self.cin[l], self.cout[l], segs)
+        offCBfeat = gemm(L['Wc0'][:, self.X:].T, nf, self.cout[0])
+        offCBnrm = thin.add(L['Wc0'][:, self.X - 3:self.X].T, lay.rowdot_index(3, self.cout[0]))
         mt = max(tl(w) for w in self.out[:nL] + self.cout[:nC] + [nf])
         desc = np.zeros(16 + 5 * M, np.int32)
         desc[0:14] = [nL, nC, self.skip, emb_rows, self.E, tl(self.E), mt, tl(nf), tl(self.F), int(self.squeeze), offBtop, offWrow, offCBfeat,
@@ -877,8 +759,14 @@ class NeusTrainEngine:
         desc[16 + 2 * M:16 + 3 * M] = offT
         desc[16 + 3 * M:16 + 4 * M] = offB
         desc[16 + 4 * M:16 + 5 * M] = offCB
-        self._bwd_dev[k] = (torch.from_numpy(np.concatenate(chunks)).to(device), desc)
-        return self._bwd_dev[k]
+        gidx = mats.index()
+        if x3:
+            assert gidx.size % 512 == 0 and gidx.max() < 2 ** 31
+            cache[k] = (torch.from_numpy(gidx.astype(np.int32)).to(device), gidx.size // 512,
+                        torch.from_numpy(thin.index().astype(np.int32)).to(device), desc)
+        else:
+            cache[k] = (torch.from_numpy(gidx).to(device), desc)
+        return cache[k]
 
     def run_fused_backward(self, flat, T, P, g_rgb, g_n, g_sdf):
         """g_rgb [P,3] (adjoint of the colours AFTER the sigmoid when the colour net has one), g_n [P,3] | None, g_sdf [P] | None."""
