@@ -95,11 +95,13 @@ class WgradBatch:
             return
         for a0 in range(0, a_nt_all, 8):
             an = min(8, a_nt_all - a0)
+            rs_done = False
             for b0 in range(0, b_nt_all, 8):
                 bn = min(8, b_nt_all - b0)
                 if col_first >= min(bn * 32, b_cols - b0 * 32) + b0 * 32:
                     continue
-                want_rs = bias_dst is not None and b0 == 0
+                want_rs = bias_dst is not None and not rs_done      # with the first block that runs (block 0 unless col_first skips it)
+                rs_done = rs_done or want_rs
                 ws, rs = self._partials(A, B, at, a0, an, bt, b0, bn, nt, want_rs)
                 ws2 = None
                 if A2 is not None:
