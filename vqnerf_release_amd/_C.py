@@ -49,12 +49,13 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack and the mesh export, dense and on bricks), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, and the image metrics), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
             'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
             'vqn_mc_brick_points': ('i', 'pppiiiplllpp'), 'vqn_mc_brick_classify': ('i', 'pplpiiifppppp'),
-            'vqn_mc_brick_emit': ('i', 'pplpiiifppllppppp')}
+            'vqn_mc_brick_emit': ('i', 'pplpiiifppllppppp'), 'vqn_image_metrics_scratch_bytes': ('l', 'lii'),
+            'vqn_image_metrics_u8': ('i', 'ppplfliiipplpp'), 'vqn_image_metrics_f32': ('i', 'ppplfliiipplpp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -772,6 +773,33 @@ def mc_brick_emit(ub, brick_ijk, slot, dims, threshold, vert_offset, tri_offset,
           None if origin is None else _host(origin, np.float32), None if step is None else _host(step, np.float32),
           _ptr(verts) if n_verts else None, _ptr(tris) if n_tris else None)
     return verts, tris
+
+
+# --------------------------------------------------------------------------------------
+# image metrics (csrc/image_metrics.hip; decomp/nerfactor/util/metric.py)
+def image_metrics(a, b, window, alpha=None, alpha_thres=0.0):
+    """a, b [B,H,W,C] contiguous device tensors, both uint8 or both float32 (rows in [0, 1], quantised by the kernel), C in {1, 3};
+    window: the 11 normalised weights (host doubles); alpha: float32 [H,W] (one plane for all pairs) or [B,H,W], pixels that are
+    not alpha > alpha_thres turn white -> int64 [B, 16], the words of vqn_image_metrics_u8's `out` (view the first ten as float64).
+    Two launches, no host read."""
+    if a.dtype != b.dtype or a.dtype not in (torch.uint8, torch.float32) or a.shape != b.shape or a.dim() != 4 or a.device != b.device \
+            or not (a.is_cuda and a.is_contiguous() and b.is_contiguous()):
+        raise VqnError(f'image_metrics: expected two contiguous device tensors [B, H, W, C] of one shape, uint8 or float32, got '
+                       f'{a.dtype} {tuple(a.shape)} on {a.device} and {b.dtype} {tuple(b.shape)} on {b.device}')
+    B, H, W, C = (int(s) for s in a.shape)
+    stride = 0
+    if alpha is not None:
+        _f32c(alpha, 'alpha')
+        if alpha.device != a.device or tuple(alpha.shape) not in ((H, W), (B, H, W)):
+            raise VqnError(f'image_metrics: alpha must be [H, W] or [B, H, W] on the device of the images, got {tuple(alpha.shape)}')
+        stride = H * W if alpha.dim() == 3 else 0
+    out = torch.empty((B, 16), dtype=torch.int64, device=a.device)
+    entry = 'vqn_image_metrics_u8' if a.dtype == torch.uint8 else 'vqn_image_metrics_f32'
+    need = lib().vqn_image_metrics_scratch_bytes(B, H, W)
+    buf = _scratch('image_metrics', max(need, 64), a.device)           # (need = 0: a shape the call itself refuses, with the reason)
+    _call(entry, _ptr(a), _ptr(b), _ptr(alpha), stride, float(alpha_thres), B, H, W, C, _host(window, np.float64), _ptr(buf), buf.numel(),
+          _ptr(out))
+    return out
 
 
 # --------------------------------------------------------------------------------------

@@ -140,7 +140,7 @@ def _shape_views(host, hw):
 
 
 def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_names, olat_first_n, alpha_thres, simp, full_vis_path,
-                pool_submit):
+                pool_submit, scores=None):
     if event is not None:
         event.synchronize()
     d = _shape_views(host, hw)
@@ -188,6 +188,9 @@ def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_
     if not simp:
         if mode not in ('test', 'render') and 'gt_rgb' in written and 'pred_rgb' in written:
             meta['psnr'] = psnr_uint8(written['gt_rgb'], written['pred_rgb'])
+            if scores is not None:                               # the device's scores of the same two images (util/metric.py)
+                from vqnerf_release_amd.decomp.nerfactor.util.metric import KEYS
+                meta.update(zip(KEYS, scores.tolist()))
         with open(os.path.join(outdir, 'metadata.json'), 'w') as f:
             json.dump(meta, f)
     for j in jobs:
@@ -204,10 +207,27 @@ def vis_light_uint8(light, h=None):
     return to_uint8(t.numpy())
 
 
+def _device_scores(data_dict, hw, white_bg, alpha_thres):
+    """psnr, mse, psnr_luma, ssim, ssim_luma (float64 [5], on the device) of gt_rgb against pred_rgb, both composited as
+    `_write_view` composites the PNGs it writes (the same f32 operations in the same order; the kernel quantises as to_uint8)"""
+    from vqnerf_release_amd.decomp.nerfactor.util import metric
+    alpha = data_dict['gt_alpha'].detach().to(torch.float32).reshape(-1, 1)
+    alpha = torch.where(alpha < alpha_thres, torch.zeros_like(alpha), alpha)
+    pair = []
+    for k in ('gt_rgb', 'pred_rgb'):
+        v = data_dict[k].detach().to(torch.float32).reshape(-1, 3)
+        bg = torch.ones_like(v) if white_bg else torch.zeros_like(v)
+        pair.append((v * alpha + bg * (1.0 - alpha)).reshape(1, hw[0], hw[1], 3))
+    return metric.image_metrics_raw(pair[0], pair[1]).view(torch.float64)[0, :len(metric.KEYS)]
+
+
 def vis_batch(model, data_dict, outdir, mode='train', light_vis_h=256, alpha_thres=0.8, simp=False, full_vis_path=None,
-              writer=None):
+              writer=None, metrics=False):
     """Model.vis_batch (vq_nfr.py:988-1134).  data_dict: the `to_vis` dict of `call` / `fast_render` / `vis_mat` (device
-    tensors with N = H*W rows, plus 'hw' [N,2] and 'id').  Returns the AsyncWriter the files were queued on."""
+    tensors with N = H*W rows, plus 'hw' [N,2] and 'id').  Returns the AsyncWriter the files were queued on.
+    metrics: where `metadata.json` gets its `psnr` (ground truth exists, not `simp`, not a test / render pass), also score the
+    two images on the device before they are fetched (util/metric.py) and write `psnr`, `mse`, `psnr_luma`, `ssim`, `ssim_luma`
+    there; `psnr` is then the device's value.  Off (the default): every file is what it was."""
     model._validate_mode(mode)
     writer = writer or default_writer()
     if mode == 'vali':
@@ -231,12 +251,16 @@ def vis_batch(model, data_dict, outdir, mode='train', light_vis_h=256, alpha_thr
         id_ = id_[0]
     if isinstance(id_, bytes):
         id_ = id_.decode()
-    host, ev = writer.fetch({k: v for k, v in data_dict.items() if v is not None})
+    scores = None
+    if metrics and not simp and mode not in ('test', 'render') and all(data_dict.get(k) is not None for k in ('gt_rgb', 'pred_rgb', 'gt_alpha')):
+        scores = _device_scores(data_dict, hw, bool(model.white_bg), alpha_thres)
+    host, ev = writer.fetch({k: v for k, v in dict(data_dict, **({} if scores is None else {'_scores': scores})).items() if v is not None})
+    scores = host.pop('_scores', None)
     probe_names = list(getattr(model, 'novel_probes', {}) or {})
     olat_names = list(getattr(model, 'novel_olat', {}) or {})
     light_res = getattr(model, 'light_res', (16, 32))
     if full_vis_path is not None:
         os.makedirs(full_vis_path, exist_ok=True)
     writer.submit(_write_view, host, ev, hw, str(id_), outdir, mode, bool(model.white_bg), probe_names, olat_names,
-                  int(np.prod(light_res)) // 2, alpha_thres, simp, full_vis_path, writer.pool.submit)
+                  int(np.prod(light_res)) // 2, alpha_thres, simp, full_vis_path, writer.pool.submit, scores)
     return writer
