@@ -49,13 +49,15 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, and the image metrics), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
             'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
             'vqn_mc_brick_points': ('i', 'pppiiiplllpp'), 'vqn_mc_brick_classify': ('i', 'pplpiiifppppp'),
             'vqn_mc_brick_emit': ('i', 'pplpiiifppllppppp'), 'vqn_image_metrics_scratch_bytes': ('l', 'lii'),
-            'vqn_image_metrics_u8': ('i', 'ppplfliiipplpp'), 'vqn_image_metrics_f32': ('i', 'ppplfliiipplpp')}
+            'vqn_image_metrics_u8': ('i', 'ppplfliiipplpp'), 'vqn_image_metrics_f32': ('i', 'ppplfliiipplpp'),
+            'vqn_seg_scratch_bytes': ('l', 'lii'), 'vqn_seg_contingency_rgb': ('i', 'pppflpipiplpp'),
+            'vqn_seg_contingency_labels': ('i', 'pppliiplpp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -799,6 +801,53 @@ def image_metrics(a, b, window, alpha=None, alpha_thres=0.0):
     buf = _scratch('image_metrics', max(need, 64), a.device)           # (need = 0: a shape the call itself refuses, with the reason)
     _call(entry, _ptr(a), _ptr(b), _ptr(alpha), stride, float(alpha_thres), B, H, W, C, _host(window, np.float64), _ptr(buf), buf.numel(),
           _ptr(out))
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# segmentation scores (csrc/segmentation_metrics.hip; decomp/nerfactor/util/segmentation.py)
+SEG_PIXELS_PER_PASS = 4096     # pixels a workgroup takes per pass (kPass of the kernel)
+SEG_GRID_CAP = 512             # workgroups at most (kGridCap)
+SEG_MAX_SIDE = 65              # table sides R = n_gt + 1, C = n_pd + 1 at most
+SEG_HEAD_WORDS = 42            # 8-byte words of the output row ahead of the table
+
+
+def segmentation_counts(gt, pd, sel=None, alpha_thres=0.0, gt_palette=None, pd_palette=None, n_gt=None, n_pd=None):
+    """Contingency table and clustering scores of n pixels, two launches, no host read.
+    Colour form: gt, pd uint8 [n, 3] contiguous device tensors, gt_palette [n_gt, 3] and pd_palette [n_pd, 3] host uint8 arrays,
+    sel = alpha float32 [n] or None (counted: alpha > alpha_thres, strict).  Label form: gt, pd int32 [n], n_gt and n_pd the largest
+    labels, sel = mask uint8 [n] or None (counted: mask != 0).
+    -> int64 [42 + R * C], the words of vqn_seg_contingency_rgb's `out` (include/vqn_neus_fold.h)."""
+    colour = gt.dtype == torch.uint8
+    want = 2 if colour else 1
+    if gt.dtype != pd.dtype or gt.dtype not in (torch.uint8, torch.int32) or gt.shape != pd.shape or gt.dim() != want \
+            or (colour and gt.shape[-1] != 3) or gt.device != pd.device or not (gt.is_cuda and gt.is_contiguous() and pd.is_contiguous()):
+        raise VqnError(f'segmentation_counts: expected two contiguous device tensors of one shape, uint8 [n, 3] or int32 [n], got '
+                       f'{gt.dtype} {tuple(gt.shape)} on {gt.device} and {pd.dtype} {tuple(pd.shape)} on {pd.device}')
+    n = int(gt.shape[0])
+    if sel is not None:
+        sel_dtype = torch.float32 if colour else torch.uint8
+        if sel.dtype != sel_dtype or tuple(sel.shape) != (n,) or sel.device != gt.device or not sel.is_contiguous():
+            raise VqnError(f'segmentation_counts: expected {"alpha float32" if colour else "mask uint8"} [{n}] contiguous on the device of '
+                           f'the labels, got {sel.dtype} {tuple(sel.shape)} on {sel.device}')
+    if colour:
+        pals = [np.ascontiguousarray(p, dtype=np.uint8) for p in (gt_palette, pd_palette)]
+        if any(p.ndim != 2 or p.shape[1] != 3 for p in pals):
+            raise VqnError(f'segmentation_counts: palettes must be uint8 [rows, 3], got {pals[0].shape} and {pals[1].shape}')
+        n_gt, n_pd = int(pals[0].shape[0]), int(pals[1].shape[0])
+    elif n_gt is None or n_pd is None:
+        raise VqnError('segmentation_counts: the label form needs n_gt and n_pd, the largest labels')
+    n_gt, n_pd = int(n_gt), int(n_pd)
+    R, C = n_gt + 1, n_pd + 1
+    cells = R * C if 1 <= R <= SEG_MAX_SIDE and 1 <= C <= SEG_MAX_SIDE else 0
+    out = torch.empty((SEG_HEAD_WORDS + cells,), dtype=torch.int64, device=gt.device)
+    need = lib().vqn_seg_scratch_bytes(n, R, C)
+    buf = _scratch('segmentation_metrics', max(need, 64), gt.device)    # (need = 0: a shape the call itself refuses, with the reason)
+    if colour:
+        _call('vqn_seg_contingency_rgb', _ptr(gt), _ptr(pd), _ptr(sel), float(alpha_thres), n, pals[0].ctypes.data, n_gt, pals[1].ctypes.data,
+              n_pd, _ptr(buf), buf.numel(), _ptr(out))
+    else:
+        _call('vqn_seg_contingency_labels', _ptr(gt), _ptr(pd), _ptr(sel), n, n_gt, n_pd, _ptr(buf), buf.numel(), _ptr(out))
     return out
 
 
