@@ -12,31 +12,35 @@
 
 void vqn_set_error(const char* fmt, ...);
 
-#define VQN_CHECK_ARG(cond, msg)                         \
+// the _IN forms report under the name `fn` (helpers shared by several entry points pass their caller's __func__ on)
+#define VQN_CHECK_ARG_IN(fn, cond, msg)                  \
   do {                                                   \
     if (!(cond)) {                                       \
-      vqn_set_error("%s: bad argument: %s", __func__, msg); \
+      vqn_set_error("%s: bad argument: %s", fn, msg);    \
       return VQN_EARG;                                   \
     }                                                    \
   } while (0)
+#define VQN_CHECK_ARG(cond, msg) VQN_CHECK_ARG_IN(__func__, cond, msg)
 
-#define VQN_CHECK_SHAPE(cond, msg)                       \
+#define VQN_CHECK_SHAPE_IN(fn, cond, msg)                \
   do {                                                   \
     if (!(cond)) {                                       \
-      vqn_set_error("%s: unsupported shape: %s", __func__, msg); \
+      vqn_set_error("%s: unsupported shape: %s", fn, msg); \
       return VQN_ESHAPE;                                 \
     }                                                    \
   } while (0)
+#define VQN_CHECK_SHAPE(cond, msg) VQN_CHECK_SHAPE_IN(__func__, cond, msg)
 
-#define VQN_HIP(call)                                                        \
+#define VQN_HIP_IN(fn, call)                                                 \
   do {                                                                       \
     hipError_t e_ = (call);                                                  \
     if (e_ != hipSuccess) {                                                  \
-      vqn_set_error("%s: HIP error %d (%s) at %s:%d", __func__, (int)e_,     \
+      vqn_set_error("%s: HIP error %d (%s) at %s:%d", fn, (int)e_,           \
                     hipGetErrorString(e_), __FILE__, __LINE__);              \
       return VQN_EHIP;                                                       \
     }                                                                        \
   } while (0)
+#define VQN_HIP(call) VQN_HIP_IN(__func__, call)
 
 #define VQN_LAUNCH_CHECK() VQN_HIP(hipGetLastError())
 

@@ -399,6 +399,11 @@ __device__ __forceinline__ float posenc_jac(int f, float x0, float x1, float x2,
 
 // feature index held by (row r of a segment, lane half h, component j)
 __device__ __forceinline__ int row_feat(int r, int h, int j) { return 32 * (r >> 2) + 2 * (4 * (r & 3) + j) + h; }
+// value of feature f (region starting at row0) of point pp: the inverse of row_feat
+__device__ __forceinline__ float lds_feat(const f32x4* __restrict__ lds, const int row0, const int f, const int pp) {
+  const int t = f >> 5, fi = f & 31, hh = fi & 1, rr = fi >> 1;
+  return reinterpret_cast<const float*>(lds)[(((row0 + t * 4 + (rr >> 2)) * 64) + pp + 32 * hh) * 4 + (rr & 3)];
+}
 
 // part[(wave*32 + p)*NOUT + o] = this wave's share of sum_f wimg[o][f] * act[f][p] over rows
 // [row0, row0+n_rows); the caller adds the four partials in a fixed order (deterministic).

@@ -10,8 +10,7 @@
 //
 // Execution model: 256-thread workgroups (4 waves), persistent over tiles of 32 points, 2 workgroups
 // per CU.  See mlp_prims.h for the LDS "activation image" and the weight-pack layout.
-#include "mlp_prims.h"
-#include "vqn_neus_desc.h"
+#include "neus_launch.h"
 #include <stdlib.h>
 
 using namespace eng;
@@ -60,10 +59,6 @@ namespace {
 constexpr int E0 = 0;        // LDS rows [0,8): embedding / colour-net extras / d sdf / d embedding
 constexpr int E_ROWS = 8;
 
-struct Smalls {              // per-tile scalars, after the activation rows
-  float pts[96], dirs[96], part[512], grad[96];
-};
-
 template <bool FINE>
 __global__ __launch_bounds__(256, 2) void neus_points_kernel(
     const SdfDesc sd, const ColDesc cd, const f32x4* __restrict__ wsdf, const f32x4* __restrict__ wcol,
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
   extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
   const int MT = sd.max_tiles;
   const int X0 = E_ROWS, Y0 = E_ROWS + 4 * MT;
-  Smalls* sm = reinterpret_cast<Smalls*>(lds + (size_t)(E_ROWS + 8 * MT) * 64);
+  Smalls<1>* sm = reinterpret_cast<Smalls<1>*>(lds + (size_t)(E_ROWS + 8 * MT) * 64);
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform by construction: let the compiler know
   const int n_lin = sd.n_lin;
@@ -88,35 +83,15 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
     const long p0 = tile << 5;
     VQN_STAMP(4)
     // ---------------- points of this tile ----------------
-    if (tid < 32) {
-      long pt = p0 + tid;
-      if (pt >= P) pt = P - 1;
-      float x, y, z, dx = 0.f, dy = 0.f, dz = 0.f;
-      if (pts_direct != nullptr) {
-        x = pts_direct[pt * 3 + 0]; y = pts_direct[pt * 3 + 1]; z = pts_direct[pt * 3 + 2];
-        if (FINE) { dx = dirs_direct[pt * 3 + 0]; dy = dirs_direct[pt * 3 + 1]; dz = dirs_direct[pt * 3 + 2]; }
-      } else {
-        const long ray = pt / S;
-        const float t = zv[pt];
-        dx = rays_d[ray * 3 + 0]; dy = rays_d[ray * 3 + 1]; dz = rays_d[ray * 3 + 2];
-        // o + d * z with separate mul/add roundings, as the reference's broadcasted expression
-        x = rays_o[ray * 3 + 0] + __fmul_rn(dx, t);
-        y = rays_o[ray * 3 + 1] + __fmul_rn(dy, t);
-        z = rays_o[ray * 3 + 2] + __fmul_rn(dz, t);
-      }
-      sm->pts[tid * 3 + 0] = x; sm->pts[tid * 3 + 1] = y; sm->pts[tid * 3 + 2] = z;
-      sm->dirs[tid * 3 + 0] = dx; sm->dirs[tid * 3 + 1] = dy; sm->dirs[tid * 3 + 2] = dz;
-    }
+    if (tid < 32)
+      load_point<FINE>(p0 + tid, P, S, rays_o, rays_d, zv, pts_direct, dirs_direct, sm->pts[0] + tid * 3, sm->dirs[0] + tid * 3);
     __syncthreads();
-    const float xs = sm->pts[p * 3 + 0] * sd.scale, ys = sm->pts[p * 3 + 1] * sd.scale, zs = sm->pts[p * 3 + 2] * sd.scale;
+    const float xs = sm->pts[0][p * 3 + 0] * sd.scale, ys = sm->pts[0][p * 3 + 1] * sd.scale, zs = sm->pts[0][p * 3 + 2] * sd.scale;
     // ---------------- positional encoding -> E rows ----------------
     for (int r = wave; r < sd.emb_rows; r += 4) {
       f32x4 v;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int f = row_feat(r, h, j);
-        v[j] = f < sd.emb_feats ? posenc_feat(f, xs, ys, zs) : 0.f;
-      }
+      for (int j = 0; j < 4; ++j) v[j] = emb_feat(row_feat(r, h, j), sd.emb_feats, xs, ys, zs);
       lds[(E0 + r) * 64 + lane] = v;
     }
     __syncthreads();
@@ -162,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
     const int hid_rows = 4 * sd.layers[n_lin - 2].n_out_tiles;
 
     // ---------------- last layer: sdf row (VALU dot) [+ feature rows -> stash] ----------------
-    rowdot<1>(lds, cur, hid_rows, wsdf + sd.last_w_off, sm->part, wave, lane);
+    rowdot<1>(lds, cur, hid_rows, wsdf + sd.last_w_off, sm->part[0], wave, lane);
     if (FINE && sd.layers[n_lin - 1].n_out_tiles > 0) {
       const LayerDesc L = sd.layers[n_lin - 1];
       const f32x4* bp = wsdf + L.b_off;
@@ -175,11 +150,7 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
                  });
     }
     __syncthreads();
-    if (tid < 32 && p0 + tid < P) {
-      const float s = ((sm->part[tid] + sm->part[32 + tid]) + (sm->part[64 + tid] + sm->part[96 + tid])) +
-                      (sd.last_b_off > 0 ? wsdf[sd.last_b_off][0] : sd.last_bias);
-      out_sdf[p0 + tid] = s / sd.scale;
-    }
+    if (tid < 32 && p0 + tid < P) out_sdf[p0 + tid] = sdf_raw(sm->part[0], tid, sd.last_b_off, sd.last_bias, wsdf) / sd.scale;
     if (!FINE) { __syncthreads(); continue; }
 
     // ---------------- reverse sweep: d sdf / d x ----------------
@@ -249,20 +220,8 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
     // chain through the embedding: thread (point pp, component c) sums its features in a fixed order
     if (tid < 96) {
       const int pp = tid & 31, c = tid >> 5;
-      const float x0 = sm->pts[pp * 3 + 0] * sd.scale, x1 = sm->pts[pp * 3 + 1] * sd.scale, x2 = sm->pts[pp * 3 + 2] * sd.scale;
-      const float* ldsf = reinterpret_cast<const float*>(lds);
-      auto G = [&](int f) {
-        const int t = f >> 5, fi = f & 31, hh = fi & 1, rr = fi >> 1;
-        return ldsf[(((E0 + t * 4 + (rr >> 2)) * 64) + pp + 32 * hh) * 4 + (rr & 3)];
-      };
-      float g = G(c);
-      int cc;
-      for (int k = 0; k < sd.multires; ++k) {
-        const int fs = 3 + 6 * k + c, fc = fs + 3;
-        g = fmaf(G(fs), posenc_jac(fs, x0, x1, x2, &cc), g);
-        g = fmaf(G(fc), posenc_jac(fc, x0, x1, x2, &cc), g);
-      }
-      sm->grad[pp * 3 + c] = g;
+      const float g = embed_chain([&](int f) { return lds_feat(lds, E0, f, pp); }, c, sd.multires, sm->pts[0] + pp * 3, sd.scale);
+      sm->grad[0][pp * 3 + c] = g;
       if (p0 + pp < P) out_grad[(p0 + pp) * 3 + c] = g;
     }
     __syncthreads();
@@ -270,19 +229,12 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
 
     // ---------------- colour network ----------------
     {
-      const float px = sm->pts[p * 3 + 0], py = sm->pts[p * 3 + 1], pz = sm->pts[p * 3 + 2];
-      const float dx = sm->dirs[p * 3 + 0], dy = sm->dirs[p * 3 + 1], dz = sm->dirs[p * 3 + 2];
+      const float px = sm->pts[0][p * 3 + 0], py = sm->pts[0][p * 3 + 1], pz = sm->pts[0][p * 3 + 2];
+      const float dx = sm->dirs[0][p * 3 + 0], dy = sm->dirs[0][p * 3 + 1], dz = sm->dirs[0][p * 3 + 2];
       for (int r = wave; r < cd.extra_rows; r += 4) {
         f32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int f = row_feat(r, h, j);
-          float val = 0.f;
-          if (f < 3) val = f == 0 ? px : (f == 1 ? py : pz);
-          else if (f < 3 + cd.n_view_feats) val = posenc_feat(f - 3, dx, dy, dz);
-          else if (f < cd.extra_feats) val = sm->grad[p * 3 + (f - 3 - cd.n_view_feats)];
-          v[j] = val;
-        }
+        for (int j = 0; j < 4; ++j) v[j] = col_extra_feat(row_feat(r, h, j), px, py, pz, dx, dy, dz, sm->grad[0] + p * 3, cd.n_view_feats, cd.extra_feats);
         lds[(E0 + r) * 64 + lane] = v;
       }
       const f32x4* sv = save + (size_t)feat_slot * 64;
@@ -318,14 +270,11 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
         const int t = cur; cur = oth; oth = t;
         in_rows = 4 * L.n_out_tiles;
       }
-      rowdot<3>(lds, cur, in_rows, wcol + cd.last_w_off, sm->part, wave, lane);
+      rowdot<3>(lds, cur, in_rows, wcol + cd.last_w_off, sm->part[0], wave, lane);
       __syncthreads();
       if (tid < 96) {
         const int pp = tid & 31, o = tid >> 5;
-        float v = ((sm->part[(0 * 32 + pp) * 3 + o] + sm->part[(1 * 32 + pp) * 3 + o]) +
-                   (sm->part[(2 * 32 + pp) * 3 + o] + sm->part[(3 * 32 + pp) * 3 + o])) +
-                  (cd.last_b_off > 0 ? wcol[cd.last_b_off][o] : cd.last_bias[o]);
-        if (cd.squeeze_out) v = 1.f / (1.f + expf(-v));
+        const float v = rgb_out(sm->part[0], pp, o, cd.last_b_off, cd.last_bias[o], cd.squeeze_out, wcol);
         if (p0 + pp < P) out_rgb[(p0 + pp) * 3 + o] = v;
       }
     }
@@ -343,10 +292,6 @@ __global__ __launch_bounds__(256, 2) void neus_points_kernel(
 // barriers and the L2 weight stream per point halve.  The VALU phases split by image: waves 0-3 image 0, waves 4-7 image 1.
 // Same per-point arithmetic as the one-image kernel except the two embedding-gradient GEMMs of the reverse sweep, which are
 // split over K (wte_split_k: a different, still fixed, summation order for d sdf / d x).
-struct Smalls2 {
-  float pts[2][96], dirs[2][96], part[2][512], grad[2][96];
-};
-
 // d sdf / d embedding of one layer for both images: E rows (+)= W_E^T . G over the K rows [k_row0, k_row0 + ng).  The result
 // has only emb_tiles (<= 2) output tiles, so as a plain gemm_tiles2 call it keeps 2 of the 8 waves busy for a whole K = 256 pass;
 // here the waves split it as (tile, K slice) units, park their partial tiles in the free activation buffer `tmp_row0`
@@ -396,24 +341,6 @@ __device__ __forceinline__ void wte_split_k(f32x4* __restrict__ lds, const int I
   __syncthreads();
 }
 
-// ---- training forward (TRAIN): the two-image fine kernel also leaves what the backward tile programs and the weight-gradient
-// contraction read (geo/train_programs.py, prog_fwd's stores) in the tile format of csrc/tile_vm.hip, [point tile][feature tile][32
-// features][32 points] f32: E (embedding), U_1..U_nL (hidden activations), OUTF ([sdf ; features], 257 rows), GH_0..GH_{nL-1} (adjoints of
-// the reverse sweep), EXTR (colour-net extras), C_1..C_nC (colour activations).  A row quad of the activation image -- lane (p, h), component
-// j = feature 2 (4 rq + j) + h of the tile -- goes out as four 256-byte stores (feature rows 8 rq + 2 j and 8 rq + 2 j + 1 are adjacent).
-struct TrainOut {
-  float* E; float* OUTF; float* EXTR;
-  float* U[VQN_MAX_SDF_LAYERS]; float* GH[VQN_MAX_SDF_LAYERS]; float* C[VQN_MAX_COL_LAYERS];
-  int e_tiles, outf_tiles, extr_tiles;
-};
-
-__device__ __forceinline__ void tfmt_store_quad(float* __restrict__ T, const long ptile, const int n_ft, const int ft, const int rq,
-                                                const int lane, const f32x4 v) {
-  float* base = T + ((ptile * n_ft + ft) * 32 + 8 * rq) * 32 + lane;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v[j], base + 64 * j);     // written once, read by later launches: past the L2-resident packs
-}
-
 template <bool FINE, bool TRAIN = false, bool FOLD = false>
 __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     const SdfDesc sd, const ColDesc cd, const f32x4* __restrict__ wsdf, const f32x4* __restrict__ wcol,
@@ -425,7 +352,7 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
   const int MT = sd.max_tiles;
   const int IMG = E_ROWS + 8 * MT, IS = IMG * 64;
   const int X0 = E_ROWS, Y0 = E_ROWS + 4 * MT;
-  Smalls2* sm = reinterpret_cast<Smalls2*>(lds + (size_t)2 * IS);
+  Smalls<2>* sm = reinterpret_cast<Smalls<2>*>(lds + (size_t)2 * IS);
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int img = wave >> 2, w4 = wave & 3;
@@ -458,22 +385,7 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     // ---------------- points of both tiles ----------------
     if (tid < 64) {
       const int im = tid >> 5, t = tid & 31;
-      long pt = ((2 * pair + im) << 5) + t;
-      if (pt >= P) pt = P - 1;
-      float x, y, z, dx = 0.f, dy = 0.f, dz = 0.f;
-      if (pts_direct != nullptr) {
-        x = pts_direct[pt * 3 + 0]; y = pts_direct[pt * 3 + 1]; z = pts_direct[pt * 3 + 2];
-        if (FINE) { dx = dirs_direct[pt * 3 + 0]; dy = dirs_direct[pt * 3 + 1]; dz = dirs_direct[pt * 3 + 2]; }
-      } else {
-        const long ray = pt / S;
-        const float tt = zv[pt];
-        dx = rays_d[ray * 3 + 0]; dy = rays_d[ray * 3 + 1]; dz = rays_d[ray * 3 + 2];
-        x = rays_o[ray * 3 + 0] + __fmul_rn(dx, tt);
-        y = rays_o[ray * 3 + 1] + __fmul_rn(dy, tt);
-        z = rays_o[ray * 3 + 2] + __fmul_rn(dz, tt);
-      }
-      sm->pts[im][t * 3 + 0] = x; sm->pts[im][t * 3 + 1] = y; sm->pts[im][t * 3 + 2] = z;
-      sm->dirs[im][t * 3 + 0] = dx; sm->dirs[im][t * 3 + 1] = dy; sm->dirs[im][t * 3 + 2] = dz;
+      load_point<FINE>(((2 * pair + im) << 5) + t, P, S, rays_o, rays_d, zv, pts_direct, dirs_direct, sm->pts[im] + t * 3, sm->dirs[im] + t * 3);
     }
     __syncthreads();
     const float xs = sm->pts[img][p * 3 + 0] * sd.scale, ys = sm->pts[img][p * 3 + 1] * sd.scale, zs = sm->pts[img][p * 3 + 2] * sd.scale;
@@ -481,10 +393,7 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     for (int r = w4; r < (TRAIN ? 4 * to.e_tiles : sd.emb_rows); r += 4) {
       f32x4 v;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int f = row_feat(r, h, j);
-        v[j] = (r < sd.emb_rows && f < sd.emb_feats) ? posenc_feat(f, xs, ys, zs) : 0.f;
-      }
+      for (int j = 0; j < 4; ++j) v[j] = r < sd.emb_rows ? emb_feat(row_feat(r, h, j), sd.emb_feats, xs, ys, zs) : 0.f;
       if (r < sd.emb_rows) ldsi[(E0 + r) * 64 + lane] = v;
       if (TRAIN && ptile_w < n_tiles) tfmt_store_quad(to.E, ptile_w, to.e_tiles, r >> 2, r & 3, lane, v);
     }
@@ -555,15 +464,10 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     if (tid < 64) {
       const int im = tid >> 5, t = tid & 31;
       const long pt = ((2 * pair + im) << 5) + t;
-      if (pt < P) {
-        const float* pr = sm->part[im];
-        const float s = ((pr[t] + pr[32 + t]) + (pr[64 + t] + pr[96 + t])) + (sd.last_b_off > 0 ? wsdf[sd.last_b_off][0] : sd.last_bias);
-        out_sdf[pt] = s / sd.scale;
-      }
+      if (pt < P) out_sdf[pt] = sdf_raw(sm->part[im], t, sd.last_b_off, sd.last_bias, wsdf) / sd.scale;
       if (TRAIN && 2 * pair + im < n_tiles) {                        // row 0 of OUTF (the raw sdf output) and the zero tail beyond row F - 1
         float* base = to.OUTF + (2 * pair + im) * (long)to.outf_tiles * 1024;
-        const float* pr = sm->part[im];
-        base[t] = ((pr[t] + pr[32 + t]) + (pr[64 + t] + pr[96 + t])) + (sd.last_b_off > 0 ? wsdf[sd.last_b_off][0] : sd.last_bias);
+        base[t] = sdf_raw(sm->part[im], t, sd.last_b_off, sd.last_bias, wsdf);
         for (int f = 32 * sd.layers[n_lin - 1].n_out_tiles + 1; f < 32 * to.outf_tiles; ++f) base[f * 32 + t] = 0.f;
       }
     }
@@ -627,19 +531,8 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
     FS(6)
     if (tid < 192) {
       const int im = tid / 96, r = tid - 96 * im, pp = r & 31, c = r >> 5;
-      const float x0 = sm->pts[im][pp * 3 + 0] * sd.scale, x1 = sm->pts[im][pp * 3 + 1] * sd.scale, x2 = sm->pts[im][pp * 3 + 2] * sd.scale;
-      const float* ldsf = reinterpret_cast<const float*>(lds + (size_t)im * IS);
-      auto G = [&](int f) {
-        const int t = f >> 5, fi = f & 31, hh = fi & 1, rr = fi >> 1;
-        return ldsf[(((E0 + t * 4 + (rr >> 2)) * 64) + pp + 32 * hh) * 4 + (rr & 3)];
-      };
-      float g = G(c);
-      int cc;
-      for (int k = 0; k < sd.multires; ++k) {
-        const int fs = 3 + 6 * k + c, fc = fs + 3;
-        g = fmaf(G(fs), posenc_jac(fs, x0, x1, x2, &cc), g);
-        g = fmaf(G(fc), posenc_jac(fc, x0, x1, x2, &cc), g);
-      }
+      const f32x4* li = lds + (size_t)im * IS;
+      const float g = embed_chain([&](int f) { return lds_feat(li, E0, f, pp); }, c, sd.multires, sm->pts[im] + pp * 3, sd.scale);
       sm->grad[im][pp * 3 + c] = g;
       const long pt = ((2 * pair + im) << 5) + pp;
       if (pt < P) out_grad[pt * 3 + c] = g;
@@ -655,15 +548,8 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
       for (int r = w4; r < (TRAIN ? 4 * to.extr_tiles : cd.extra_rows); r += 4) {
         f32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int f = row_feat(r, h, j);
-          float val = 0.f;
-          if (r >= cd.extra_rows) val = 0.f;
-          else if (f < 3) val = f == 0 ? px : (f == 1 ? py : pz);
-          else if (f < 3 + cd.n_view_feats) val = posenc_feat(f - 3, dx, dy, dz);
-          else if (f < cd.extra_feats) val = sm->grad[img][p * 3 + (f - 3 - cd.n_view_feats)];
-          v[j] = val;
-        }
+        for (int j = 0; j < 4; ++j)
+          v[j] = r < cd.extra_rows ? col_extra_feat(row_feat(r, h, j), px, py, pz, dx, dy, dz, sm->grad[img] + p * 3, cd.n_view_feats, cd.extra_feats) : 0.f;
         if (r < cd.extra_rows) ldsi[(E0 + r) * 64 + lane] = v;
         if (TRAIN && ptile_w < n_tiles) tfmt_store_quad(to.EXTR, ptile_w, to.extr_tiles, r >> 2, r & 3, lane, v);
       }
@@ -729,10 +615,7 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
       __syncthreads();
       if (tid < 192) {
         const int im = tid / 96, r = tid - 96 * im, pp = r & 31, o = r >> 5;
-        const float* pr = sm->part[im];
-        float v = ((pr[(0 * 32 + pp) * 3 + o] + pr[(1 * 32 + pp) * 3 + o]) + (pr[(2 * 32 + pp) * 3 + o] + pr[(3 * 32 + pp) * 3 + o])) +
-                  (cd.last_b_off > 0 ? wcol[cd.last_b_off][o] : cd.last_bias[o]);
-        if (cd.squeeze_out) v = 1.f / (1.f + expf(-v));
+        const float v = rgb_out(sm->part[im], pp, o, cd.last_b_off, cd.last_bias[o], cd.squeeze_out, wcol);
         const long pt = ((2 * pair + im) << 5) + pp;
         if (pt < P) out_rgb[pt * 3 + o] = v;
       }
@@ -754,57 +637,42 @@ int check_sdf_desc(const SdfDesc& d) {
   return 0;
 }
 
-size_t lds_bytes(int MT) { return (size_t)(E_ROWS + 8 * MT) * 1024 + sizeof(Smalls); }
-size_t lds_bytes2(int MT) { return (size_t)2 * (E_ROWS + 8 * MT) * 1024 + sizeof(Smalls2); }
+template <int NIMG>
+size_t lds_bytes(int MT) { return (size_t)NIMG * (E_ROWS + 8 * MT) * 1024 + sizeof(Smalls<NIMG>); }
 
 // two 32-point images per workgroup for networks wide enough to give eight waves a tile each (and small enough to fit),
 // unless VQN_NEUS_TILE32 is set
 bool use_two_images(int MT) {
   static const bool forced32 = getenv("VQN_NEUS_TILE32") != nullptr;
-  return !forced32 && MT >= 5 && lds_bytes2(MT) <= 160 * 1024;
+  return !forced32 && MT >= 5 && lds_bytes<2>(MT) <= 160 * 1024;
 }
+
+bool extras_rows_ok(const ColDesc& cd) { return cd.extra_rows >= 1 && cd.extra_rows <= 8; }
 
 }  // namespace
 
 extern "C" int vqn_neus_sdf_points(const int32_t* sdf_desc, const float* wbuf_sdf, const float* rays_o,
                                    const float* rays_d, const float* z, const float* pts, int64_t P, int S,
                                    float* out_sdf, void* stream) {
-  VQN_CHECK_ARG(sdf_desc && wbuf_sdf && out_sdf, "sdf_desc, wbuf_sdf, out_sdf must be non-null");
-  VQN_CHECK_ARG(P >= 0, "P >= 0");
-  if (P == 0) return VQN_OK;
-  VQN_CHECK_ARG(pts != nullptr || (rays_o && rays_d && z && S > 0), "either pts or (rays_o, rays_d, z, S) required");
   SdfDesc sd;
-  memcpy(&sd, sdf_desc, sizeof(SdfDesc));
-  VQN_CHECK_SHAPE(check_sdf_desc(sd) == 0, "invalid SDF network descriptor");
+  const int rc = neus_sdf_args(__func__, sdf_desc, wbuf_sdf, rays_o, rays_d, z, pts, P, S, out_sdf, check_sdf_desc,
+                               "invalid SDF network descriptor", &sd);
+  if (rc != VQN_OK || P == 0) return rc;
   ColDesc cd;
   memset(&cd, 0, sizeof(cd));
   const long n_tiles = (P + 31) / 32;
-  if (use_two_images(sd.max_tiles)) {
-    const size_t lds2 = lds_bytes2(sd.max_tiles);
-    VQN_HIP(hipFuncSetAttribute((const void*)neus_points2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    long grid = (long)vqn_num_cus();
-    if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-    hipLaunchKernelGGL(neus_points2_kernel<false>, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
-                       reinterpret_cast<const f32x4*>(wbuf_sdf), (const f32x4*)nullptr, rays_o, rays_d, z, pts,
-                       (const float*)nullptr, (long)P, S, (f32x4*)nullptr, out_sdf, (float*)nullptr, (float*)nullptr, TrainOut{});
-    VQN_LAUNCH_CHECK();
-    return VQN_OK;
-  }
-  const size_t lds = lds_bytes(sd.max_tiles);
+  const f32x4* ws = reinterpret_cast<const f32x4*>(wbuf_sdf);
+  if (use_two_images(sd.max_tiles))
+    return neus_launch(__func__, neus_points2_kernel<false>, true, pair_grid(n_tiles, 2, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws,
+                       nullptr, rays_o, rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
+  const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  if (lds > 64 * 1024)
-    VQN_HIP(hipFuncSetAttribute((const void*)neus_points_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  long grid = (long)vqn_num_cus() * 2;
-  if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL(neus_points_kernel<false>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, sd, cd,
-                     reinterpret_cast<const f32x4*>(wbuf_sdf), (const f32x4*)nullptr, rays_o, rays_d, z, pts,
-                     (const float*)nullptr, (long)P, S, (f32x4*)nullptr, out_sdf, (float*)nullptr, (float*)nullptr);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return neus_launch(__func__, neus_points_kernel<false>, lds > 64 * 1024, pair_grid(n_tiles, 1, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o, rays_d,
+                     z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr);
 }
 
 // Training forward: vqn_neus_fine_points at explicit (pts, dirs) that ALSO writes the saved tensors of the training engine (see
-// TrainOut above).  tensors: device pointers in the order [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC] with nL = n_lin - 1
+// TrainOut in neus_phases.h).  tensors: device pointers in the order [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC] with nL = n_lin - 1
 // SDF hidden layers and nC = col n_lin - 1 colour hidden layers; each [ceil(P/32)][tiles][32][32] f32 with tiles = ceil(width / 32)
 // (e_tiles / outf_tiles / extr_tiles given, the others from the descriptors).  Needs the two-image form (networks of >= 5 tiles that fit).
 extern "C" int vqn_neus_train_fwd(const int32_t* sdf_desc, const float* wbuf_sdf, const int32_t* col_desc, const float* wbuf_col,
@@ -824,28 +692,13 @@ extern "C" int vqn_neus_train_fwd(const int32_t* sdf_desc, const float* wbuf_sdf
   VQN_CHECK_ARG(n_tensors == 3 + 2 * nL + nC, "tensors: [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC]");
   VQN_CHECK_SHAPE(e_tiles * 4 >= sd.emb_rows && e_tiles <= 2 && extr_tiles * 4 >= cd.extra_rows && extr_tiles <= 2 &&
                   outf_tiles >= sd.layers[sd.n_lin - 1].n_out_tiles && 32 * outf_tiles >= 32 * sd.layers[sd.n_lin - 1].n_out_tiles + 1, "tile counts");
-  TrainOut to;
-  memset(&to, 0, sizeof(to));
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
-  to.E = tensors[0]; to.OUTF = tensors[1]; to.EXTR = tensors[2];
-  for (int l = 1; l <= nL; ++l) to.U[l] = tensors[3 + (l - 1)];
-  for (int l = 0; l < nL; ++l) to.GH[l] = tensors[3 + nL + l];
-  for (int l = 1; l <= nC; ++l) to.C[l] = tensors[3 + 2 * nL + (l - 1)];
-  to.e_tiles = e_tiles; to.outf_tiles = outf_tiles; to.extr_tiles = extr_tiles;
-  const long n_tiles = (P + 31) / 32;
-  const int64_t per_wg = (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
-  const size_t lds2 = lds_bytes2(sd.max_tiles);
-  VQN_HIP(hipFuncSetAttribute((const void*)neus_points2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  long grid = (long)vqn_num_cus();
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-  if ((int64_t)grid * 2 * per_wg > scratch_bytes) grid = (long)(scratch_bytes / (2 * per_wg));
+  const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  hipLaunchKernelGGL((neus_points2_kernel<true, true>), dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
-                     reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, pts, dirs, (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n,
-                     out_rgb, to);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return neus_launch(__func__, neus_points2_kernel<true, true>, true, grid, 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd,
+                     reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr, nullptr, pts, dirs,
+                     (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb,
+                     neus_train_out(tensors, nL, nC, e_tiles, outf_tiles, extr_tiles));
 }
 
 extern "C" int64_t vqn_neus_fine_scratch_bytes(const int32_t* sdf_desc) {
@@ -857,9 +710,9 @@ extern "C" int64_t vqn_neus_fine_scratch_bytes(const int32_t* sdf_desc) {
   if (emb_rows >= 1 && emb_rows <= 12) sd.emb_rows = 1;
   if (check_sdf_desc(sd) != 0) return -2;
 #ifdef VQN_DIAG_STASH_ROT
-  return (int64_t)VQN_DIAG_STASH_ROT * vqn_num_cus() * 2 * (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
+  return (int64_t)VQN_DIAG_STASH_ROT * vqn_num_cus() * 2 * neus_stash_bytes(sd);
 #else
-  return (int64_t)vqn_num_cus() * 2 * (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
+  return (int64_t)vqn_num_cus() * 2 * neus_stash_bytes(sd);
 #endif
 }
 
@@ -868,60 +721,35 @@ extern "C" int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_s
                                     const float* pts, const float* dirs, int64_t P, int S, void* scratch,
                                     int64_t scratch_bytes, float* out_sdf, float* out_grad, float* out_rgb,
                                     void* stream) {
-  VQN_CHECK_ARG(sdf_desc && wbuf_sdf && col_desc && wbuf_col, "descriptors and weight packs must be non-null");
-  VQN_CHECK_ARG(out_sdf && out_grad && scratch, "out_sdf, out_grad and scratch must be non-null");
-  VQN_CHECK_ARG(P >= 0, "P >= 0");
-  if (P == 0) return VQN_OK;
-  VQN_CHECK_ARG((pts != nullptr && dirs != nullptr) || (rays_o && rays_d && z && S > 0),
-                "either (pts, dirs) or (rays_o, rays_d, z, S) required");
   SdfDesc sd;
   ColDesc cd;
-  memcpy(&sd, sdf_desc, sizeof(SdfDesc));
-  memcpy(&cd, col_desc, sizeof(ColDesc));
-  VQN_CHECK_SHAPE(check_sdf_desc(sd) == 0, "invalid SDF network descriptor");
-  if (cd.n_lin != 0) {
-    VQN_CHECK_ARG(out_rgb != nullptr, "out_rgb must be non-null when a colour net is given");
-    VQN_CHECK_SHAPE(sd.layers[sd.n_lin - 1].n_out_tiles >= 1, "SDF network has no feature outputs (d_out == 1)");
-    VQN_CHECK_SHAPE(cd.n_lin >= 2 && cd.n_lin <= VQN_MAX_COL_LAYERS && cd.d_out == 3, "colour net: 2..8 layers, d_out == 3");
-    VQN_CHECK_SHAPE(cd.extra_feats >= 3 && cd.extra_feats <= 64 && cd.extra_rows >= 1 && cd.extra_rows <= 8, "colour net extras");
-    for (int l = 0; l < cd.n_lin - 1; ++l)
-      VQN_CHECK_SHAPE(cd.layers[l].n_out_tiles >= 1 && cd.layers[l].n_out_tiles <= sd.max_tiles, "colour layer wider than max_tiles");
-    // a folded colour pack (vqn_neus_fold_pack) announces its three blocks together; 0 = not folded
+  const int rc = neus_fine_args(__func__, sdf_desc, wbuf_sdf, col_desc, wbuf_col, rays_o, rays_d, z, pts, dirs, P, S, scratch, out_sdf,
+                                out_grad, out_rgb, check_sdf_desc, "invalid SDF network descriptor", extras_rows_ok, &sd, &cd);
+  if (rc != VQN_OK || P == 0) return rc;
+  if (cd.n_lin != 0)       // a folded colour pack (vqn_neus_fold_pack) announces its three blocks together; 0 = not folded
     VQN_CHECK_ARG((cd.reserved1 > 0 && cd.reserved2 > cd.reserved1 && cd.reserved3 > cd.reserved2) ||
                   (cd.reserved1 == 0 && cd.reserved2 == 0 && cd.reserved3 == 0), "col_desc: fold offsets (reserved1..3) inconsistent");
-  }
   const long n_tiles = (P + 31) / 32;
-  const int64_t per_wg = (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
+  const int64_t per_img = neus_stash_bytes(sd);
+  const f32x4* ws = reinterpret_cast<const f32x4*>(wbuf_sdf);
+  const f32x4* wc = reinterpret_cast<const f32x4*>(wbuf_col);
   if (use_two_images(sd.max_tiles)) {
-    const size_t lds2 = lds_bytes2(sd.max_tiles);
     const bool fold = cd.n_lin != 0 && cd.reserved1 > 0;
-    const auto kernel = fold ? neus_points2_kernel<true, false, true> : neus_points2_kernel<true>;
-    VQN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    long grid = (long)vqn_num_cus();
-    if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
 #ifdef VQN_DIAG_STASH_ROT
-    VQN_CHECK_ARG((int64_t)VQN_DIAG_STASH_ROT * grid * 2 * per_wg <= scratch_bytes, "diag build: scratch must hold ROT regions per workgroup");
+    const long grid = pair_grid(n_tiles, 2, 0, 0);
+    VQN_CHECK_ARG((int64_t)VQN_DIAG_STASH_ROT * grid * 2 * per_img <= scratch_bytes, "diag build: scratch must hold ROT regions per workgroup");
 #else
-    if ((int64_t)grid * 2 * per_wg > scratch_bytes) grid = (long)(scratch_bytes / (2 * per_wg));
+    const long grid = pair_grid(n_tiles, 2, per_img, scratch_bytes);
 #endif
     VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
-                       reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d,
-                       z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb, TrainOut{});
-    VQN_LAUNCH_CHECK();
-    return VQN_OK;
+    return neus_launch(__func__, fold ? neus_points2_kernel<true, false, true> : neus_points2_kernel<true>, true, grid, 512, lds_bytes<2>(sd.max_tiles),
+                       stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad,
+                       out_rgb, TrainOut{});
   }
-  const size_t lds = lds_bytes(sd.max_tiles);
+  const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  if (lds > 64 * 1024)
-    VQN_HIP(hipFuncSetAttribute((const void*)neus_points_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  long grid = (long)vqn_num_cus() * 2;
-  if (grid > n_tiles) grid = n_tiles;
-  if ((int64_t)grid * per_wg > scratch_bytes) grid = (long)(scratch_bytes / per_wg);
+  const long grid = pair_grid(n_tiles, 1, per_img, scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  hipLaunchKernelGGL(neus_points_kernel<true>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, sd, cd,
-                     reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d,
-                     z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return neus_launch(__func__, neus_points_kernel<true>, lds > 64 * 1024, grid, 256, lds, stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S,
+                     reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);
 }

@@ -12,7 +12,7 @@
 // features), keeps the finished tile in registers as its six piece fragments, and writes it over the input only after a
 // workgroup barrier has seen every wave out of its K loop -- two barriers per layer instead of one.
 #include "mlp_prims_x3.h"
-#include "vqn_neus_desc.h"
+#include "neus_launch.h"
 #include <stdlib.h>
 
 using namespace eng;
@@ -30,41 +30,14 @@ constexpr int MAX_CALLS = 40;
 constexpr int RING = 2;
 constexpr int NW = 8;
 
-struct Smalls2 {
-  float pts[2][96], dirs[2][96], part[2][512], grad[2][96];
+struct SmallsTab : Smalls<2> {
   int tab[MAX_CALLS * 4];     // GEMM calls of one tile pair in program order: {float4 offset, 0 = SDF pack / 1 = colour pack, K blocks, out tiles}
   int n_calls;
 };
 
 // ---- training forward (TRAIN): as neus_points2_kernel<FINE, TRAIN> of csrc/neus_mlp.hip -- the fine kernel also leaves what the backward
-// (csrc/neus_train_bwd.hip) and the weight-gradient contraction read, in the tile format [point tile][feature tile][32 features][32 points]
-// f32.  The values stored are the f32 ones the epilogues hold BEFORE the split into bf16 pieces.
-struct TrainOut {
-  float* E; float* OUTF; float* EXTR;
-  float* U[VQN_MAX_SDF_LAYERS]; float* GH[VQN_MAX_SDF_LAYERS]; float* C[VQN_MAX_COL_LAYERS];
-  int e_tiles, outf_tiles, extr_tiles;
-};
-// an accumulator tile: register i of lane (p, h) is feature (i & 3) + 8 (i >> 2) + 4 h of the tile
-__device__ __forceinline__ void tfmt_store_acc(float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, const float (&v)[16]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(v[0]), "v"(v[3]), "v"(v[7]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) __builtin_nontemporal_store(v[i], base + ((i & 3) + 8 * (i >> 2)) * 32);
-}
-// a K step of an image: slot jj of lane (p, h) is feature 16 sl + 8 (jj >> 2) + 4 h + (jj & 3)
-__device__ __forceinline__ void tfmt_store_step(float* __restrict__ T, const long ptile, const int n_ft, const int sl, const int lane, const float (&x)[8]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(x[0]), "v"(x[3]), "v"(x[7]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + (sl >> 1)) * 32 + 16 * (sl & 1) + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) __builtin_nontemporal_store(x[jj], base + (8 * (jj >> 2) + (jj & 3)) * 32);
-}
-
+// (csrc/neus_train_bwd.hip) and the weight-gradient contraction read, in the tile format (TrainOut, tfmt_store_acc / tfmt_store_step of
+// neus_phases.h).  The values stored are the f32 ones the epilogues hold BEFORE the split into bf16 pieces.
 template <bool FINE, int NACC, bool TRAIN = false>
 __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
     const SdfDesc sd, const ColDesc cd, const f32x4* __restrict__ wsdf, const f32x4* __restrict__ wcol,
@@ -75,7 +48,7 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
   extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
   const int MT = sd.max_tiles;
   const int IMG = E_ROWS + 6 * MT, IS = IMG * 64;            // rows / float4 per image
-  Smalls2* sm = reinterpret_cast<Smalls2*>(lds + (size_t)2 * IS);
+  SmallsTab* sm = reinterpret_cast<SmallsTab*>(lds + (size_t)2 * IS);
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int img = wave >> 2, w4 = wave & 3;                  // VALU phases: this wave's image and its rank among the image's 4 waves
@@ -168,22 +141,7 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
     // ---------------- points of both tiles ----------------
     if (tid < 64) {
       const int im = tid >> 5, t = tid & 31;
-      long pt = ((2 * pair + im) << 5) + t;
-      if (pt >= P) pt = P - 1;
-      float x, y, z, dx = 0.f, dy = 0.f, dz = 0.f;
-      if (pts_direct != nullptr) {
-        x = pts_direct[pt * 3 + 0]; y = pts_direct[pt * 3 + 1]; z = pts_direct[pt * 3 + 2];
-        if (FINE) { dx = dirs_direct[pt * 3 + 0]; dy = dirs_direct[pt * 3 + 1]; dz = dirs_direct[pt * 3 + 2]; }
-      } else {
-        const long ray = pt / S;
-        const float tt = zv[pt];
-        dx = rays_d[ray * 3 + 0]; dy = rays_d[ray * 3 + 1]; dz = rays_d[ray * 3 + 2];
-        x = rays_o[ray * 3 + 0] + __fmul_rn(dx, tt);
-        y = rays_o[ray * 3 + 1] + __fmul_rn(dy, tt);
-        z = rays_o[ray * 3 + 2] + __fmul_rn(dz, tt);
-      }
-      sm->pts[im][t * 3 + 0] = x; sm->pts[im][t * 3 + 1] = y; sm->pts[im][t * 3 + 2] = z;
-      sm->dirs[im][t * 3 + 0] = dx; sm->dirs[im][t * 3 + 1] = dy; sm->dirs[im][t * 3 + 2] = dz;
+      load_point<FINE>(((2 * pair + im) << 5) + t, P, S, rays_o, rays_d, zv, pts_direct, dirs_direct, sm->pts[im] + t * 3, sm->dirs[im] + t * 3);
     }
     __syncthreads();
     const float xs = sm->pts[img][p * 3 + 0] * sd.scale, ys = sm->pts[img][p * 3 + 1] * sd.scale, zs = sm->pts[img][p * 3 + 2] * sd.scale;
@@ -192,10 +150,7 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
     for (int sl = w4; sl < (TRAIN ? 2 * to.e_tiles : sd.emb_rows / 3); sl += 4) {
       float x[8];
 #pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int f = step_feat(sl, h, jj);
-        x[jj] = (sl < sd.emb_rows / 3 && f < sd.emb_feats) ? posenc_feat(f, xs, ys, zs) : 0.f;
-      }
+      for (int jj = 0; jj < 8; ++jj) x[jj] = sl < sd.emb_rows / 3 ? emb_feat(step_feat(sl, h, jj), sd.emb_feats, xs, ys, zs) : 0.f;
       if (TRAIN && ptile_w < n_tiles) tfmt_store_step(to.E, ptile_w, to.e_tiles, sl, lane, x);
       if (sl < sd.emb_rows / 3) {
         f32x4 q0, q1, q2;
@@ -262,12 +217,10 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
     if (tid < 64) {
       const int im = tid >> 5, t = tid & 31;
       const long pt = ((2 * pair + im) << 5) + t;
-      const float* pr = sm->part[im];
-      const float s = ((pr[t] + pr[32 + t]) + (pr[64 + t] + pr[96 + t])) + (sd.last_b_off > 0 ? wsdf[sd.last_b_off][0] : sd.last_bias);
-      if (pt < P) out_sdf[pt] = s / sd.scale;
+      if (pt < P) out_sdf[pt] = sdf_raw(sm->part[im], t, sd.last_b_off, sd.last_bias, wsdf) / sd.scale;
       if (TRAIN && 2 * pair + im < n_tiles) {                 // row 0 of OUTF (the raw sdf output) and the zero tail beyond row F - 1
         float* base = to.OUTF + (2 * pair + im) * (long)to.outf_tiles * 1024;
-        base[t] = s;
+        base[t] = sdf_raw(sm->part[im], t, sd.last_b_off, sd.last_bias, wsdf);
         for (int f = 32 * sd.layers[n_lin - 1].n_out_tiles + 1; f < 32 * to.outf_tiles; ++f) base[f * 32 + t] = 0.f;
       }
     }
@@ -385,14 +338,7 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
     if (tid < 192) {
       const int im = tid / 96, r = tid - 96 * im, pp = r & 31, c = r >> 5;
       const f32x4* li = lds + (size_t)im * IS;
-      const float x0 = sm->pts[im][pp * 3 + 0] * sd.scale, x1 = sm->pts[im][pp * 3 + 1] * sd.scale, x2 = sm->pts[im][pp * 3 + 2] * sd.scale;
-      float g = lds_feat_x3(li, E0, c, pp);
-      int cc;
-      for (int k = 0; k < sd.multires; ++k) {
-        const int fs = 3 + 6 * k + c, fc = fs + 3;
-        g = fmaf(lds_feat_x3(li, E0, fs, pp), posenc_jac(fs, x0, x1, x2, &cc), g);
-        g = fmaf(lds_feat_x3(li, E0, fc, pp), posenc_jac(fc, x0, x1, x2, &cc), g);
-      }
+      const float g = embed_chain([&](int f) { return lds_feat_x3(li, E0, f, pp); }, c, sd.multires, sm->pts[im] + pp * 3, sd.scale);
       sm->grad[im][pp * 3 + c] = g;
       const long pt = ((2 * pair + im) << 5) + pp;
       if (pt < P) out_grad[pt * 3 + c] = g;
@@ -407,15 +353,8 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
       for (int sl = w4; sl < (TRAIN ? 2 * to.extr_tiles : cd.extra_rows / 3); sl += 4) {
         float x[8];
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-          const int f = step_feat(sl, h, jj);
-          float val = 0.f;
-          if (sl >= cd.extra_rows / 3) val = 0.f;
-          else if (f < 3) val = f == 0 ? px : (f == 1 ? py : pz);
-          else if (f < 3 + cd.n_view_feats) val = posenc_feat(f - 3, dx, dy, dz);
-          else if (f < cd.extra_feats) val = sm->grad[img][p * 3 + (f - 3 - cd.n_view_feats)];
-          x[jj] = val;
-        }
+        for (int jj = 0; jj < 8; ++jj)
+          x[jj] = sl < cd.extra_rows / 3 ? col_extra_feat(step_feat(sl, h, jj), px, py, pz, dx, dy, dz, sm->grad[img] + p * 3, cd.n_view_feats, cd.extra_feats) : 0.f;
         if (TRAIN && ptile_w < n_tiles) tfmt_store_step(to.EXTR, ptile_w, to.extr_tiles, sl, lane, x);
         if (sl < cd.extra_rows / 3) {
           f32x4 q0, q1, q2;
@@ -459,10 +398,7 @@ __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
       __syncthreads();
       if (tid < 192) {
         const int im = tid / 96, r = tid - 96 * im, pp = r & 31, oc = r >> 5;
-        const float* pr = sm->part[im];
-        float v = ((pr[(0 * 32 + pp) * 3 + oc] + pr[(1 * 32 + pp) * 3 + oc]) + (pr[(2 * 32 + pp) * 3 + oc] + pr[(3 * 32 + pp) * 3 + oc])) +
-                  (cd.last_b_off > 0 ? wcol[cd.last_b_off][oc] : cd.last_bias[oc]);
-        if (cd.squeeze_out) v = 1.f / (1.f + expf(-v));
+        const float v = rgb_out(sm->part[im], pp, oc, cd.last_b_off, cd.last_bias[oc], cd.squeeze_out, wcol);
         const long pt = ((2 * pair + im) << 5) + pp;
         if (pt < P) out_rgb[pt * 3 + oc] = v;
       }
@@ -483,7 +419,7 @@ int check_sdf_desc_x3(const SdfDesc& d) {
   return 0;
 }
 
-size_t lds_bytes_x3(int MT) { return (size_t)2 * (E_ROWS + 6 * MT) * 1024 + sizeof(Smalls2); }
+size_t lds_bytes_x3(int MT) { return (size_t)2 * (E_ROWS + 6 * MT) * 1024 + sizeof(SmallsTab); }
 
 // accumulators per image: 1 (all six terms of a step into one) or 2 (a0 w0 apart from the five smaller terms); VQN_X3_NACC overrides
 int x3_nacc() {
@@ -493,32 +429,25 @@ int x3_nacc() {
   return n;
 }
 
+bool extras_rows_ok(const ColDesc& cd) { return cd.extra_rows == x3_rows(cd.extra_feats); }
+
+constexpr const char* DESC_MSG = "invalid SDF network descriptor for the x3 engine (x3 packs: 3 rows per 16 features; layers of at most 256 outputs)";
+
 }  // namespace
 
 extern "C" int vqn_neus_sdf_points_x3(const int32_t* sdf_desc, const float* wbuf_sdf, const float* rays_o,
                                       const float* rays_d, const float* z, const float* pts, int64_t P, int S,
                                       float* out_sdf, void* stream) {
-  VQN_CHECK_ARG(sdf_desc && wbuf_sdf && out_sdf, "sdf_desc, wbuf_sdf, out_sdf must be non-null");
-  VQN_CHECK_ARG(P >= 0, "P >= 0");
-  if (P == 0) return VQN_OK;
-  VQN_CHECK_ARG(pts != nullptr || (rays_o && rays_d && z && S > 0), "either pts or (rays_o, rays_d, z, S) required");
   SdfDesc sd;
-  memcpy(&sd, sdf_desc, sizeof(SdfDesc));
-  VQN_CHECK_SHAPE(check_sdf_desc_x3(sd) == 0, "invalid SDF network descriptor for the x3 engine (x3 packs: 3 rows per 16 features; layers of at most 256 outputs)");
+  const int rc = neus_sdf_args(__func__, sdf_desc, wbuf_sdf, rays_o, rays_d, z, pts, P, S, out_sdf, check_sdf_desc_x3, DESC_MSG, &sd);
+  if (rc != VQN_OK || P == 0) return rc;
   ColDesc cd;
   memset(&cd, 0, sizeof(cd));
-  const long n_tiles = (P + 31) / 32;
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
-  auto kern = x3_nacc() == 2 ? neus_points_x3_kernel<false, 2> : neus_points_x3_kernel<false, 1>;
-  VQN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  long grid = (long)vqn_num_cus();
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
-                     reinterpret_cast<const f32x4*>(wbuf_sdf), (const f32x4*)nullptr, rays_o, rays_d, z, pts,
-                     (const float*)nullptr, (long)P, S, (f32x4*)nullptr, out_sdf, (float*)nullptr, (float*)nullptr, TrainOut{});
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return neus_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<false, 2> : neus_points_x3_kernel<false, 1>, true,
+                     pair_grid((P + 31) / 32, 2, 0, 0), 512, lds2, stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), nullptr, rays_o,
+                     rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
 }
 
 extern "C" int vqn_neus_fine_points_x3(const int32_t* sdf_desc, const float* wbuf_sdf, const int32_t* col_desc,
@@ -526,40 +455,18 @@ extern "C" int vqn_neus_fine_points_x3(const int32_t* sdf_desc, const float* wbu
                                        const float* pts, const float* dirs, int64_t P, int S, void* scratch,
                                        int64_t scratch_bytes, float* out_sdf, float* out_grad, float* out_rgb,
                                        void* stream) {
-  VQN_CHECK_ARG(sdf_desc && wbuf_sdf && col_desc && wbuf_col, "descriptors and weight packs must be non-null");
-  VQN_CHECK_ARG(out_sdf && out_grad && scratch, "out_sdf, out_grad and scratch must be non-null");
-  VQN_CHECK_ARG(P >= 0, "P >= 0");
-  if (P == 0) return VQN_OK;
-  VQN_CHECK_ARG((pts != nullptr && dirs != nullptr) || (rays_o && rays_d && z && S > 0),
-                "either (pts, dirs) or (rays_o, rays_d, z, S) required");
   SdfDesc sd;
   ColDesc cd;
-  memcpy(&sd, sdf_desc, sizeof(SdfDesc));
-  memcpy(&cd, col_desc, sizeof(ColDesc));
-  VQN_CHECK_SHAPE(check_sdf_desc_x3(sd) == 0, "invalid SDF network descriptor for the x3 engine (x3 packs: 3 rows per 16 features; layers of at most 256 outputs)");
-  if (cd.n_lin != 0) {
-    VQN_CHECK_ARG(out_rgb != nullptr, "out_rgb must be non-null when a colour net is given");
-    VQN_CHECK_SHAPE(sd.layers[sd.n_lin - 1].n_out_tiles >= 1, "SDF network has no feature outputs (d_out == 1)");
-    VQN_CHECK_SHAPE(cd.n_lin >= 2 && cd.n_lin <= VQN_MAX_COL_LAYERS && cd.d_out == 3, "colour net: 2..8 layers, d_out == 3");
-    VQN_CHECK_SHAPE(cd.extra_feats >= 3 && cd.extra_feats <= 64 && cd.extra_rows == x3_rows(cd.extra_feats), "colour net extras");
-    for (int l = 0; l < cd.n_lin - 1; ++l)
-      VQN_CHECK_SHAPE(cd.layers[l].n_out_tiles >= 1 && cd.layers[l].n_out_tiles <= sd.max_tiles, "colour layer wider than max_tiles");
-  }
-  const long n_tiles = (P + 31) / 32;
-  const int64_t per_wg = (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
+  const int rc = neus_fine_args(__func__, sdf_desc, wbuf_sdf, col_desc, wbuf_col, rays_o, rays_d, z, pts, dirs, P, S, scratch, out_sdf,
+                                out_grad, out_rgb, check_sdf_desc_x3, DESC_MSG, extras_rows_ok, &sd, &cd);
+  if (rc != VQN_OK || P == 0) return rc;
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
-  auto kern = x3_nacc() == 2 ? neus_points_x3_kernel<true, 2> : neus_points_x3_kernel<true, 1>;
-  VQN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  long grid = (long)vqn_num_cus();
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-  if ((int64_t)grid * 2 * per_wg > scratch_bytes) grid = (long)(scratch_bytes / (2 * per_wg));
+  const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd,
-                     reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d,
-                     z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb, TrainOut{});
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return neus_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2> : neus_points_x3_kernel<true, 1>, true, grid, 512, lds2, stream, sd,
+                     cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d, z, pts, dirs,
+                     (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb, TrainOut{});
 }
 
 // Training forward on the exact-split engine: vqn_neus_train_fwd with x3 packs and descriptors (vqn_neus_pack_create(..., f16s = 2)).
@@ -576,34 +483,20 @@ extern "C" int vqn_neus_train_fwd_x3(const int32_t* sdf_desc, const float* wbuf_
   memcpy(&cd, col_desc, sizeof(ColDesc));
   VQN_CHECK_SHAPE(check_sdf_desc_x3(sd) == 0, "invalid SDF network descriptor for the x3 engine");
   VQN_CHECK_SHAPE(cd.n_lin >= 2 && cd.n_lin <= VQN_MAX_COL_LAYERS && cd.d_out == 3 && sd.layers[sd.n_lin - 1].n_out_tiles >= 1, "colour net");
-  VQN_CHECK_SHAPE(cd.extra_feats >= 3 && cd.extra_feats <= 64 && cd.extra_rows == x3_rows(cd.extra_feats), "colour net extras");
+  VQN_CHECK_SHAPE(cd.extra_feats >= 3 && cd.extra_feats <= 64 && extras_rows_ok(cd), "colour net extras");
   for (int l = 0; l < cd.n_lin - 1; ++l)
     VQN_CHECK_SHAPE(cd.layers[l].n_out_tiles >= 1 && cd.layers[l].n_out_tiles <= sd.max_tiles, "colour layer wider than max_tiles");
   const int nL = sd.n_lin - 1, nC = cd.n_lin - 1;
   VQN_CHECK_ARG(n_tensors == 3 + 2 * nL + nC, "tensors: [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC]");
   VQN_CHECK_SHAPE(2 * e_tiles * 3 >= sd.emb_rows && e_tiles <= 2 && 2 * extr_tiles * 3 >= cd.extra_rows && extr_tiles <= 2 &&
                   32 * outf_tiles >= 32 * sd.layers[sd.n_lin - 1].n_out_tiles + 1, "tile counts");
-  TrainOut to;
-  memset(&to, 0, sizeof(to));
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
-  to.E = tensors[0]; to.OUTF = tensors[1]; to.EXTR = tensors[2];
-  for (int l = 1; l <= nL; ++l) to.U[l] = tensors[3 + (l - 1)];
-  for (int l = 0; l < nL; ++l) to.GH[l] = tensors[3 + nL + l];
-  for (int l = 1; l <= nC; ++l) to.C[l] = tensors[3 + 2 * nL + (l - 1)];
-  to.e_tiles = e_tiles; to.outf_tiles = outf_tiles; to.extr_tiles = extr_tiles;
-  const long n_tiles = (P + 31) / 32;
-  const int64_t per_wg = (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024;
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
-  auto kern = x3_nacc() == 2 ? neus_points_x3_kernel<true, 2, true> : neus_points_x3_kernel<true, 1, true>;
-  VQN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  long grid = (long)vqn_num_cus();
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-  if ((int64_t)grid * 2 * per_wg > scratch_bytes) grid = (long)(scratch_bytes / (2 * per_wg));
+  const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds2, (hipStream_t)stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf),
-                     reinterpret_cast<const f32x4*>(wbuf_col), (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pts, dirs,
-                     (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb, to);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return neus_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2, true> : neus_points_x3_kernel<true, 1, true>, true, grid, 512, lds2,
+                     stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr,
+                     nullptr, pts, dirs, (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb,
+                     neus_train_out(tensors, nL, nC, e_tiles, outf_tiles, extr_tiles));
 }

@@ -18,7 +18,7 @@
 // (the same statement as the interpreted programs prog_cbwd / prog_sbwd of geo/train_programs.py, which remain the path of
 // networks this kernel does not take: fewer than five or more than eight feature tiles.  csrc/neus_train_bwd_x3.hip is the same pass on the
 // exact-split engine, the trainers' default.)
-#include "mlp_prims.h"
+#include "neus_phases.h"
 #include "vqnerf_hip.h"
 #include <stdlib.h>
 
@@ -58,13 +58,8 @@ struct SmallsB {
   float pts[2][96], dout[2][96], gn[2][96], v[2][96], gs[2][32], part[2][512];
 };
 
-// a row quad of an activation image <-> the tile format: lane (p, h), component j = feature 8 rq + 2 j + h of the feature tile
-__device__ __forceinline__ void tf_store(float* __restrict__ T, const long ptile, const int n_ft, const int ft, const int rq, const int lane,
-                                         const f32x4 v) {
-  float* base = T + ((ptile * n_ft + ft) * 32 + 8 * rq) * 32 + lane;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v[j], base + 64 * j);
-}
+// the tile format -> a row quad of an activation image (the reverse of tfmt_store_quad, neus_phases.h): lane (p, h), component j =
+// feature 8 rq + 2 j + h of the feature tile
 __device__ __forceinline__ f32x4 tf_load(const float* __restrict__ T, const long ptile, const int n_ft, const int ft, const int rq,
                                          const int lane) {
   const float* base = T + ((ptile * n_ft + ft) * 32 + 8 * rq) * 32 + lane;
@@ -144,7 +139,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
         v[j] = f < 3 ? sm->dout[img][p * 3 + f] : 0.f;
       }
       ldsi[(E0 + w4) * 64 + lane] = v;
-      if (live_w) tf_store(tp.DC[nC], ptile_w, 1, 0, w4, lane, v);
+      if (live_w) tfmt_store_quad(tp.DC[nC], ptile_w, 1, 0, w4, lane, v);
     }
     __syncthreads();
 
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
                        for (int j = 0; j < 4; ++j) v[j] *= act_bwd_from_out<ACT_RELU>(ca[im][rq][j]);
                        fetch_q(nxt, im, rq);
                        li[(dst + ot * 4 + rq) * 64 + lane] = v;
-                       if (2 * pair + im < n_tiles) tf_store(t_dc, 2 * pair + im, n_ot, ot, rq, lane, v);
+                       if (2 * pair + im < n_tiles) tfmt_store_quad(t_dc, 2 * pair + im, n_ot, ot, rq, lane, v);
                      });
       if (wave >= n_ot) fetch(nxt);                        // (a wave without a tile in this GEMM may own one in the next)
       __syncthreads();
@@ -226,7 +221,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
           y[j] = val;
         }
         if (r < bd.emb_rows) ldsi[(E0 + r) * 64 + lane] = y;
-        if (live_w) tf_store(tp.ED, ptile_w, bd.e_tiles, r >> 2, r & 3, lane, y);
+        if (live_w) tfmt_store_quad(tp.ED, ptile_w, bd.e_tiles, r >> 2, r & 3, lane, y);
       }
     }
     __syncthreads();
@@ -256,7 +251,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
                        li[(dst + ot * 4 + rq) * 64 + lane] = v;
                        st_stream(sv + (ot * 4 + rq) * 64 + lane, s);
                        fetch_q(nxt, im, rq);                 // (l = nL - 1: reads back the stash quad stored just above -- same wave, in order)
-                       if (2 * pair + im < n_tiles) tf_store(t_ud, 2 * pair + im, n_ot, ot, rq, lane, v);
+                       if (2 * pair + im < n_tiles) tfmt_store_quad(t_ud, 2 * pair + im, n_ot, ot, rq, lane, v);
                      });
       if (wave >= n_ot) fetch(nxt);
       __syncthreads();
@@ -306,7 +301,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
                          v[j] = acc[4 * rq + j] * act_bwd_from_out<ACT_SOFTPLUS100>(ca[im][rq][j]) + cb[im][rq][j];
                        fetch_q(nxt, im, rq);
                        li[(dst + ot * 4 + rq) * 64 + lane] = v;
-                       if (2 * pair + im < n_tiles) tf_store(t_ab, 2 * pair + im, n_ot, ot, rq, lane, v);
+                       if (2 * pair + im < n_tiles) tfmt_store_quad(t_ab, 2 * pair + im, n_ot, ot, rq, lane, v);
                      });
       if (wave >= n_ot) fetch(nxt);
       __syncthreads();

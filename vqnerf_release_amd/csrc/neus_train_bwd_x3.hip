@@ -8,6 +8,7 @@
 // Also here: vqn_pack_x3_gather, the weight pack of this kernel in one launch (gather from the flat parameter vector + the exact
 // three-way split of every gathered value into bf16 pieces, geo/packing.py: split_pack_x3).
 #include "mlp_prims_x3.h"
+#include "neus_phases.h"
 #include "vqnerf_hip.h"
 #include <stdlib.h>
 
@@ -45,32 +46,12 @@ struct SmallsB {
   int n_calls;
 };
 
-// accumulator tile <-> tile format: register i of lane (p, h) is feature (i & 3) + 8 (i >> 2) + 4 h of the feature tile
-__device__ __forceinline__ void tf_store_acc(float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, const float (&v)[16]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(v[0]), "v"(v[3]), "v"(v[7]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) __builtin_nontemporal_store(v[i], base + ((i & 3) + 8 * (i >> 2)) * 32);
-}
+// tile format -> accumulator tile (the reverse of tfmt_store_acc, neus_phases.h): register i of lane (p, h) is feature (i & 3) + 8 (i >> 2) + 4 h of the feature tile
 __device__ __forceinline__ void tf_load_acc(const float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, float (&v)[16]) {
   const float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
 #pragma unroll
   for (int i = 0; i < 16; ++i) v[i] = base[((i & 3) + 8 * (i >> 2)) * 32];
 }
-// a K step of an image: slot jj of lane (p, h) is feature 16 sl + 8 (jj >> 2) + 4 h + (jj & 3)
-__device__ __forceinline__ void tf_store_step(float* __restrict__ T, const long ptile, const int n_ft, const int sl, const int lane, const float (&x)[8]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(x[0]), "v"(x[3]), "v"(x[7]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + (sl >> 1)) * 32 + 16 * (sl & 1) + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) __builtin_nontemporal_store(x[jj], base + (8 * (jj >> 2) + (jj & 3)) * 32);
-}
-
 template <int NACC>
 __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBwdDesc bd, const f32x4* __restrict__ wx, const f32x4* __restrict__ wf,
                                                                    const TrainBwdPtrs tp, const long P, f32x4* __restrict__ scratch) {
@@ -181,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
         const int f = step_feat(w4, h, jj);
         x[jj] = f < 3 ? sm->dout[img][p * 3 + f] : 0.f;
       }
-      if (live_w) tf_store_step(tp.DC[nC], ptile_w, 1, w4, lane, x);
+      if (live_w) tfmt_store_step(tp.DC[nC], ptile_w, 1, w4, lane, x);
       if (w4 == 0) {
         f32x4 q0, q1, q2;
         split3x8(x, q0, q1, q2);
@@ -211,7 +192,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
           float v[16];
 #pragma unroll
           for (int i = 0; i < 16; ++i) v[i] = acc[i] * act_bwd_from_out<ACT_RELU>(au[im][i]);
-          if (2 * pair + im < n_tiles) tf_store_acc(t_dc, 2 * pair + im, n_ot, ot, lane, v);
+          if (2 * pair + im < n_tiles) tfmt_store_acc(t_dc, 2 * pair + im, n_ot, ot, lane, v);
           store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
         });
     }
@@ -269,7 +250,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
           }
           x[jj] = val;
         }
-        if (live_w) tf_store_step(tp.ED, ptile_w, bd.e_tiles, sl, lane, x);
+        if (live_w) tfmt_store_step(tp.ED, ptile_w, bd.e_tiles, sl, lane, x);
         if (sl < bd.emb_rows / 3) {
           f32x4 q0, q1, q2;
           split3x8(x, q0, q1, q2);
@@ -309,7 +290,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
           }
 #pragma unroll
           for (int q = 0; q < 4; ++q) st_stream(sv + (ot * 4 + q) * 64 + lane, (f32x4){s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]});
-          if (2 * pair + im < n_tiles) tf_store_acc(t_ud, 2 * pair + im, n_ot, ot, lane, v);
+          if (2 * pair + im < n_tiles) tfmt_store_acc(t_ud, 2 * pair + im, n_ot, ot, lane, v);
           store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
         });
     }
@@ -361,7 +342,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
           float v[16];
 #pragma unroll
           for (int i = 0; i < 16; ++i) v[i] = acc[i] * act_bwd_from_out<ACT_SOFTPLUS100>(au[im][i]) + ab[im][i];
-          if (2 * pair + im < n_tiles) tf_store_acc(t_ab, 2 * pair + im, n_ot, ot, lane, v);
+          if (2 * pair + im < n_tiles) tfmt_store_acc(t_ab, 2 * pair + im, n_ot, ot, lane, v);
           store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
         });
     }
