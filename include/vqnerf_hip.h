@@ -237,7 +237,10 @@ int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_sdf, const i
  * [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC] (embedding; [sdf ; features]; colour-net extras; SDF hidden
  * activations; the adjoints of the d sdf / d x sweep; colour hidden activations) with nL / nC the hidden layer counts of the
  * descriptors, n_tensors = 3 + 2 nL + nC, and e_tiles / outf_tiles / extr_tiles the feature tiles of the first three.
- * Networks of 5..8 feature tiles (the two-image kernel).  out_sdf [P], out_n [P,3], out_rgb [P,3]. */
+ * Networks of 5..8 feature tiles (the two-image kernel).  out_sdf [P], out_n [P,3], out_rgb [P,3].
+ * outf_tiles must be ceil(F / 32) for the F = 1 + features rows of OUTF (likewise GOUTF of the backward).  The entries are not given F:
+ * they refuse fewer tiles than the features' own, bound every store by outf_tiles, and zero the rows past the last feature tile; a
+ * caller that passes ceil((F - 1) / 32) where F - 1 is a multiple of 32 is not detected and loses the last feature row. */
 int vqn_neus_train_fwd(const int32_t* sdf_desc, const float* wbuf_sdf, const int32_t* col_desc, const float* wbuf_col,
                        const float* pts, const float* dirs, int64_t P, void* scratch, int64_t scratch_bytes,
                        float* const* tensors, int n_tensors, int e_tiles, int outf_tiles, int extr_tiles, float* out_sdf,

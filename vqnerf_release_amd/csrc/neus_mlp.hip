@@ -691,7 +691,8 @@ extern "C" int vqn_neus_train_fwd(const int32_t* sdf_desc, const float* wbuf_sdf
   const int nL = sd.n_lin - 1, nC = cd.n_lin - 1;
   VQN_CHECK_ARG(n_tensors == 3 + 2 * nL + nC, "tensors: [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC]");
   VQN_CHECK_SHAPE(e_tiles * 4 >= sd.emb_rows && e_tiles <= 2 && extr_tiles * 4 >= cd.extra_rows && extr_tiles <= 2 &&
-                  outf_tiles >= sd.layers[sd.n_lin - 1].n_out_tiles && 32 * outf_tiles >= 32 * sd.layers[sd.n_lin - 1].n_out_tiles + 1, "tile counts");
+                  outf_tiles >= sd.layers[sd.n_lin - 1].n_out_tiles, "tile counts");   // (outf_tiles = ceil(F / 32): with F - 1 no multiple of 32
+                  // that is the features' own tile count, and row 32 outf_tiles -- padding past the last feature -- is not stored, see the kernel)
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
   const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");

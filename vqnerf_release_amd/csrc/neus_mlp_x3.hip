@@ -489,7 +489,7 @@ extern "C" int vqn_neus_train_fwd_x3(const int32_t* sdf_desc, const float* wbuf_
   const int nL = sd.n_lin - 1, nC = cd.n_lin - 1;
   VQN_CHECK_ARG(n_tensors == 3 + 2 * nL + nC, "tensors: [E, OUTF, EXTR, U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC]");
   VQN_CHECK_SHAPE(2 * e_tiles * 3 >= sd.emb_rows && e_tiles <= 2 && 2 * extr_tiles * 3 >= cd.extra_rows && extr_tiles <= 2 &&
-                  32 * outf_tiles >= 32 * sd.layers[sd.n_lin - 1].n_out_tiles + 1, "tile counts");
+                  outf_tiles >= sd.layers[sd.n_lin - 1].n_out_tiles, "tile counts");   // (as vqn_neus_train_fwd: stores are bounded by outf_tiles)
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");

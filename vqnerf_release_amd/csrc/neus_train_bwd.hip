@@ -318,7 +318,7 @@ int load_desc(const int32_t* desc, TrainBwdDesc& bd) {
   if (bd.max_tiles < 5 || bd.max_tiles > 8 || lds_bytes_b(bd.max_tiles) > 160 * 1024) return 2;      // (<= 8: a wave owns at most one tile per GEMM)
   if (bd.emb_rows < 1 || bd.emb_rows > E_ROWS || bd.e_tiles * 4 < bd.emb_rows || bd.e_tiles > 2 || bd.emb_feats < 3 || bd.emb_feats > 8 * bd.emb_rows) return 3;
   if (bd.skip == 0 || bd.skip >= bd.nL) return 4;
-  if (bd.feat_tiles < 1 || bd.feat_tiles > bd.max_tiles || 32 * bd.outf_tiles < 32 * bd.feat_tiles + 1) return 5;
+  if (bd.feat_tiles < 1 || bd.feat_tiles > bd.max_tiles || bd.outf_tiles < bd.feat_tiles) return 5;      // (GOUTF stores are bounded by outf_tiles)
   for (int l = 0; l < bd.nL; ++l) if (bd.ts[l] < 1 || bd.ts[l] > bd.max_tiles) return 6;
   for (int l = 0; l < bd.nC; ++l) if (bd.tc[l] < 1 || bd.tc[l] > bd.max_tiles) return 7;
   if (!(bd.scale > 0.f)) return 8;

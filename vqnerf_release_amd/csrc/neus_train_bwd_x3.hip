@@ -357,7 +357,7 @@ int load_desc(const int32_t* desc, TrainBwdDesc& bd) {
   if (bd.max_tiles < 1 || bd.max_tiles > NW || lds_bytes_b(bd.max_tiles) > 160 * 1024) return 2;
   if (bd.emb_feats < 3 || bd.emb_feats > 64 || bd.emb_rows != x3_rows(bd.emb_feats) || bd.emb_rows > E_ROWS || 2 * bd.e_tiles * 3 < bd.emb_rows || bd.e_tiles > 2) return 3;
   if (bd.skip == 0 || bd.skip >= bd.nL) return 4;
-  if (bd.feat_tiles < 1 || bd.feat_tiles > bd.max_tiles || 32 * bd.outf_tiles < 32 * bd.feat_tiles + 1) return 5;
+  if (bd.feat_tiles < 1 || bd.feat_tiles > bd.max_tiles || bd.outf_tiles < bd.feat_tiles) return 5;      // (GOUTF stores are bounded by outf_tiles)
   for (int l = 0; l < bd.nL; ++l) if (bd.ts[l] < 1 || bd.ts[l] > bd.max_tiles) return 6;
   for (int l = 0; l < bd.nC; ++l) if (bd.tc[l] < 1 || bd.tc[l] > bd.max_tiles) return 7;
   if (!(bd.scale > 0.f)) return 8;
@@ -365,8 +365,12 @@ int load_desc(const int32_t* desc, TrainBwdDesc& bd) {
   return 0;
 }
 
+// accumulators per image, as in the forward (csrc/neus_mlp_x3.hip): 2 = a0 w0 apart from the five smaller terms, joined by one rounded add
+// per tile; VQN_X3_BWD_NACC=1 selects one.  With one, the small terms meet the large accumulator inside the MFMA, which loses them with a
+// one-signed error: the pass is then not odd in its adjoints, and the sums over points of a loss on the colours alone carry a bias that
+// grows with the point count (scripts/probe_neus_bwd_x3_bias.py, profiles/neus_train_bwd_x3_bias.json)
 int bwd_nacc() {
-  static const int n = [] { const char* e = getenv("VQN_X3_BWD_NACC"); return (e && e[0] == '2') ? 2 : 1; }();
+  static const int n = [] { const char* e = getenv("VQN_X3_BWD_NACC"); return (e && e[0] == '1') ? 1 : 2; }();
   return n;
 }
 

@@ -596,15 +596,16 @@ class NeusTrainEngine:
         return self.forward_mode() is not None
 
     def forward_mode(self):
-        """'f32' (vqn_neus_train_fwd) | 'x3' (vqn_neus_train_fwd_x3: the exact-split engine, layers of at most 256 outputs) | None (the
-        interpreted prog_fwd).  VQN_TRAIN_FWD = fused | x3 | prog; narrow networks always take the interpreter."""
+        """'f32' (vqn_neus_train_fwd) | 'x3' (vqn_neus_train_fwd_x3: the exact-split engine) | None (the interpreted prog_fwd).
+        VQN_TRAIN_FWD = fused | x3 | prog; networks of fewer than 5 or more than 8 feature tiles always take the interpreter."""
         want = os.environ.get('VQN_TRAIN_FWD', TRAIN_FWD_DEFAULT)
         if want not in ('fused', 'x3') or os.environ.get('VQN_NEUS_TILE32') is not None:
             return None
         mt = max(self.sdf_net.plan(max_tiles=self.col_net.max_tiles()).max_tiles, self.col_net.max_tiles())
-        if not (5 <= mt <= 9 and self.skip != 0 and self.E <= 64 and self.X <= 64):      # (embedding / extras: at most two feature tiles)
+        # 5..8 tiles: the kernels' two-image form (two activation images of 9 tiles are 166 KB of LDS: vqn_neus_train_fwd refuses them)
+        if not (5 <= mt <= 8 and self.skip != 0 and self.E <= 64 and self.X <= 64):      # (embedding / extras: at most two feature tiles)
             return None
-        return 'x3' if (want == 'x3' and mt <= 8) else 'f32'
+        return 'x3' if want == 'x3' else 'f32'
 
     def _x3_handle(self):
         if self._x3_pack is None:
@@ -895,6 +896,8 @@ class NeusCoreFunction(torch.autograd.Function):
         W, b = list(params[:nS]), list(params[nS:2 * nS])
         Wc, bc = list(params[2 * nS:2 * nS + nCc]), list(params[2 * nS + nCc:])
         P = x.shape[0]
+        # an output the loss does not touch reaches backward() as None (the kernels take a NULL adjoint), not as a tensor of zeros
+        ctx.set_materialize_grads(False)
         with torch.no_grad():
             wbuf, descs, flat = engine.pack([w.detach().float() for w in W], [t.detach().float() for t in b],
                                             [w.detach().float() for w in Wc], [t.detach().float() for t in bc], want_flat=True)
