@@ -49,7 +49,7 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
             'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
@@ -57,7 +57,9 @@ ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': (
             'vqn_mc_brick_emit': ('i', 'pplpiiifppllppppp'), 'vqn_image_metrics_scratch_bytes': ('l', 'lii'),
             'vqn_image_metrics_u8': ('i', 'ppplfliiipplpp'), 'vqn_image_metrics_f32': ('i', 'ppplfliiipplpp'),
             'vqn_seg_scratch_bytes': ('l', 'lii'), 'vqn_seg_contingency_rgb': ('i', 'pppflpipiplpp'),
-            'vqn_seg_contingency_labels': ('i', 'pppliiplpp')}
+            'vqn_seg_contingency_labels': ('i', 'pppliiplpp'), 'vqn_meanshift_seek': ('i', 'plplidipppp'),
+            'vqn_meanshift_merge_scratch_bytes': ('l', 'li'), 'vqn_meanshift_merge': ('i', 'pplidplppp'),
+            'vqn_meanshift_assign': ('i', 'plpiidppp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -849,6 +851,63 @@ def segmentation_counts(gt, pd, sel=None, alpha_thres=0.0, gt_palette=None, pd_p
     else:
         _call('vqn_seg_contingency_labels', _ptr(gt), _ptr(pd), _ptr(sel), n, n_gt, n_pd, _ptr(buf), buf.numel(), _ptr(out))
     return out
+
+
+# --------------------------------------------------------------------------------------
+# mean-shift clustering (csrc/meanshift.hip; decomp/nerfactor/util/meanshift.py)
+MEANSHIFT_MAX_DIM = 8              # features per point at most (kMaxD)
+MEANSHIFT_POINTS_PER_TILE = 256    # points the seek kernel stages in LDS per pass (kSeekTile)
+MEANSHIFT_SEEDS_PER_GROUP = 64     # seeds a seek workgroup owns (kSeekSeeds)
+MEANSHIFT_ASSIGN_SPAN = 256        # points an assign workgroup labels per pass (kAssignThreads)
+MEANSHIFT_ASSIGN_CENTRES = 512     # centres the assign kernel holds in LDS at a time (kAssignCentres)
+
+
+def _f64_rows(t, name, D=None):
+    if t.dtype != torch.float64 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda or (D is not None and t.shape[1] != D):
+        raise VqnError(f'{name}: expected a contiguous float64 device tensor [rows, {"D" if D is None else D}], got {t.dtype} '
+                       f'{tuple(t.shape)} contiguous={t.is_contiguous()} device={t.device}')
+    return t
+
+
+def meanshift_seek(points, seeds, bandwidth, max_iter):
+    """points [n, D], seeds [S, D] float64 -> (means float64 [S, D], counts int32 [S] (0: dropped), iters int32 [S]): every seed to
+    convergence in one launch, no host read (vqn_meanshift_seek)."""
+    _f64_rows(points, 'points')
+    n, D = (int(s) for s in points.shape)
+    _f64_rows(seeds, 'seeds', D)
+    S = int(seeds.shape[0])
+    means = torch.empty((S, D), dtype=torch.float64, device=points.device)
+    counts = torch.empty((S,), dtype=torch.int32, device=points.device)
+    iters = torch.empty((S,), dtype=torch.int32, device=points.device)
+    _call('vqn_meanshift_seek', _ptr(points), n, _ptr(seeds), S, D, float(bandwidth), int(max_iter), _ptr(means), _ptr(counts), _ptr(iters))
+    return means, counts, iters
+
+
+def meanshift_merge(candidates, counts, bandwidth):
+    """candidates float64 [M, D] with their int32 counts [M], sorted descending by (count, coordinates) -> (kept uint8 [M],
+    n_kept int32 [1]), one launch, no host read (vqn_meanshift_merge)."""
+    _f64_rows(candidates, 'candidates')
+    M, D = (int(s) for s in candidates.shape)
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (M,) or not counts.is_contiguous() or counts.device != candidates.device:
+        raise VqnError(f'meanshift_merge: counts must be a contiguous int32 [{M}] on the device of the candidates')
+    kept = torch.empty((M,), dtype=torch.uint8, device=candidates.device)
+    n_kept = torch.empty((1,), dtype=torch.int32, device=candidates.device)
+    need = lib().vqn_meanshift_merge_scratch_bytes(M, D)
+    buf = _scratch('meanshift_merge', max(need, 64), candidates.device)      # (need = 0: a shape the call itself refuses, with the reason)
+    _call('vqn_meanshift_merge', _ptr(candidates), _ptr(counts), M, D, float(bandwidth), _ptr(buf), buf.numel(), _ptr(kept), _ptr(n_kept))
+    return kept, n_kept
+
+
+def meanshift_assign(points, centres, bandwidth=0.0, want_dist=False):
+    """points [n, D], centres [K, D] float64 -> (labels int32 [n], dist float64 [n] | None): the nearest centre, ties to the lowest
+    index; bandwidth > 0: -1 where the distance is larger (vqn_meanshift_assign)."""
+    _f64_rows(points, 'points')
+    n, D = (int(s) for s in points.shape)
+    _f64_rows(centres, 'centres', D)
+    labels = torch.empty((n,), dtype=torch.int32, device=points.device)
+    dist = torch.empty((n,), dtype=torch.float64, device=points.device) if want_dist else None
+    _call('vqn_meanshift_assign', _ptr(points), n, _ptr(centres), int(centres.shape[0]), D, float(bandwidth), _ptr(labels), _ptr(dist))
+    return labels, dist
 
 
 # --------------------------------------------------------------------------------------

@@ -21,8 +21,8 @@ I;16) on both sides are read as labels 0 .. 64 directly; a label out of range ra
 `cv2.imwrite`, which reads it as B, G, R, and the writer here reproduces those files.  The 18 colours the writer uses are closed under that swap, so
 this permutes the predicted labels and changes no score (every score is invariant under a relabelling of the prediction).
 
-Not rebuilt: the mean-shift clustering itself (`meanshift.py`), and the averaging over the paper's five named scenes: a caller
-loops `evaluate`."""
+The mean-shift baseline's files are written by decomp/meanshift.py (`run`: the clustering on the device, labels.png per view).  Not
+rebuilt: the averaging over the paper's five named scenes: a caller loops `evaluate`."""
 import json
 import os
 import re
