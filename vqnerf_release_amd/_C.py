@@ -49,7 +49,7 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift, the material edit), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
             'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
@@ -59,7 +59,7 @@ ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': (
             'vqn_seg_scratch_bytes': ('l', 'lii'), 'vqn_seg_contingency_rgb': ('i', 'pppflpipiplpp'),
             'vqn_seg_contingency_labels': ('i', 'pppliiplpp'), 'vqn_meanshift_seek': ('i', 'plplidipppp'),
             'vqn_meanshift_merge_scratch_bytes': ('l', 'li'), 'vqn_meanshift_merge': ('i', 'pplidplppp'),
-            'vqn_meanshift_assign': ('i', 'plpiidppp')}
+            'vqn_meanshift_assign': ('i', 'plpiidppp'), 'vqn_material_select_edit': ('i', 'pppiplppipipfppppppppppppp')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -851,6 +851,110 @@ def segmentation_counts(gt, pd, sel=None, alpha_thres=0.0, gt_palette=None, pd_p
     else:
         _call('vqn_seg_contingency_labels', _ptr(gt), _ptr(pd), _ptr(sel), n, n_gt, n_pd, _ptr(buf), buf.numel(), _ptr(out))
     return out
+
+
+# --------------------------------------------------------------------------------------
+# material selection and editing (csrc/material_edit.hip; decomp/nerfactor/util/material_edit.py)
+MATEDIT_ROWS_PER_PASS = 1024   # rows a workgroup takes per pass (kPass of the kernel)
+MATEDIT_GRID_CAP = 1024        # workgroups at most (kGridCap)
+MATEDIT_MAX_PLANES = 8         # property planes at most, of 1 .. 3 channels each
+MATEDIT_MAX_TERMS = 32         # terms of a program at most
+MATEDIT_MAX_CONDS = 8          # conditions of a program at most
+MATEDIT_HEAD_WORDS = 3         # words of the counts row ahead of the 65 per-code counts: selected, rows, invalid
+MATEDIT_CODES = 65             # code labels 0 .. 64
+
+
+def _overlap(a, b):
+    """do the bytes of two tensors overlap (views of one storage that do not touch are fine)"""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def material_select_edit(n, planes=(), embed=None, mask_in=None, terms=(), ops=(), n_conds=0, codes=None, eps=5e-6, edit=None, dst=None,
+                         opt_scale=None, out=None, want_mask=True, device=None):
+    """Selection, material edit, opt_scale scaling and counts of n rows in ONE launch (include/vqn_neus_fold.h), no host read.
+    planes: up to 8 float32 [n, ch] (ch <= 3) contiguous device tensors or None; embed: int32 [n] or float32 [n] or None; mask_in:
+    uint8 [n] or None.  terms: rows (plane, channel, denominator channel or -1, lo, hi, condition id); ops: 0 'and' / 1 'or', one
+    fewer than n_conds; codes: the labels of the set (each in 0 .. 64) or None.  edit = (albedo [n, 3], spec [n, 3], rough [n, 1])
+    with dst = 7 floats diff[3], spec[3], rough[1] and opt_scale = 3 floats or None; `out`: the output tensors to write (default:
+    new ones), in the order of the result.
+    -> (mask uint8 [n] or None, counts int64 [68] = selected, n, invalid, per code [65], edited: None or (albedo', spec', rough') or
+    (albedo', spec', rough', albedo' * opt_scale, spec' * opt_scale)).
+    Inputs need not be 16-byte aligned (the kernel then goes row by row) but must be contiguous; outputs may not overlap inputs."""
+    n = int(n)
+    planes = list(planes) + [None] * (MATEDIT_MAX_PLANES - len(planes))
+    if len(planes) > MATEDIT_MAX_PLANES:
+        raise VqnError(f'material_select_edit: at most {MATEDIT_MAX_PLANES} planes, got {len(planes)}')
+    given = [t for t in planes if t is not None] + [t for t in (embed, mask_in) if t is not None] + list(edit or ())
+    dev = given[0].device if given else torch.device(device or 'cuda')
+    plane_ch = np.zeros(MATEDIT_MAX_PLANES, np.int32)
+    for p, t in enumerate(planes):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != n or not t.is_cuda or not t.is_contiguous() or t.device != dev:
+            raise VqnError(f'material_select_edit: plane {p}: expected a contiguous float32 [{n}, ch] tensor on {dev}, got {t.dtype} '
+                           f'{tuple(t.shape)} contiguous={t.is_contiguous()} on {t.device}')
+        plane_ch[p] = t.shape[1]
+    if embed is not None and (embed.dtype not in (torch.int32, torch.float32) or tuple(embed.shape) != (n,) or embed.device != dev
+                              or not embed.is_contiguous()):
+        raise VqnError(f'material_select_edit: embed: expected a contiguous int32 or float32 [{n}] tensor on {dev}, got {embed.dtype} '
+                       f'{tuple(embed.shape)} on {embed.device}')
+    if mask_in is not None and (mask_in.dtype != torch.uint8 or tuple(mask_in.shape) != (n,) or mask_in.device != dev or not mask_in.is_contiguous()):
+        raise VqnError(f'material_select_edit: mask_in: expected a contiguous uint8 [{n}] tensor on {dev}, got {mask_in.dtype} '
+                       f'{tuple(mask_in.shape)} on {mask_in.device}')
+    shapes = [(n, 3), (n, 3), (n, 1)]
+    if edit is not None:
+        if dst is None or len(edit) != 3:
+            raise VqnError('material_select_edit: an edit needs (albedo, spec, rough) and dst')
+        for t, shp in zip(edit, shapes):
+            if t.dtype != torch.float32 or tuple(t.shape) != shp or t.device != dev or not t.is_contiguous():
+                raise VqnError(f'material_select_edit: edit inputs are contiguous float32 [n, 3], [n, 3], [n, 1] on {dev}, got {t.dtype} '
+                               f'{tuple(t.shape)} on {t.device}')
+        if opt_scale is not None:
+            shapes = shapes + [(n, 3), (n, 3)]
+    outs = []
+    if edit is not None:
+        outs = list(out) if out is not None else [torch.empty(shp, dtype=torch.float32, device=dev) for shp in shapes]
+        if len(outs) != len(shapes) or any(o.dtype != torch.float32 or tuple(o.shape) != shp or o.device != dev or not o.is_contiguous()
+                                           for o, shp in zip(outs, shapes)):
+            raise VqnError(f'material_select_edit: outputs are contiguous float32 tensors of shapes {shapes} on {dev}')
+    mask_out = torch.empty((n,), dtype=torch.uint8, device=dev) if want_mask else None
+    written = outs + ([mask_out] if mask_out is not None else [])
+    for i, o in enumerate(written):
+        if any(_overlap(o, t) for t in given) or any(_overlap(o, w) for w in written[:i]):
+            raise VqnError('material_select_edit: an output aliases an input (or another output); the selection reads the pre-edit values')
+    terms = list(terms)
+    ti = np.ascontiguousarray([[t[0], t[1], t[2], t[5]] for t in terms], dtype=np.int32).reshape(-1, 4)
+    tf = np.ascontiguousarray([[t[3], t[4]] for t in terms], dtype=np.float32).reshape(-1, 2)
+    ops_h = np.ascontiguousarray(list(ops), dtype=np.int32)
+    if len(ops_h) != max(int(n_conds) - 1, 0):
+        raise VqnError(f'material_select_edit: {n_conds} conditions take {max(int(n_conds) - 1, 0)} ops, got {len(ops_h)}')
+    codes_h = None
+    if codes is not None:
+        codes_h = np.zeros(MATEDIT_CODES, np.uint8)
+        for c in codes:
+            if not 0 <= int(c) < MATEDIT_CODES:
+                raise VqnError(f'material_select_edit: code labels are 0 .. {MATEDIT_CODES - 1}, got {c}')
+            codes_h[int(c)] = 1
+    dst_h = None if dst is None else np.ascontiguousarray(dst, dtype=np.float32).reshape(-1)
+    if dst_h is not None and dst_h.size != 7:
+        raise VqnError(f'material_select_edit: dst is 7 floats diff[3], spec[3], rough[1], got {dst_h.size}')
+    scale_h = None if opt_scale is None else np.ascontiguousarray(
+        opt_scale.detach().cpu().numpy() if torch.is_tensor(opt_scale) else opt_scale, dtype=np.float32).reshape(-1)
+    if scale_h is not None and scale_h.size != 3:
+        raise VqnError(f'material_select_edit: opt_scale is 3 floats, got {scale_h.size}')
+    nul = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    e = list(edit) if edit is not None else [None] * 3
+    o = outs + [None] * (5 - len(outs))
+    if n == 0 and len(terms) <= MATEDIT_MAX_TERMS and int(n_conds) <= MATEDIT_MAX_CONDS:
+        # nothing to launch: the counts of no rows (the refusals below still come from the library when a limit is exceeded)
+        return mask_out, torch.zeros((MATEDIT_HEAD_WORDS + MATEDIT_CODES,), dtype=torch.int64, device=dev), (tuple(outs) if edit is not None else None)
+    counts = torch.empty((MATEDIT_HEAD_WORDS + MATEDIT_CODES,), dtype=torch.int64, device=dev)
+    _call('vqn_material_select_edit', _ptrs(planes, MATEDIT_MAX_PLANES), plane_ch.ctypes.data, _ptr(embed),
+          int(embed is not None and embed.dtype == torch.float32), _ptr(mask_in), n, nul(ti), nul(tf), len(terms), nul(ops_h), int(n_conds),
+          nul(codes_h), float(eps), _ptr(e[0]), _ptr(e[1]), _ptr(e[2]), nul(dst_h), nul(scale_h), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]),
+          _ptr(o[4]), _ptr(mask_out), _ptr(counts))
+    return mask_out, counts, (tuple(outs) if edit is not None else None)
 
 
 # --------------------------------------------------------------------------------------

@@ -1,0 +1,208 @@
+"""Material editing over the views of a scene: select a material by its VQ code (optionally narrowed by bounds on other per-pixel
+properties), replace it, and re-render every view under the original or a new light -- the loop of the reference's
+decomp/nerfvq_nfr3/nerfactor/offline_edit.py:183-205 (with edit.py:213-230 for a new light) with the selection made on the device
+(decomp/nerfactor/util/material_edit.py) where the reference reads masks a PyQt window wrote (ui4_offline.py `map_f`).
+
+  run                 per view: vq_model.fast_render(edit_select=...) makes the mask and the edited stage-2 render in one pass; the same
+                      mask goes to the stage-3 model; both write into outroot/<name>/ through the asynchronous vis_batch; the mask is
+                      also written as the UI writes it (outroot/auto_sel/<name>.npy, bool [H, W, 3], and auto_sel/dst.json), so that
+                      the reference's own scripts could consume it;
+  select_views        the file form of `map_f`: the same selection from the files of rendered views, evaluated on the device;
+  compute_rgb_scales  offline_edit.py:52-120: the per-channel scale that matches predicted albedo (+ spec) to the ground truth.
+
+One deviation from the reference: its `mat` property reads the SOURCE view's files for every view (ui4_offline.py:295-297), a slip;
+here every view tests its own values.  Not here: the polling server around edit.py's loop (status.json), the PyQt window, its preset
+table of named materials, and cv2 resizing of masks (a size mismatch raises)."""
+import json
+import os
+import re
+
+import numpy as np
+import torch
+
+from vqnerf_release_amd import parallel
+from vqnerf_release_amd.decomp.nerfactor.util import img as imgutil
+from vqnerf_release_amd.decomp.nerfactor.util import material_edit, vis
+from vqnerf_release_amd.decomp.nerfactor.util.segmentation import _UNIT8
+
+_FILES = {'rgb': 'pred_rgb.png', 'diff': 'pred_albedo.png', 'spec': 'pred_spec.png', 'rough': 'pred_rough.png'}       # ui4_offline.py:28-31
+
+
+def _dst(dst):
+    return {k: [float(x) for x in np.asarray(dst[k], np.float64).reshape(-1)] for k in ('diff', 'spec', 'rough')}
+
+
+def _write_dst(sel_dir, dst):
+    os.makedirs(sel_dir, exist_ok=True)
+    with open(os.path.join(sel_dir, 'dst.json'), 'w') as f:
+        json.dump(_dst(dst), f)
+
+
+def _save_selection(host, event, hw, path):
+    if event is not None:
+        event.synchronize()
+    m = host['mask'].numpy().reshape(hw) != 0
+    np.save(path, np.repeat(m[..., None], 3, axis=-1))               # ui4_offline.py:333-334
+
+
+def _hw(to_vis):
+    hw = to_vis['hw']
+    return tuple(int(x) for x in (hw[0] if hw.ndim == 2 else hw).tolist())
+
+
+@torch.no_grad()
+def run(vq_model, dataset, outroot, selection, dst, ref_model=None, ref_dataset=None, opt_scale=None, relight_probes=True, dst_env=None,
+        name_fmt='batch{i:09d}', writer=None, num_p=None, p_i=None):
+    """Every view of `dataset` (sharded as in train_nfr.render_views: process p_i of num_p takes views p_i, p_i + num_p, ...):
+    vq_model.fast_render(edit_select=selection, edit_material=dst, opt_scale, relight_probes | dst_env) -> the mask and the edited
+    stage-2 render; with ref_model (and ref_dataset, the same views with the stage-3 inputs; not under dst_env, as in edit.py:225-230)
+    ref_model.fast_render(edit_rows=that mask, opt_scale).  Files: outroot/<name>/ by vis_batch (pred_edit_mask.png and embed_map.png
+    among them; the two models write the files both know with the same content), outroot/auto_sel/<name>.npy and auto_sel/dst.json.  If a condition
+    names rgb, a plain render of the view comes first (the stage-3 model's if given, else the stage-2 model's `call`) and feeds it.
+    -> (writer, {name: selected pixels}), the counts read from the device once, at the end."""
+    if not isinstance(selection, material_edit.Selection):
+        raise ValueError(f'selection is a material_edit.Selection, got {type(selection).__name__}')
+    if (ref_model is None) != (ref_dataset is None):
+        raise ValueError('ref_model and ref_dataset are given together')
+    if num_p is None:
+        num_p, p_i = parallel.world_size(), parallel.rank()
+    writer = writer or vis.default_writer()
+    files = sorted(dataset.files)
+    ref_files = sorted(ref_dataset.files) if ref_dataset is not None else None
+    if ref_files is not None and len(ref_files) != len(files):
+        raise ValueError(f'the two datasets differ in their views: {len(files)} and {len(ref_files)}')
+    sel_dir = os.path.join(outroot, 'auto_sel')
+    if p_i == 0:
+        _write_dst(sel_dir, dst)
+    os.makedirs(sel_dir, exist_ok=True)
+    needs_rgb = 'rgb' in selection.needs()
+    names, counts = [], []
+    for i, f in enumerate(files):
+        if i % num_p != p_i:
+            continue
+        name = name_fmt.format(i=i)
+        batch = dataset.view(f)
+        ref_batch = ref_dataset.view(ref_files[i]) if ref_dataset is not None else None
+        props = None
+        if needs_rgb:
+            plain = ref_model.fast_render(ref_batch, mode='test')[0] if ref_model is not None else vq_model.call(batch, mode='test')[0]
+            props = {'rgb': plain['rgb']}
+        pred, _, _, to_vis = vq_model.fast_render(batch, mode='test', opt_scale=opt_scale, relight_probes=relight_probes and dst_env is None,
+                                                  dst_env=dst_env, ref_batch=True, gen_embed=True, edit_material=dst, edit_select=selection,
+                                                  edit_props=props)
+        picked = pred['edit_mask']
+        outdir = os.path.join(outroot, name)
+        if ref_model is not None and dst_env is None:
+            rows = (picked[:, 0] != 0).to(torch.uint8)
+            _, _, _, ref_vis = ref_model.fast_render(ref_batch, mode='test', opt_scale=opt_scale, edit_material=dst, edit_rows=rows)
+            ref_model.vis_batch(ref_vis, outdir, mode='test', writer=writer)
+        vq_model.vis_batch(to_vis, outdir, mode='test', writer=writer)
+        host, ev = writer.fetch({'mask': picked})
+        writer.submit(_save_selection, host, ev, _hw(to_vis), os.path.join(sel_dir, name + '.npy'))
+        names.append(name)
+        counts.append(picked.sum())
+    totals = torch.stack(counts).tolist() if counts else []
+    return writer, {n: int(c) for n, c in zip(names, totals)}
+
+
+# ---- the file form -------------------------------------------------------------------------------------------------------------
+def _load(path, mode):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert(mode))
+
+
+def _view_dirs(pred_root):
+    return [d for d in sorted(os.listdir(pred_root))
+            if (d.startswith('batch') or d.startswith('test')) and os.path.isdir(os.path.join(pred_root, d))]       # ui4_offline.py:288
+
+
+def _embed_labels(rgb, device):
+    """embed_map.png (uint8 [H, W, 3], RGB) -> int32 labels [H * W]: 1 + the row of vis._EMBED_COLOURS the pixel equals, 0 for none"""
+    px = torch.as_tensor(rgb, device=device).reshape(-1, 3).to(torch.int32)
+    pal = torch.as_tensor(vis._EMBED_COLOURS[:, ::-1].copy(), device=device).to(torch.int32)         # (the table is B, G, R)
+    hit = (px[:, None, :] == pal[None]).all(-1)
+    return torch.where(hit.any(1), hit.to(torch.int32).argmax(1).to(torch.int32) + 1, torch.zeros((), dtype=torch.int32, device=device))
+
+
+def view_props(view_dir, selection, device='cuda'):
+    """the files of one rendered view the selection names -> ({prop: float32 [H * W, ch]}, int32 labels or None, (H, W)); bytes become
+    floats through the / 255 host table of util/segmentation.py (correctly rounded, where a device division may not be)"""
+    unit = torch.as_tensor(_UNIT8, device=device)
+    props, shapes = {}, {}
+    for p in selection.needs():
+        if p == 'xyz':
+            path = os.path.join(view_dir, 'xyz.npy')
+            path = path if os.path.exists(path) else os.path.join(view_dir, 'pred_xyz.npy')                  # ui4_offline.py:305-306
+            a = np.load(path).astype(np.float32)
+            shapes[path], props[p] = a.shape[:2], torch.as_tensor(a, device=device).reshape(-1, 3)
+        else:
+            path = os.path.join(view_dir, _FILES[p])
+            a = _load(path, 'L' if p == 'rough' else 'RGB')
+            shapes[path] = a.shape[:2]
+            props[p] = unit[torch.as_tensor(a, device=device).long()].reshape(-1, 1 if p == 'rough' else 3)
+    labels = None
+    if selection.codes is not None:
+        path = os.path.join(view_dir, 'embed_map.png')
+        a = _load(path, 'RGB')
+        shapes[path], labels = a.shape[:2], _embed_labels(a, device)
+    if len(set(shapes.values())) != 1:
+        raise ValueError(f'{view_dir}: the files of the view differ in size: {shapes}')
+    return props, labels, next(iter(shapes.values()))
+
+
+def select_views(pred_root, selection, dst=None, src_view=None, device='cuda'):
+    """The file form of `map_f`: for every view directory of pred_root (`batch*` / `test*`) the selection from embed_map.png,
+    pred_rgb.png, pred_albedo.png, pred_spec.png, pred_rough.png and xyz.npy (else pred_xyz.npy) -- only the ones the selection names
+    -- evaluated on the device.  Writes pred_root/../auto_sel/<basename of pred_root>/<view>.npy (bool [H, W, 3]), dst.json there when
+    dst is given, and edit_mask.png of `src_view` (a view's name), as the UI does (ui4_offline.py:267-271, :333-338).
+    -> {view: selected pixels}, read from the device once, at the end."""
+    if not isinstance(selection, material_edit.Selection):
+        raise ValueError(f'selection is a material_edit.Selection, got {type(selection).__name__}')
+    pred_root = pred_root.rstrip('/')
+    sel_dir = os.path.join(os.path.dirname(pred_root), 'auto_sel', os.path.basename(pred_root))
+    os.makedirs(sel_dir, exist_ok=True)
+    if dst is not None:
+        _write_dst(sel_dir, dst)
+    views, counts = _view_dirs(pred_root), []
+    if src_view is not None and src_view not in views:
+        raise ValueError(f'src_view {src_view!r} is not a view of {pred_root}')
+    for v in views:
+        props, labels, hw = view_props(os.path.join(pred_root, v), selection, device)
+        res = material_edit.select(props, selection, embed=labels)
+        m = np.repeat((res['mask'].cpu().numpy().reshape(hw) != 0)[..., None], 3, axis=-1)
+        np.save(os.path.join(sel_dir, v + '.npy'), m)
+        if v == src_view:
+            vis.write_png(os.path.join(sel_dir, 'edit_mask.png'), (np.where(m, 1.0, 0.0) * 255).astype(np.uint8))
+        counts.append(res['selected'])
+    totals = torch.stack(counts).tolist() if counts else []
+    return {v: int(c) for v, c in zip(views, totals)}
+
+
+def compute_rgb_scales(pred_root, gt_root, vis_root, with_spec=False, device='cuda'):
+    """offline_edit.py:52-120.  Per view directory batch<i> of pred_root: prediction = pred_albedo.png + pred_spec.png, ground truth =
+    vis_root/val_<i:03d>/albedo.png (+ metal.png when with_spec: the reference's list of scenes is the caller's business), alpha =
+    gt_root/val_<i:03d>/rgba.png; both sides through linear2srgb; the per-channel ratio of the alpha-weighted means, ground truth over
+    prediction, per view; then the mean over views.  float64 on the device -> float64 [3] (device).  The reference resizes the ground
+    truth to the prediction; here a size mismatch raises, as in metric_eval."""
+    dev = torch.device(device)
+    load = lambda path, mode='RGB': torch.as_tensor(_load(path, mode), device=dev).to(torch.float64) / 255.0
+    ratios = []
+    for name in sorted(os.listdir(pred_root)):
+        if not re.fullmatch(r'batch\d+', name) or not os.path.isdir(os.path.join(pred_root, name)):
+            continue
+        view = 'val_{i:03d}'.format(i=int(name[len('batch'):]))
+        pred = load(os.path.join(pred_root, name, 'pred_albedo.png')) + load(os.path.join(pred_root, name, 'pred_spec.png'))
+        gt = load(os.path.join(vis_root, view, 'albedo.png'))
+        if with_spec:
+            gt = gt + load(os.path.join(vis_root, view, 'metal.png'))
+        alpha = load(os.path.join(gt_root, view, 'rgba.png'), 'RGBA')[..., 3]
+        if pred.shape != gt.shape or pred.shape[:2] != alpha.shape:
+            raise ValueError(f'{name}: image sizes differ: prediction {tuple(pred.shape)}, ground truth {tuple(gt.shape)}, alpha '
+                             f'{tuple(alpha.shape)} (resizing is not implemented)')
+        gt, pred = imgutil.linear2srgb(gt), imgutil.linear2srgb(pred)
+        a = alpha[..., None]
+        ratios.append(((gt * a).sum((0, 1)) / a.sum()) / ((pred * a).sum((0, 1)) / a.sum()))
+    if not ratios:
+        raise ValueError(f'{pred_root}: no view directory batch<i>')
+    return torch.stack(ratios).mean(0)

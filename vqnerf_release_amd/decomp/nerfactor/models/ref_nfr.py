@@ -11,7 +11,7 @@ from vqnerf_release_amd.decomp import packing
 from vqnerf_release_amd import _C
 from vqnerf_release_amd.decomp.nerfactor.models.nfr_unit import BrdfModel, fg_rows, scatter_rows, take_rows
 from vqnerf_release_amd.decomp.nerfactor.networks import mlp
-from vqnerf_release_amd.decomp.nerfactor.util import img as imgutil
+from vqnerf_release_amd.decomp.nerfactor.util import img as imgutil, material_edit
 
 
 class Model(BrdfModel):
@@ -164,11 +164,14 @@ class Model(BrdfModel):
         return pred, gt, loss_kwargs, to_vis
 
     def fast_render(self, batch, mode='train', relight_olat=False, relight_probes=False, opt_scale=None, edit_mask=None,
-                    edit_material=None):
+                    edit_material=None, edit_rows=None):
         """ref_nfr.py:303-418 (the `pd_test` / `pd_vq` passes of test.py:216-300): `rgb` from the UNscaled materials under the
         model light, the probe renders from the materials scaled by `opt_scale` -- one shading pass: when both are asked for,
-        the scaled set rides as material set 0 (the one the kernel relights) and the unscaled one as set 1."""
+        the scaled set rides as material set 0 (the one the kernel relights) and the unscaled one as set 1.
+        edit_rows: a uint8 [n] device mask over all rows (the one vq_nfr's fast_render(edit_select=...) returns), applied as edit_mask
+        is, in one launch of csrc/material_edit.hip together with the opt_scale scaling."""
         self._validate_mode(mode)
+        kernel_edit = material_edit.check_edit_keywords(edit_mask, edit_material, None, edit_rows, None)
         id_, hw, rayo, rayd, rgb, alpha, pred_alpha, xyz, normal, ref = batch[:10]
         lvis = batch[10] if self.data_type == 'nerf' else None
         mask = fg_rows(alpha)
@@ -192,9 +195,12 @@ class Model(BrdfModel):
             if not edit_material['rough'][0] < 0:
                 rough = upd(rough, edit_material['rough'])
         maps = list(self.novel_probes.values()) if relight_probes else []
+        if kernel_edit:
+            _, albedo, spec, rough, s_albedo, s_spec = material_edit.edit_rows_of_a_view(
+                mask, albedo, spec, rough, None, None, edit_material, None, edit_rows, None, opt_scale if (opt_scale is not None and maps) else None)
         sets = [(albedo, spec, rough)]
         if opt_scale is not None and maps:
-            sets = [(albedo * opt_scale, spec * opt_scale, rough), (albedo, spec, rough)]
+            sets = [(s_albedo, s_spec, rough) if kernel_edit else (albedo * opt_scale, spec * opt_scale, rough), (albedo, spec, rough)]
         if self._fused(xyz_m, albedo, spec, rough):
             pr = torch.stack([torch.as_tensor(lp, dtype=torch.float32, device=xyz_m.device).reshape(-1, 3) for lp in maps], 0) if maps else None
             sh = self._shade(xyz_m, normal_m, rayo, lvis_m, sets, probes=pr)

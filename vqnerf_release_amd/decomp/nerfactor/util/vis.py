@@ -4,8 +4,8 @@ device-resident result dicts with an asynchronous writer.
 
 Same files per view directory as the reference: `<key>.png` for every image-like entry (rgb / diff / normal composited over
 the white or black background with the thresholded ground-truth alpha; albedo / spec / rough / ks / basecolor as they are,
-plus `<key>.npy`), `<key>_<probe>.png` per relighting probe, `embed_map.png`, `<key>.npy` for xyz (and z / embed under
-`full_vis_path`), `metadata.json` (`id`, and `psnr` of the written 8-bit gt_rgb / pred_rgb when ground truth exists); once per
+plus `<key>.npy`), `<key>_<probe>.png` per relighting probe, `embed_map.png`, `pred_edit_mask.png` (an edit's selection),
+`<key>.npy` for xyz (and z / embed under `full_vis_path`), `metadata.json` (`id`, and `psnr` of the written 8-bit gt_rgb / pred_rgb when ground truth exists); once per
 run `pred_light.png`, `np_light.npy` (and `vq_embed.npy` under `full_vis_path`).
 
 What is different on purpose: nothing is written on the calling thread.  The tensors of a view leave the device through
@@ -133,6 +133,8 @@ def _shape_views(host, hw):
             a = a.reshape(hw)
         elif k.endswith(('z',)):
             a = a.reshape(hw + (a.shape[1],))
+        elif k.endswith('edit_mask'):                                # the selection of fast_render(edit_select=...), 0 / 1
+            a = a.reshape(hw)
         else:
             raise NotImplementedError(k)
         out[k] = a
@@ -180,6 +182,8 @@ def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_
             jobs.append(pool_submit(np.save, os.path.join(outdir, k + '.npy'), v))
         elif k.endswith('normal'):
             png(k, over_bg((v + 1.0) / 2.0))
+        elif k.endswith('edit_mask'):
+            png(k, v)
         elif k.endswith(('z',)):
             pass                                                 # latent codes are only dumped under full_vis
         elif mode != 'render' and not simp:
