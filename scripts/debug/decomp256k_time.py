@@ -1,4 +1,4 @@
-import os, sys, time
+import sys, time
 sys.path.insert(0, '.')
 import numpy as np, torch, bench
 from vqnerf_release_amd.decomp.nerfactor import train_nfr
@@ -21,7 +21,7 @@ for _ in range(2): tr.train_iter(batch, global_bs=n)
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(5): tr.train_iter(batch, global_bs=n)
 torch.cuda.synchronize()
-print(f'VQN_WGRAD_X3_SMALL_TILES={os.environ.get("VQN_WGRAD_X3_SMALL_TILES", "-")} n={n}: {(time.perf_counter()-t0)/5*1e3:.2f} ms/step')
+print(f'n={n}: {(time.perf_counter()-t0)/5*1e3:.2f} ms/step')
 from vqnerf_release_amd import _C
 from vqnerf_release_amd.geo import train_programs as tp
 for batched in (False, True):

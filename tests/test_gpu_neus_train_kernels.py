@@ -241,3 +241,54 @@ def test_training_kernels_read_nothing_they_did_not_write(shape, engine, monkeyp
             assert bool(torch.isfinite(t).all()), f'{shape}/{engine}/P{P}: {k} is not finite over NaN-filled tensors'
         diff = [k for k in runs['nan'] if not torch.equal(_bits(runs['nan'][k]), _bits(runs['zeros'][k]))]
         assert not diff, f'{shape}/{engine}/P{P}: {diff} depend on what the tensors held before'
+
+
+@pytest.mark.parametrize('engine', ['x3', 'fused'])
+def test_backward_is_the_same_under_one_workgroup_of_scratch(engine, monkeypatch):
+    """The backward's grid is sized by its scratch (csrc/neus_launch.h: pair_grid over train_bwd_stash_bytes).  w160 at 161 points is
+    three tile pairs: with the scratch the query asks for, three workgroups take one pair each; with exactly one workgroup's -- a fresh
+    buffer of that size, handed to the entry in place of the wrapper's cached one -- a single workgroup walks all three.  Every tensor
+    the backward writes, and every gradient behind them, has the same bits both ways."""
+    from vqnerf_release_amd import _C
+    shape, P = 'w160', 161
+    nc.select(monkeypatch, engine)
+    eng, _ = _engine(shape)
+    mode = eng.backward_mode()
+    assert mode == nc.MODES[engine][1] and (P + 31) // 32 == 6
+    meth, query = {'x3': ('run_fused_backward_x3', 'vqn_neus_train_bwd_x3_scratch_bytes'),
+                   'f32': ('run_fused_backward', 'vqn_neus_train_bwd_scratch_bytes')}[mode]
+    ref = nc.reference(shape, P)
+    x, dirs = ref['x'].cuda(), ref['dirs'].cuda()
+    adj = tuple(ref[k].cuda() for k in ('g_rgb', 'g_n', 'g_sdf'))
+    desc = eng._bwd_static(x.device, mode)[-1]
+    per_wg = 2 * (int(desc[0]) + 1) * 4 * int(desc[6]) * 1024           # two images of S_0..S_{nL-1} and g_feat, 4 max_tiles KB each
+    cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+    assert _C._scratch_bytes(query, _C._host(desc)) == cus * per_wg and cus >= 3
+
+    written, sizes = [], []
+    orig = getattr(eng, meth)
+
+    def spy(flat, T, Pn, g_rgb, g_n, g_sdf):
+        orig(flat, T, Pn, g_rgb, g_n, g_sdf)
+        names = ['DC%d' % l for l in range(eng.nC + 1)] + ['GOUTF', 'ED'] + ['UD%d' % (l + 1) for l in range(eng.nL)] + \
+            ['AB%d' % l for l in range(eng.nL)]
+        written.append({k: T[k].clone() for k in names})
+
+    monkeypatch.setattr(eng, meth, spy)
+    real_scratch = _C._scratch
+
+    def scratch(tag, need, device, *a, **kw):
+        if tag != 'bwd':
+            return real_scratch(tag, need, device, *a, **kw)
+        sizes.append(need)
+        return torch.empty((small[0] or need,), dtype=torch.uint8, device=device)
+
+    monkeypatch.setattr(_C, '_scratch', scratch)
+    small = [None]
+    full = _run(shape, engine, x, dirs, adj)
+    small[0] = per_wg
+    one = _run(shape, engine, x, dirs, adj)
+    assert sizes == [cus * per_wg] * 2 and len(written) == 2
+    diff = [k for k in written[0] if not torch.equal(_bits(written[0][k]), _bits(written[1][k]))]
+    assert not diff, f'{shape}/{engine}: {diff} differ between {cus} workgroups\' scratch and one\'s'
+    assert _same_bits(full, one)

@@ -10,8 +10,6 @@ Three kinds of comparison (cases, operands and references: tests/wgrad_cases.py,
     (tests/kernel_cases.yardstick: 3x max / 2x rms of the float32 torch.matmul's own error, floor 8 eps), and bit for bit between
     the single-problem and the batched entry (vqnerf_hip.h: "the same kernels, hence the same partial blocks bit for bit")."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -28,18 +26,6 @@ NAN = float('nan')
 # key suffix of the figures that are NOT kernel measurements: the error of torch.matmul in float32 on the CPU against float64, recorded
 # next to the bound it produces (3x max / 2x rms of itself) -- the pair of figures a changed factor would have to be justified by
 REF32 = '#float32_matmul_own_error'
-
-
-def _skip_if_x3_switches():
-    """The diagnostic switches of csrc/wgrad_x3.hip are read once per process and would silently move a case to another kernel."""
-    def atoi(v):                                                 # C's atoi: the leading integer, 0 without one
-        m = re.match(r'\s*[+-]?\d+', v)
-        return int(m.group()) if m else 0
-    for k in wc.X3_ENV:
-        v = os.environ.get(k)
-        # the kernels' own reading: SMALL_TILES counts once it is non-empty, the two NO_ switches once atoi(value) != 0
-        if v and (k == 'VQN_WGRAD_X3_SMALL_TILES' or atoi(v) != 0):
-            pytest.skip(f'{k}={v}: the case would run on another kernel than the one it is written for')
 
 
 class Guarded:
@@ -93,8 +79,6 @@ def test_partial_blocks_are_exact_and_read_only_their_window(case):
     block s must equal the integer contraction over point tiles s, s + n, ... of the window (rows, columns, split, tile range: any
     slip changes an integer), with the tiles around the window poisoned and the workspaces guarded."""
     a_tiles, a_t0, a_nt, b_tiles, b_t0, b_nt, npt, n_split, rowsum = case
-    if npt >= wc.X3_SMALL_FROM:
-        _skip_if_x3_switches()
     ref = wc.exact_partial_case(case)
     Ap, Bp, want_ws, want_rs = ref['Ap'].cuda(), ref['Bp'].cuda(), ref['ws'].cuda(), ref['rs'].cuda()
     got = {}
@@ -119,8 +103,6 @@ def test_partial_blocks_meet_the_float32_yardstick_and_are_the_same_through_both
     the sum of the terms' magnitudes (the relation test_bf16x3_weight_gradient_contraction_matches_the_f32_one holds whole tensors to).
     Row sums: within the rounding bound gamma_K of a float32 sum of the K points, in whatever order."""
     a_tiles, a_t0, a_nt, b_tiles, b_t0, b_nt, npt, n_split, rowsum = case
-    if x3:
-        _skip_if_x3_switches()
     name = 'test_partial_blocks_meet_the_float32_yardstick'
     key = ('x3-' if x3 else 'f32-') + wc.case_id(case)
     assert wc.partial_class(a_nt, b_nt, x3, npt) >= (3 if x3 else 0)
@@ -161,8 +143,6 @@ def test_batched_call_of_forty_problems_equals_forty_single_calls(x3, npt, n_spl
     """One vqn_wgrad_partials_batched call of 40 windows into two shared operands: 26 of one class (more than WG_MAX = 24: its table
     is flushed in the middle of the loop), 14 of every other class reachable, interleaved, every third without row sums.  Integer
     operands: each problem's blocks exact and torch.equal to its single call.  Real operands: bit-equal to the single call."""
-    if x3:
-        _skip_if_x3_switches()
     probs, _ = wc.batched_problems(x3, npt)
     ref = wc.batched_reference(npt, n_split)
     n_exp = ref['n']
@@ -473,8 +453,6 @@ def test_wgradbatch_plan_is_the_matrix_product(which, mode):
     """WgradBatch's windows (8-tile blocking, col_first clipped per block, the thin path's negative pointer offsets) against the
     integer product of the rows the operands were packed from; 3 point tiles, n_split = 64."""
     from vqnerf_release_amd.geo import train_programs as tp
-    if mode == 'bf16x3':
-        _skip_if_x3_switches()
     old = tp.wgrad_mode()
     try:
         tp.wgrad_mode(mode)
@@ -489,7 +467,6 @@ def test_wgradbatch_plan_at_1025_point_tiles():
     """The 257 x 295 weight again at 1025 point tiles under 'bf16x3': its 8 + 1 by 8 + 2 tile blocks run the full, the guarded and
     (the 1-tile row block) the narrow exact-split kernel."""
     from vqnerf_release_amd.geo import train_programs as tp
-    _skip_if_x3_switches()
     old = tp.wgrad_mode()
     try:
         tp.wgrad_mode('bf16x3')

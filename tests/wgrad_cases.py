@@ -14,15 +14,14 @@ U = 2.0 ** -24                # unit roundoff of float32
 GUARD = 64                    # floats of NaN before and after every workspace / destination
 INT_MAX = 8                   # integer operands are drawn from [-INT_MAX, INT_MAX]: one bf16 piece each
 WG_MAX, TH_MAX, FIN_MAX = 24, 24, 40          # problems / entries per launch of the batched kernels (csrc/wgrad_batch.h, wgrad_thin.hip, wgrad_finalize.hip)
-X3_SMALL_FROM = 1024          # point tiles from which vqn_wgrad_partials_x3 keeps a_nt <= 4 problems on the exact-split kernels
-X3_ENV = ('VQN_WGRAD_X3_SMALL_TILES', 'VQN_WGRAD_X3_NO_LDS', 'VQN_WGRAD_X3_NO_NARROW')
+X3_SMALL_FROM = 1024          # csrc/wgrad_batch.h WG_X3_SMALL_FROM: point tiles from which a_nt <= 4 problems stay on the exact-split kernels
 
 CLASS_NAMES = ('f32<1,4,6>', 'f32<1,8,4>', 'f32<2,8,D>', 'x3 full', 'x3 guarded', 'x3 narrow')
 
 
 def partial_class(a_nt, b_nt, x3, n_point_tiles):
-    """The kernel class vqn_wgrad_partials_batched files a problem under (csrc/wgrad_x3.hip); the single-problem entries run the same
-    class, except that they have no narrow kernel: class 5 is the guarded kernel with one idle output tile per wave there."""
+    """wgrad_class of csrc/wgrad_batch.h, restated: the kernel class all three entries file a problem under; the single-problem x3
+    entry has no narrow kernel: class 5 is the guarded kernel with one idle output tile per wave there."""
     f32 = (not x3) or (a_nt <= 4 and n_point_tiles < X3_SMALL_FROM)
     if f32:
         return 0 if (a_nt <= 4 and b_nt <= 4) else (1 if a_nt <= 4 else 2)

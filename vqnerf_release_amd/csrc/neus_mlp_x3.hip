@@ -23,6 +23,9 @@ using namespace eng;
 
 namespace {
 
+// (This file keeps its own copy of the image constants, the call table and next_stream / G / GC that csrc/x3_calls.h holds for the two
+//  training files: on the shared header the fine render kernel measured 0.8 % slower -- 156.4 against 155.0 ms per 640,000-ray view,
+//  three alternations, parent spread 0.5 ms -- with identical compiler resource figures: profiles/train_kernels_shared.json.)
 constexpr int E0 = 0;         // LDS rows [0, 12): embedding / colour-net extras / d sdf / d embedding (up to 4 steps = 64 features)
 constexpr int E_ROWS = 12;
 constexpr int X0 = E_ROWS;    // the activation buffer
@@ -37,7 +40,7 @@ struct SmallsTab : Smalls<2> {
 
 // ---- training forward (TRAIN): as neus_points2_kernel<FINE, TRAIN> of csrc/neus_mlp.hip -- the fine kernel also leaves what the backward
 // (csrc/neus_train_bwd.hip) and the weight-gradient contraction read, in the tile format (TrainOut, tfmt_store_acc / tfmt_store_step of
-// neus_phases.h).  The values stored are the f32 ones the epilogues hold BEFORE the split into bf16 pieces.
+// tfmt.h).  The values stored are the f32 ones the epilogues hold BEFORE the split into bf16 pieces.
 template <bool FINE, int NACC, bool TRAIN = false>
 __global__ __launch_bounds__(512, 1) void neus_points_x3_kernel(
     const SdfDesc sd, const ColDesc cd, const f32x4* __restrict__ wsdf, const f32x4* __restrict__ wcol,

@@ -1,10 +1,11 @@
 // What the fused NeuS point kernels share outside their GEMMs (neus_mlp.hip, neus_mlp_f16s.hip, neus_mlp_x3.hip; the tile-format
-// stores also serve neus_train_bwd.hip and neus_train_bwd_x3.hip).  The three engines differ in how an activation image lies in LDS
+// accessors their training forms use are in tfmt.h).  The three engines differ in how an activation image lies in LDS
 // and in their GEMM loops, epilogues and weight rings, which stay in their own files; the VALU phases around the GEMMs -- point load,
 // sdf output, chain through the embedding, colour-net extras, rgb output -- are the same arithmetic in the same order everywhere and
 // live here once, as plain functions of their inputs.  The host side of the entry points is in neus_launch.h.  Not a public header.
 #pragma once
 #include "mlp_prims.h"
+#include "tfmt.h"
 #include "vqn_neus_desc.h"
 
 namespace eng {
@@ -98,35 +99,6 @@ struct TrainOut {
   float* U[VQN_MAX_SDF_LAYERS]; float* GH[VQN_MAX_SDF_LAYERS]; float* C[VQN_MAX_COL_LAYERS];
   int e_tiles, outf_tiles, extr_tiles;
 };
-
-// A row quad of an f32 activation image -- lane (p, h), component j = feature 2 (4 rq + j) + h of the tile -- goes out as four
-// 256-byte stores (feature rows 8 rq + 2 j and 8 rq + 2 j + 1 are adjacent).
-__device__ __forceinline__ void tfmt_store_quad(float* __restrict__ T, const long ptile, const int n_ft, const int ft, const int rq,
-                                                const int lane, const f32x4 v) {
-  float* base = T + ((ptile * n_ft + ft) * 32 + 8 * rq) * 32 + lane;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v[j], base + 64 * j);     // written once, read by later launches: past the L2-resident packs
-}
-// an accumulator tile of the pair engines: register i of lane (p, h) is feature (i & 3) + 8 (i >> 2) + 4 h of the tile
-__device__ __forceinline__ void tfmt_store_acc(float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, const float (&v)[16]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(v[0]), "v"(v[3]), "v"(v[7]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) __builtin_nontemporal_store(v[i], base + ((i & 3) + 8 * (i >> 2)) * 32);
-}
-// a K step of an image of the pair engines: slot jj of lane (p, h) is feature 16 sl + 8 (jj >> 2) + 4 h + (jj & 3)
-__device__ __forceinline__ void tfmt_store_step(float* __restrict__ T, const long ptile, const int n_ft, const int sl, const int lane, const float (&x)[8]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(x[0]), "v"(x[3]), "v"(x[7]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + (sl >> 1)) * 32 + 16 * (sl & 1) + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) __builtin_nontemporal_store(x[jj], base + (8 * (jj >> 2) + (jj & 3)) * 32);
-}
 
 }  // namespace eng
 

@@ -18,7 +18,7 @@
 // (the same statement as the interpreted programs prog_cbwd / prog_sbwd of geo/train_programs.py, which remain the path of
 // networks this kernel does not take: fewer than five or more than eight feature tiles.  csrc/neus_train_bwd_x3.hip is the same pass on the
 // exact-split engine, the trainers' default.)
-#include "neus_phases.h"
+#include "neus_launch.h"
 #include "vqnerf_hip.h"
 #include <stdlib.h>
 
@@ -28,43 +28,9 @@ namespace {
 
 constexpr int E0 = 0;
 constexpr int E_ROWS = 8;
-constexpr int TB_MAX_L = 12;
-
-struct TrainBwdDesc {        // int32 words, filled by the host (geo/train_programs.py: NeusTrainEngine._bwd_static)
-  int nL, nC, skip, emb_rows, emb_feats, e_tiles, max_tiles, feat_tiles;
-  int outf_tiles, squeeze, offBtop, offWrow, offCBfeat, offCBnrm;
-  float scale, inv_scale;
-  int ts[TB_MAX_L];          // feature tiles of SDF hidden layer l's output
-  int tc[TB_MAX_L];          // feature tiles of colour hidden layer l's output
-  int offT[TB_MAX_L];        // W_l (K = [u_{l-1} (, e)]), float4 units into the pack
-  int offB[TB_MAX_L];        // W_l[:, :out_{l-1}]^T, l = 1..nL-1
-  int offCB[TB_MAX_L];       // Wc_l^T, l = 1..nC (l = nC: K = one row)
-};
-constexpr int TB_DESC_INTS = 16 + 5 * TB_MAX_L;
-static_assert(sizeof(TrainBwdDesc) == TB_DESC_INTS * 4, "descriptor layout");
-
-struct TrainBwdPtrs {
-  const float* X; const float* G_RGB; const float* RGB; const float* G_N; const float* G_SDF;
-  const float* U[TB_MAX_L];    // U[l], l = 1..nL: output of SDF layer l - 1
-  const float* GH[TB_MAX_L];   // GH[l], l = 0..nL-1
-  const float* C[TB_MAX_L];    // C[l], l = 1..nC: output of colour layer l - 1
-  float* DC[TB_MAX_L];         // DC[l], l = 0..nC
-  float* UD[TB_MAX_L];         // UD[l], l = 1..nL
-  float* AB[TB_MAX_L];         // AB[l], l = 0..nL-1
-  float* GOUTF; float* ED;
-};
-
 struct SmallsB {
   float pts[2][96], dout[2][96], gn[2][96], v[2][96], gs[2][32], part[2][512];
 };
-
-// the tile format -> a row quad of an activation image (the reverse of tfmt_store_quad, neus_phases.h): lane (p, h), component j =
-// feature 8 rq + 2 j + h of the feature tile
-__device__ __forceinline__ f32x4 tf_load(const float* __restrict__ T, const long ptile, const int n_ft, const int ft, const int rq,
-                                         const int lane) {
-  const float* base = T + ((ptile * n_ft + ft) * 32 + 8 * rq) * 32 + lane;
-  return (f32x4){base[0], base[64], base[128], base[192]};
-}
 
 __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdDesc bd, const f32x4* __restrict__ wb, const TrainBwdPtrs tp,
                                                                  const long P, f32x4* __restrict__ scratch) {
@@ -99,8 +65,8 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
     auto fetch_q = [&](const Aux& x, int im, int rq) {
       if (wave >= x.tiles) return;
       const bool live = 2 * pair + im < n_tiles;
-      ca[im][rq] = (x.a != nullptr && live) ? tf_load(x.a, 2 * pair + im, x.tiles, wave, rq, lane) : zero4;
-      if (x.b != nullptr) cb[im][rq] = live ? tf_load(x.b, 2 * pair + im, x.tiles, wave, rq, lane) : zero4;
+      ca[im][rq] = (x.a != nullptr && live) ? tfmt_load_quad(x.a, 2 * pair + im, x.tiles, wave, rq, lane) : zero4;
+      if (x.b != nullptr) cb[im][rq] = live ? tfmt_load_quad(x.b, 2 * pair + im, x.tiles, wave, rq, lane) : zero4;
       else if (x.s != nullptr) cb[im][rq] = ld_stream(x.s + (size_t)im * per_img + (wave * 4 + rq) * 64 + lane);
     };
     auto fetch = [&](const Aux& x) {
@@ -312,62 +278,26 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd2_kernel(const TrainBwdD
 
 size_t lds_bytes_b(int MT) { return (size_t)2 * (E_ROWS + 8 * MT) * 1024 + sizeof(SmallsB); }
 
-int load_desc(const int32_t* desc, TrainBwdDesc& bd) {
-  memcpy(&bd, desc, sizeof(TrainBwdDesc));
-  if (bd.nL < 2 || bd.nL >= TB_MAX_L || bd.nC < 1 || bd.nC >= TB_MAX_L) return 1;
+// this engine's descriptor rules (the shared ones: train_bwd_load_desc, neus_launch.h)
+int engine_rules(const TrainBwdDesc& bd) {
   if (bd.max_tiles < 5 || bd.max_tiles > 8 || lds_bytes_b(bd.max_tiles) > 160 * 1024) return 2;      // (<= 8: a wave owns at most one tile per GEMM)
   if (bd.emb_rows < 1 || bd.emb_rows > E_ROWS || bd.e_tiles * 4 < bd.emb_rows || bd.e_tiles > 2 || bd.emb_feats < 3 || bd.emb_feats > 8 * bd.emb_rows) return 3;
-  if (bd.skip == 0 || bd.skip >= bd.nL) return 4;
-  if (bd.feat_tiles < 1 || bd.feat_tiles > bd.max_tiles || bd.outf_tiles < bd.feat_tiles) return 5;      // (GOUTF stores are bounded by outf_tiles)
-  for (int l = 0; l < bd.nL; ++l) if (bd.ts[l] < 1 || bd.ts[l] > bd.max_tiles) return 6;
-  for (int l = 0; l < bd.nC; ++l) if (bd.tc[l] < 1 || bd.tc[l] > bd.max_tiles) return 7;
-  if (!(bd.scale > 0.f)) return 8;
   return 0;
 }
 
 }  // namespace
 
-extern "C" int64_t vqn_neus_train_bwd_scratch_bytes(const int32_t* desc) {
-  if (!desc) return -1;
-  TrainBwdDesc bd;
-  if (load_desc(desc, bd) != 0) return -1;
-  return (int64_t)vqn_num_cus() * 2 * (bd.nL + 1) * 4 * bd.max_tiles * 1024;
-}
+extern "C" int64_t vqn_neus_train_bwd_scratch_bytes(const int32_t* desc) { return train_bwd_scratch_bytes(desc, engine_rules); }
 
 extern "C" int vqn_neus_train_bwd(const int32_t* desc, const float* wbuf, const float* pts, const float* g_rgb, const float* rgb,
                                   const float* g_n, const float* g_sdf, int64_t P, void* scratch, int64_t scratch_bytes,
                                   const float* const* saved, int n_saved, float* const* outs, int n_outs, void* stream) {
-  VQN_CHECK_ARG(desc && wbuf && pts && g_rgb && scratch && saved && outs, "null pointer");
-  VQN_CHECK_ARG(P >= 1, "P >= 1");
   TrainBwdDesc bd;
-  VQN_CHECK_SHAPE(load_desc(desc, bd) == 0, "invalid backward descriptor");
-  const int nL = bd.nL, nC = bd.nC;
-  VQN_CHECK_ARG(n_saved == 2 * nL + nC, "saved: [U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC]");
-  VQN_CHECK_ARG(n_outs == (nC + 1) + 2 + 2 * nL, "outs: [DC_0..DC_nC, GOUTF, ED, UD_1..UD_nL, AB_0..AB_{nL-1}]");
-  VQN_CHECK_ARG((rgb != nullptr) == (bd.squeeze != 0), "rgb: the forward's colours when the colour net ends in a sigmoid, else NULL");
-  for (int i = 0; i < n_saved; ++i) VQN_CHECK_ARG(saved[i] != nullptr, "null saved tensor");
-  for (int i = 0; i < n_outs; ++i) VQN_CHECK_ARG(outs[i] != nullptr, "null output tensor");
   TrainBwdPtrs tp;
-  memset(&tp, 0, sizeof(tp));
-  tp.X = pts; tp.G_RGB = g_rgb; tp.RGB = rgb; tp.G_N = g_n; tp.G_SDF = g_sdf;
-  for (int l = 1; l <= nL; ++l) tp.U[l] = saved[l - 1];
-  for (int l = 0; l < nL; ++l) tp.GH[l] = saved[nL + l];
-  for (int l = 1; l <= nC; ++l) tp.C[l] = saved[2 * nL + l - 1];
-  for (int l = 0; l <= nC; ++l) tp.DC[l] = outs[l];
-  tp.GOUTF = outs[nC + 1];
-  tp.ED = outs[nC + 2];
-  for (int l = 1; l <= nL; ++l) tp.UD[l] = outs[nC + 3 + l - 1];
-  for (int l = 0; l < nL; ++l) tp.AB[l] = outs[nC + 3 + nL + l];
-  const long n_tiles = (P + 31) / 32;
-  const int64_t per_wg = (int64_t)2 * (nL + 1) * 4 * bd.max_tiles * 1024;
-  const size_t lds = lds_bytes_b(bd.max_tiles);
-  VQN_HIP(hipFuncSetAttribute((const void*)neus_train_bwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  long grid = (long)vqn_num_cus();
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-  if ((int64_t)grid * per_wg > scratch_bytes) grid = (long)(scratch_bytes / per_wg);
-  VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_train_bwd_scratch_bytes)");
-  hipLaunchKernelGGL(neus_train_bwd2_kernel, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, bd,
+  long grid;
+  const int rc = train_bwd_args(__func__, desc, wbuf, wbuf, pts, g_rgb, rgb, g_n, g_sdf, P, scratch, scratch_bytes, saved, n_saved, outs,
+                                n_outs, engine_rules, "invalid backward descriptor", &bd, &tp, &grid);
+  if (rc != VQN_OK) return rc;
+  return neus_launch(__func__, neus_train_bwd2_kernel, true, grid, 512, lds_bytes_b(bd.max_tiles), stream, bd,
                      reinterpret_cast<const f32x4*>(wbuf), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
 }

@@ -7,51 +7,22 @@
 //
 // Also here: vqn_pack_x3_gather, the weight pack of this kernel in one launch (gather from the flat parameter vector + the exact
 // three-way split of every gathered value into bf16 pieces, geo/packing.py: split_pack_x3).
-#include "mlp_prims_x3.h"
-#include "neus_phases.h"
+#include "x3_calls.h"
+#include "neus_launch.h"
 #include "vqnerf_hip.h"
 #include <stdlib.h>
 
 using namespace eng;
+using namespace eng::x3;
 
 namespace {
 
-constexpr int E0 = 0;
-constexpr int E_ROWS = 12;
-constexpr int X0 = E_ROWS;
-constexpr int RING = 2;
-constexpr int NW = 8;
-constexpr int MAX_CALLS = 40;
-constexpr int TB_MAX_L = 12;
-
-struct TrainBwdDesc {        // as csrc/neus_train_bwd.hip; here emb_rows counts x3 rows, offT / offB / offCB / offBtop / offCBfeat index the
-  int nL, nC, skip, emb_rows, emb_feats, e_tiles, max_tiles, feat_tiles;     // piece pack and offWrow / offCBnrm the f32 image buffer (float4 units)
-  int outf_tiles, squeeze, offBtop, offWrow, offCBfeat, offCBnrm;
-  float scale, inv_scale;
-  int ts[TB_MAX_L], tc[TB_MAX_L], offT[TB_MAX_L], offB[TB_MAX_L], offCB[TB_MAX_L];
-};
-constexpr int TB_DESC_INTS = 16 + 5 * TB_MAX_L;
-static_assert(sizeof(TrainBwdDesc) == TB_DESC_INTS * 4, "descriptor layout");
-
-struct TrainBwdPtrs {
-  const float* X; const float* G_RGB; const float* RGB; const float* G_N; const float* G_SDF;
-  const float* U[TB_MAX_L]; const float* GH[TB_MAX_L]; const float* C[TB_MAX_L];
-  float* DC[TB_MAX_L]; float* UD[TB_MAX_L]; float* AB[TB_MAX_L];
-  float* GOUTF; float* ED;
-};
 
 struct SmallsB {
   float pts[2][96], dout[2][96], gn[2][96], v[2][96], gs[2][32], part[2][512];
-  int tab[MAX_CALLS * 3];      // GEMM calls of one tile pair in program order: {float4 offset, K blocks, out tiles}
-  int n_calls;
+  CallTab calls;               // GEMM calls of one tile pair (x3_calls.h)
 };
 
-// tile format -> accumulator tile (the reverse of tfmt_store_acc, neus_phases.h): register i of lane (p, h) is feature (i & 3) + 8 (i >> 2) + 4 h of the feature tile
-__device__ __forceinline__ void tf_load_acc(const float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, float (&v)[16]) {
-  const float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v[i] = base[((i & 3) + 8 * (i >> 2)) * 32];
-}
 template <int NACC>
 __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBwdDesc bd, const f32x4* __restrict__ wx, const f32x4* __restrict__ wf,
                                                                    const TrainBwdPtrs tp, const long P, f32x4* __restrict__ scratch) {
@@ -68,62 +39,29 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
   const size_t per_img = (size_t)(nL + 1) * 4 * MT * 64;           // stash: S_0..S_{nL-1}, g_feat (accumulator-order quads)
   f32x4* save0 = scratch + (size_t)blockIdx.x * 2 * per_img;
   const int feat_slot = nL * 4 * MT;
-  auto blocks_of = [](int krows) { return (krows / 3 + 1) >> 1; };
 
   // ---------------- the pass's GEMM calls, in order (the weight stream follows this table) ----------------
   if (tid == 0) {
     int n = 0;
-    auto add = [&](int off, int krows, int tiles) { sm->tab[3 * n] = off; sm->tab[3 * n + 1] = blocks_of(krows); sm->tab[3 * n + 2] = tiles; ++n; };
+    auto add = [&](int off, int krows, int tiles) { add_call(&sm->calls, n, off, 0, krows, tiles); };
     for (int l = nC; l >= 1; --l) add(bd.offCB[l], l == nC ? 3 : 6 * bd.tc[l], bd.tc[l - 1]);
     add(bd.offCBfeat, 6 * bd.tc[0], bd.feat_tiles);
     for (int l = 0; l < nL; ++l) add(bd.offT[l], l == 0 ? bd.emb_rows : 6 * bd.ts[l - 1] + (l == bd.skip ? bd.emb_rows : 0), bd.ts[l]);
     add(bd.offBtop, 6 * bd.feat_tiles, bd.ts[nL - 1]);
     for (int l = nL - 1; l >= 1; --l) add(bd.offB[l], 6 * bd.ts[l], bd.ts[l - 1]);
-    sm->n_calls = n;
+    sm->calls.n_calls = n;
   }
   __syncthreads();
-  const int n_calls = __builtin_amdgcn_readfirstlane(sm->n_calls);
-  auto next_stream = [&](int idx, const f32x4*& nwp, int& nnb) {
-    nwp = wx + lane; nnb = 1;
-    for (int k = 1; k <= n_calls; ++k) {
-      const int m = (idx + k) % n_calls;
-      const int tiles = __builtin_amdgcn_readfirstlane(sm->tab[3 * m + 2]);
-      if (wave < tiles) {
-        const int off = __builtin_amdgcn_readfirstlane(sm->tab[3 * m]);
-        nnb = __builtin_amdgcn_readfirstlane(sm->tab[3 * m + 1]);
-        nwp = wx + off + (size_t)wave * nnb * 384 + lane;
-        return;
-      }
-    }
-  };
+  const int n_calls = __builtin_amdgcn_readfirstlane(sm->calls.n_calls);
   f32x4 ring[RING][6];
-  {
-    const f32x4* wp0; int nb0;
-    next_stream(n_calls - 1, wp0, nb0);
-    ring_prime_x3<RING>(ring, wp0, nb0);
-  }
+  prime_stream(&sm->calls, n_calls, wx, wx, lane, [&](int) { return wave; }, ring);
   int call = 0;
+  // a GEMM call, and one whose output goes over its own input (a layer in place): x3_calls.h
   auto G = [&](const f32x4* wbase, const KSegs ks, const int tiles, auto init, auto epi) {
-    const f32x4* nwp; int nnb;
-    next_stream(call, nwp, nnb);
-    ++call;
-    gemm_tiles_x3_ring2<NW, RING, NACC>(lds, IS, ks, wbase, tiles, wave, lane, ring, nwp, nnb, init, epi);
+    gemm_call2<NACC, false>(&sm->calls, n_calls, call, wx, wx, lds, IS, ks, wbase, tiles, wave, lane, ring, init, epi);
   };
-  // A layer IN PLACE (its output tile `wave` goes over its own input, the X buffer): the accumulators stay where the K loop left them,
-  // a barrier sees every wave out of its K loop -- the input rows are dead --, then the epilogues write their tiles straight over the
-  // input (store_tile_x3) and a second barrier publishes them; waves without a tile in this GEMM reach the same two barriers from
-  // the branch below.  (Rounds 3's form parked the finished, already split tiles in 48 registers across the barrier: they ended in
-  // scratch, and every layer re-read 18 x 16 B per lane behind the epilogue's global stores -- round 4, found with in-kernel stamps
-  // on csrc/refl_train_x3.hip, where the same change took a third off the backward.)
   auto GC = [&](const f32x4* wbase, const KSegs ks, const int tiles, auto init, auto epi) {
-    const f32x4* nwp; int nnb;
-    next_stream(call, nwp, nnb);
-    ++call;
-    gemm_tiles_x3_ring2<NW, RING, NACC>(lds, IS, ks, wbase, tiles, wave, lane, ring, nwp, nnb, init,
-                                        [&](int ot, auto im_c, const f32x16& acc) __attribute__((always_inline)) {
-          if (decltype(im_c)::value == 0) __syncthreads(); epi(ot, im_c, acc); });
-    if (wave >= tiles) __syncthreads();
-    __syncthreads();
+    gemm_call2<NACC, true>(&sm->calls, n_calls, call, wx, wx, lds, IS, ks, wbase, tiles, wave, lane, ring, init, epi);
   };
   // epilogue operands of this wave's tile, both images, requested right before the K loop.  (The f32 kernel's refinement -- the NEXT GEMM's
   // operands requested in place from inside the current epilogue -- measured slower here: 6.80 -> 7.19 ms, 39 -> 99 spilled VGPRs: the
@@ -180,7 +118,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
       GC(wx + bd.offCB[l], ks, n_ot,
         [&](int ot, auto im_c, f32x16& acc) __attribute__((always_inline)) {
           constexpr int im = decltype(im_c)::value; (void)im;
-          if (2 * pair + im < n_tiles) tf_load_acc(t_c, 2 * pair + im, n_ot, ot, lane, au[im]);
+          if (2 * pair + im < n_tiles) tfmt_load_acc(t_c, 2 * pair + im, n_ot, ot, lane, au[im]);
           else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) au[im][i] = 0.f;
@@ -269,8 +207,8 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
         [&](int ot, auto im_c, f32x16& acc) __attribute__((always_inline)) {
           constexpr int im = decltype(im_c)::value; (void)im;
           if (2 * pair + im < n_tiles) {
-            tf_load_acc(t_u, 2 * pair + im, n_ot, ot, lane, au[im]);
-            tf_load_acc(t_gh, 2 * pair + im, n_ot, ot, lane, ab[im]);
+            tfmt_load_acc(t_u, 2 * pair + im, n_ot, ot, lane, au[im]);
+            tfmt_load_acc(t_gh, 2 * pair + im, n_ot, ot, lane, ab[im]);
           } else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { au[im][i] = 0.f; ab[im][i] = 0.f; }
@@ -320,7 +258,7 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
         [&](int ot, auto im_c, f32x16& acc) __attribute__((always_inline)) {
           constexpr int im = decltype(im_c)::value; (void)im;
           const f32x4* sv = save0 + (size_t)im * per_img + (size_t)(l - 1) * 4 * MT * 64;
-          if (2 * pair + im < n_tiles) tf_load_acc(t_u, 2 * pair + im, n_ot, ot, lane, au[im]);
+          if (2 * pair + im < n_tiles) tfmt_load_acc(t_u, 2 * pair + im, n_ot, ot, lane, au[im]);
           else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) au[im][i] = 0.f;
@@ -351,16 +289,11 @@ __global__ __launch_bounds__(512, 1) void neus_train_bwd_x3_kernel(const TrainBw
 
 size_t lds_bytes_b(int MT) { return (size_t)2 * (E_ROWS + 6 * MT) * 1024 + sizeof(SmallsB); }
 
-int load_desc(const int32_t* desc, TrainBwdDesc& bd) {
-  memcpy(&bd, desc, sizeof(TrainBwdDesc));
-  if (bd.nL < 2 || bd.nL >= TB_MAX_L || bd.nC < 1 || bd.nC >= TB_MAX_L) return 1;
+// this engine's descriptor rules (the shared ones: train_bwd_load_desc, neus_launch.h); emb_rows counts x3 rows, offT / offB / offCB /
+// offBtop / offCBfeat index the piece pack and offWrow / offCBnrm the f32 image buffer
+int engine_rules(const TrainBwdDesc& bd) {
   if (bd.max_tiles < 1 || bd.max_tiles > NW || lds_bytes_b(bd.max_tiles) > 160 * 1024) return 2;
   if (bd.emb_feats < 3 || bd.emb_feats > 64 || bd.emb_rows != x3_rows(bd.emb_feats) || bd.emb_rows > E_ROWS || 2 * bd.e_tiles * 3 < bd.emb_rows || bd.e_tiles > 2) return 3;
-  if (bd.skip == 0 || bd.skip >= bd.nL) return 4;
-  if (bd.feat_tiles < 1 || bd.feat_tiles > bd.max_tiles || bd.outf_tiles < bd.feat_tiles) return 5;      // (GOUTF stores are bounded by outf_tiles)
-  for (int l = 0; l < bd.nL; ++l) if (bd.ts[l] < 1 || bd.ts[l] > bd.max_tiles) return 6;
-  for (int l = 0; l < bd.nC; ++l) if (bd.tc[l] < 1 || bd.tc[l] > bd.max_tiles) return 7;
-  if (!(bd.scale > 0.f)) return 8;
   if (2 * bd.nL + bd.nC + 2 > MAX_CALLS) return 9;
   return 0;
 }
@@ -428,48 +361,19 @@ extern "C" int vqn_pack_x3_gather(const float* flat, const int32_t* gidx, int64_
   return vqn_pack_x3_gather2(flat, gidx, n_steps, out, nullptr, 0, nullptr, stream);
 }
 
-extern "C" int64_t vqn_neus_train_bwd_x3_scratch_bytes(const int32_t* desc) {
-  if (!desc) return -1;
-  TrainBwdDesc bd;
-  if (load_desc(desc, bd) != 0) return -1;
-  return (int64_t)vqn_num_cus() * 2 * (bd.nL + 1) * 4 * bd.max_tiles * 1024;
-}
+extern "C" int64_t vqn_neus_train_bwd_x3_scratch_bytes(const int32_t* desc) { return train_bwd_scratch_bytes(desc, engine_rules); }
 
 extern "C" int vqn_neus_train_bwd_x3(const int32_t* desc, const void* wbuf_pieces, const float* wbuf_f32, const float* pts, const float* g_rgb,
                                      const float* rgb, const float* g_n, const float* g_sdf, int64_t P, void* scratch, int64_t scratch_bytes,
                                      const float* const* saved, int n_saved, float* const* outs, int n_outs, void* stream) {
-  VQN_CHECK_ARG(desc && wbuf_pieces && wbuf_f32 && pts && g_rgb && scratch && saved && outs, "null pointer");
-  VQN_CHECK_ARG(P >= 1, "P >= 1");
   TrainBwdDesc bd;
-  VQN_CHECK_SHAPE(load_desc(desc, bd) == 0, "invalid backward descriptor for the x3 engine (layers of at most 256 outputs)");
-  const int nL = bd.nL, nC = bd.nC;
-  VQN_CHECK_ARG(n_saved == 2 * nL + nC, "saved: [U_1..U_nL, GH_0..GH_{nL-1}, C_1..C_nC]");
-  VQN_CHECK_ARG(n_outs == (nC + 1) + 2 + 2 * nL, "outs: [DC_0..DC_nC, GOUTF, ED, UD_1..UD_nL, AB_0..AB_{nL-1}]");
-  VQN_CHECK_ARG((rgb != nullptr) == (bd.squeeze != 0), "rgb: the forward's colours when the colour net ends in a sigmoid, else NULL");
-  for (int i = 0; i < n_saved; ++i) VQN_CHECK_ARG(saved[i] != nullptr, "null saved tensor");
-  for (int i = 0; i < n_outs; ++i) VQN_CHECK_ARG(outs[i] != nullptr, "null output tensor");
   TrainBwdPtrs tp;
-  memset(&tp, 0, sizeof(tp));
-  tp.X = pts; tp.G_RGB = g_rgb; tp.RGB = rgb; tp.G_N = g_n; tp.G_SDF = g_sdf;
-  for (int l = 1; l <= nL; ++l) tp.U[l] = saved[l - 1];
-  for (int l = 0; l < nL; ++l) tp.GH[l] = saved[nL + l];
-  for (int l = 1; l <= nC; ++l) tp.C[l] = saved[2 * nL + l - 1];
-  for (int l = 0; l <= nC; ++l) tp.DC[l] = outs[l];
-  tp.GOUTF = outs[nC + 1];
-  tp.ED = outs[nC + 2];
-  for (int l = 1; l <= nL; ++l) tp.UD[l] = outs[nC + 3 + l - 1];
-  for (int l = 0; l < nL; ++l) tp.AB[l] = outs[nC + 3 + nL + l];
-  const long n_tiles = (P + 31) / 32;
-  const int64_t per_wg = (int64_t)2 * (nL + 1) * 4 * bd.max_tiles * 1024;
-  const size_t lds = lds_bytes_b(bd.max_tiles);
-  auto kern = bwd_nacc() == 2 ? neus_train_bwd_x3_kernel<2> : neus_train_bwd_x3_kernel<1>;
-  VQN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  long grid = (long)vqn_num_cus();
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
-  if ((int64_t)grid * per_wg > scratch_bytes) grid = (long)(scratch_bytes / per_wg);
-  VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_train_bwd_x3_scratch_bytes)");
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, bd, reinterpret_cast<const f32x4*>(wbuf_pieces),
+  long grid;
+  const int rc = train_bwd_args(__func__, desc, wbuf_pieces, wbuf_f32, pts, g_rgb, rgb, g_n, g_sdf, P, scratch, scratch_bytes, saved, n_saved,
+                                outs, n_outs, engine_rules, "invalid backward descriptor for the x3 engine (layers of at most 256 outputs)",
+                                &bd, &tp, &grid);
+  if (rc != VQN_OK) return rc;
+  return neus_launch(__func__, bwd_nacc() == 2 ? neus_train_bwd_x3_kernel<2> : neus_train_bwd_x3_kernel<1>, true, grid, 512,
+                     lds_bytes_b(bd.max_tiles), stream, bd, reinterpret_cast<const f32x4*>(wbuf_pieces),
                      reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
 }

@@ -17,24 +17,21 @@
 // most four (the 128-wide ones): the waves split by image (gemm_tile_x3_ring1) so that all eight have a tile.  The 1..3-output last
 // layer of a head never touches the matrix pipe: forward row dots, backward rank-c updates on the vector ALU.
 // Saved tensors and adjoints are f32 in the tile format [point tile][feature tile][32 features][32 points] the contraction reads.
-#include "mlp_prims_x3.h"
+#include "x3_calls.h"
+#include "tfmt.h"
 #include "vqnerf_hip.h"
 #include <stdlib.h>
 #include <type_traits>
 
 using namespace eng;
+using namespace eng::x3;
 template <int I> using IC = std::integral_constant<int, I>;
 
 namespace {
 
-constexpr int E0 = 0;
-constexpr int E_ROWS = 12;
-constexpr int X0 = E_ROWS;
-constexpr int RING = 2;
-constexpr int NW = 8;
 constexpr int RT_MAX_L = 8;
 constexpr int RT_MAX_H = 3;
-constexpr int MAX_CALLS = RT_MAX_L + 2 * RT_MAX_H;
+static_assert(RT_MAX_L + 2 * RT_MAX_H <= MAX_CALLS, "a unit's GEMM calls fit the call table");
 
 // In-kernel phase timing of the backward (diagnostic build -DVQN_RT_STAMPS only; scripts/debug/refl_stamps.py): wave 0 of every
 // workgroup accumulates shader-clock cycles per phase.
@@ -87,38 +84,8 @@ struct ReflBwdPtrs {
 
 struct SmallsR {
   float pts[2][96], part[2 * 4 * 32 * 3], h2z[RT_MAX_H][2][96], d2[2][96];
-  int tab[MAX_CALLS * 4];                   // GEMM calls of one unit in program order: {float4 offset, K blocks, out tiles, 0}
-  int n_calls;
+  CallTab calls;                            // GEMM calls of one unit (x3_calls.h)
 };
-
-// accumulator tile <-> tile format: register i of lane (p, h) is feature (i & 3) + 8 (i >> 2) + 4 h of the feature tile
-__device__ __forceinline__ void tf_store_acc(float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, const float (&v)[16]) {
-#ifdef VQN_DIAG_RT_NO_ST        // timing only
-  asm volatile("" ::"v"(v[0]), "v"(v[5]), "v"(v[10]), "v"(v[15]));
-  return;
-#endif
-  float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) __builtin_nontemporal_store(v[i], base + ((i & 3) + 8 * (i >> 2)) * 32);
-}
-__device__ __forceinline__ void tf_load_acc(const float* __restrict__ T, const long ptile, const int n_ft, const int ot, const int lane, float (&v)[16]) {
-#ifdef VQN_DIAG_RT_NO_LD        // timing only
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v[i] = 0.5f + 0.001f * (float)(lane + i);
-  return;
-#endif
-  // (streaming `nt` loads here -- so that the saved tensors, 14 KB per point passing through once, leave the weight packs in L2 --
-  //  measured no better: backward 3.18 -> 3.26 ms per 262,144 points)
-  const float* base = T + ((ptile * n_ft + ot) * 32 + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v[i] = base[((i & 3) + 8 * (i >> 2)) * 32];
-}
-// a K step of an image: slot jj of lane (p, h) is feature 16 sl + 8 (jj >> 2) + 4 h + (jj & 3)
-__device__ __forceinline__ void tf_store_step(float* __restrict__ T, const long ptile, const int n_ft, const int sl, const int lane, const float (&x)[8]) {
-  float* base = T + ((ptile * n_ft + (sl >> 1)) * 32 + 16 * (sl & 1) + 4 * (lane >> 5)) * 32 + (lane & 31);
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) __builtin_nontemporal_store(x[jj], base + (8 * (jj >> 2) + (jj & 3)) * 32);
-}
 
 __device__ __forceinline__ void act_apply(const int act, const f32x16& acc, float (&v)[16]) {
   if (act == ACT_RELU) {
@@ -171,9 +138,8 @@ __device__ __forceinline__ void dact_mul(const int act, const float (&y)[16], fl
   float* part_i = sm->part + img * (4 * 32 * 3);        /* (NIMG = 1: all 8 x 32 x 3 floats are image 0's) */ \
   const long n_tiles = (P + 31) >> 5, n_units = NIMG == 1 ? n_tiles : ((n_tiles + 1) >> 1);                  \
   const int k_lo = gridDim.y > 1 ? (int)blockIdx.y : 0, k_hi = gridDim.y > 1 ? k_lo + 1 : rd.n_heads;       \
-  auto blocks_of = [](int krows) { return (krows / 3 + 1) >> 1; };                                           \
   auto ptile_of = [&](long unit, int im) { return NIMG == 1 ? unit : 2 * unit + im; };                       \
-  (void)ldsi; (void)h; (void)p; (void)blocks_of; (void)part_i; (void)k_hi; (void)NWI; (void)X1;              \
+  (void)ldsi; (void)h; (void)p; (void)part_i; (void)k_hi; (void)NWI; (void)X1;              \
   RT_OCC2_PHASE_DELAY();
 
 // sum of the NWI per-wave partial row dots of (point pp, output c)
@@ -182,29 +148,12 @@ __device__ __forceinline__ void dact_mul(const int act, const float (&y)[16], fl
                (((pr)[(4 * 32 + (pp)) * (nc) + (c)] + (pr)[(5 * 32 + (pp)) * (nc) + (c)]) + ((pr)[(6 * 32 + (pp)) * (nc) + (c)] + (pr)[(7 * 32 + (pp)) * (nc) + (c)])) \
              : (((pr)[(0 * 32 + (pp)) * (nc) + (c)] + (pr)[(1 * 32 + (pp)) * (nc) + (c)]) + ((pr)[(2 * 32 + (pp)) * (nc) + (c)] + (pr)[(3 * 32 + (pp)) * (nc) + (c)])))
 
-// the wave's first tile of the next GEMM call (after `idx`, wrapping into the next unit) in which it owns one
+// the unit's call stream (x3_calls.h) under this kernel's ownership rule: layers of at most four output tiles split the waves by image
 #define REFL_STREAM()                                                                                        \
-  const int n_calls = __builtin_amdgcn_readfirstlane(sm->n_calls);                                           \
-  auto next_stream = [&](int idx, const f32x4*& nwp, int& nnb) {                                             \
-    nwp = wx + lane; nnb = 1;                                                                                \
-    for (int k = 1; k <= n_calls; ++k) {                                                                     \
-      const int m = (idx + k) % n_calls;                                                                     \
-      const int tiles = __builtin_amdgcn_readfirstlane(sm->tab[4 * m + 2]);                                  \
-      const int mine = (NIMG == 2 && tiles <= 4) ? w4 : wave;                                                \
-      if (mine < tiles) {                                                                                    \
-        const int off = __builtin_amdgcn_readfirstlane(sm->tab[4 * m]);                                      \
-        nnb = __builtin_amdgcn_readfirstlane(sm->tab[4 * m + 1]);                                            \
-        nwp = wx + off + (size_t)mine * nnb * 384 + lane;                                                    \
-        return;                                                                                              \
-      }                                                                                                      \
-    }                                                                                                        \
-  };                                                                                                         \
+  const int n_calls = __builtin_amdgcn_readfirstlane(sm->calls.n_calls);                                           \
+  const auto own = [&](const int tiles) { return (NIMG == 2 && tiles <= 4) ? w4 : wave; };                   \
   f32x4 ring[RING][6];                                                                                       \
-  if (n_calls > 0) {                                                                                         \
-    const f32x4* wp0; int nb0;                                                                               \
-    next_stream(n_calls - 1, wp0, nb0);                                                                      \
-    ring_prime_x3<RING>(ring, wp0, nb0);                                                                     \
-  }                                                                                                          \
+  if (n_calls > 0) prime_stream(&sm->calls, n_calls, wx, wx, lane, own, ring);                                       \
   int call = 0;                                                                                              \
   /* init(ot, im, slot, acc) / epi(ot, im, slot, acc) once per (tile, image) the wave owns; `slot` (a compile-time constant    \
      after inlining: 0 in the one-tile forms, the image in the two-image form) indexes the per-image REGISTER arrays (o, au) -- a  \
@@ -212,7 +161,7 @@ __device__ __forceinline__ void dact_mul(const int act, const float (&y)[16], fl
   auto Gx = [&](const int off, const KSegs ks, const int tiles, auto commit_c, auto init, auto epi) __attribute__((always_inline)) { \
     constexpr bool COMMIT = decltype(commit_c)::value != 0;                                                  \
     const f32x4* nwp; int nnb;                                                                               \
-    next_stream(call, nwp, nnb);                                                                             \
+    next_stream(&sm->calls, n_calls, call, wx, wx, lane, own, nwp, nnb);                                             \
     ++call;                                                                                                  \
     /* COMMIT (a layer IN PLACE): the wave's accumulators stay where the K loop left them, a barrier sees every wave out of its K   \
        loop -- the input rows are dead --, then the epilogues write their tiles straight over the input (store_tile_x3) and a second  \
@@ -272,10 +221,10 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
   const bool wr_shared = blockIdx.y == 0;             // (heads split over blockIdx.y: the encoder's tensors are written by row 0 only)
   if (tid == 0) {
     int n = 0;
-    auto add = [&](int off, int krows, int tiles) { sm->tab[4 * n] = off; sm->tab[4 * n + 1] = blocks_of(krows); sm->tab[4 * n + 2] = tiles; sm->tab[4 * n + 3] = 0; ++n; };
+    auto add = [&](int off, int krows, int tiles) { add_call(&sm->calls, n, off, 0, krows, tiles); };
     for (int l = 0; l < nE; ++l) add(rd.offW[l], l == 0 ? rd.emb_rows : 6 * rd.te[l - 1] + (l == rd.skip ? rd.emb_rows : 0), rd.te[l]);
     for (int k = k_lo; k < k_hi; ++k) { add(rd.offW0[k], 6 * ZT + 6 * rd.zx_tiles, rd.t0[k]); add(rd.offW1[k], 6 * rd.t0[k], rd.t1[k]); }
-    sm->n_calls = n;
+    sm->calls.n_calls = n;
   }
   __syncthreads();
   REFL_STREAM();
@@ -302,7 +251,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
           const int f = step_feat(sl, h, jj);
           x[jj] = (sl < rd.emb_rows / 3 && f < rd.emb_feats) ? posenc_feat(f, xs, ys, zs) : 0.f;
         }
-        if (live_w && wr_shared && tp.save) tf_store_step(tp.E, ptile_w, rd.e_tiles, sl, lane, x);
+        if (live_w && wr_shared && tp.save) tfmt_store_step(tp.E, ptile_w, rd.e_tiles, sl, lane, x);
         if (sl < rd.emb_rows / 3) {
           f32x4 q0, q1, q2;
           split3x8(x, q0, q1, q2);
@@ -325,7 +274,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
             act_apply(act, acc, v);
             const long ptile = ptile_of(unit, im);
             if (ptile < n_tiles && wr_shared) {
-              if (tp.save || top) tf_store_acc(t_y, ptile, n_ot, ot, lane, v);
+              if (tp.save || top) tfmt_store_acc(t_y, ptile, n_ot, ot, lane, v);
               if (top && tp.ZROWS != nullptr) {
                 const long pt = (ptile << 5) + p;
                 if (pt < P) {
@@ -355,7 +304,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
 #pragma unroll
           for (int jj = 0; jj < 8; ++jj) x[jj] = 0.f;
         }
-        if (live_w && wr_shared) tf_store_step(tp.ZT, ptile_w, ZT, sl, lane, x);
+        if (live_w && wr_shared) tfmt_store_step(tp.ZT, ptile_w, ZT, sl, lane, x);
         f32x4 q0, q1, q2;
         split3x8(x, q0, q1, q2);
         ldsi[(X0 + 3 * sl) * 64 + lane] = q0; ldsi[(X0 + 3 * sl + 1) * 64 + lane] = q1; ldsi[(X0 + 3 * sl + 2) * 64 + lane] = q2;
@@ -380,7 +329,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
 #pragma unroll
           for (int jj = 0; jj < 8; ++jj) x[jj] = 0.f;
         }
-        if (live_w && wr_shared && tp.ZXT != nullptr) tf_store_step(tp.ZXT, ptile_w, ZXT, sl, lane, x);
+        if (live_w && wr_shared && tp.ZXT != nullptr) tfmt_store_step(tp.ZXT, ptile_w, ZXT, sl, lane, x);
         f32x4 q0, q1, q2;
         split3x8(x, q0, q1, q2);
         ldsi[(X1 + 3 * sl) * 64 + lane] = q0; ldsi[(X1 + 3 * sl + 1) * 64 + lane] = q1; ldsi[(X1 + 3 * sl + 2) * 64 + lane] = q2;
@@ -416,7 +365,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
         owned(ZT, [&](int ot, int im, auto) __attribute__((always_inline)) {
           float v[16];
           const long ptile = ptile_of(unit, im);
-          if (ptile < n_tiles) tf_load_acc(tp.ZT, ptile, ZT, ot, lane, v);
+          if (ptile < n_tiles) tfmt_load_acc(tp.ZT, ptile, ZT, ot, lane, v);
           else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = 0.f;
@@ -436,7 +385,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
             float v[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = fmaxf(acc[i], 0.f);
-            if (tp.save && ptile_of(unit, im) < n_tiles) tf_store_acc(t_y, ptile_of(unit, im), n_ot, ot, lane, v);
+            if (tp.save && ptile_of(unit, im) < n_tiles) tfmt_store_acc(t_y, ptile_of(unit, im), n_ot, ot, lane, v);
             store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
           });
       }
@@ -451,7 +400,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_fwd_x3_kern
             float v[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = fmaxf(acc[i], 0.f);
-            if (tp.save && ptile_of(unit, im) < n_tiles) tf_store_acc(t_y, ptile_of(unit, im), n_ot, ot, lane, v);
+            if (tp.save && ptile_of(unit, im) < n_tiles) tfmt_store_acc(t_y, ptile_of(unit, im), n_ot, ot, lane, v);
             store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
           });
       }
@@ -487,11 +436,11 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
   f32x4* save0 = scratch + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NIMG * per_img;
   if (tid == 0) {
     int n = 0;
-    auto add = [&](int off, int krows, int tiles) { sm->tab[4 * n] = off; sm->tab[4 * n + 1] = blocks_of(krows); sm->tab[4 * n + 2] = tiles; sm->tab[4 * n + 3] = 0; ++n; };
+    auto add = [&](int off, int krows, int tiles) { add_call(&sm->calls, n, off, 0, krows, tiles); };
     if (heads)
       for (int k = k_lo; k < k_hi; ++k) { add(rd.offW1b[k], 6 * rd.t1[k], rd.t0[k]); add(rd.offW0b[k], 6 * rd.t0[k], ZT); }
     for (int l = nE - 1; l >= 1; --l) add(rd.offWb[l], 6 * rd.te[l], rd.te[l - 1]);
-    sm->n_calls = n;
+    sm->calls.n_calls = n;
   }
   __syncthreads();
   REFL_STREAM();
@@ -525,9 +474,9 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
       if (nE > 0) {
         if (ptile < n_tiles) {
           float y[16];
-          tf_load_acc(tp.Y[nE - 1], ptile, ZT, ot, lane, y);
+          tfmt_load_acc(tp.Y[nE - 1], ptile, ZT, ot, lane, y);
           dact_mul(rd.act[nE - 1], y, v);
-          tf_store_acc(tp.D[nE - 1], ptile, ZT, ot, lane, v);
+          tfmt_store_acc(tp.D[nE - 1], ptile, ZT, ot, lane, v);
         }
         store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
       } else if (valid) {
@@ -587,14 +536,14 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
         rank_c(wf + rd.offA2y[k], T1, ot, im, acc);
         float v[16], y[16];
         const long ptile = ptile_of(unit, im);
-        if (ptile < n_tiles) tf_load_acc(tp.H1[k], ptile, T1, ot, lane, y);
+        if (ptile < n_tiles) tfmt_load_acc(tp.H1[k], ptile, T1, ot, lane, y);
         else {
 #pragma unroll
           for (int i = 0; i < 16; ++i) y[i] = 0.f;
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) v[i] = y[i] > 0.f ? acc[i] : 0.f;
-        if (ptile < n_tiles) tf_store_acc(tp.D1[k], ptile, T1, ot, lane, v);
+        if (ptile < n_tiles) tfmt_store_acc(tp.D1[k], ptile, T1, ot, lane, v);
         store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
       });
       __syncthreads();
@@ -607,7 +556,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
           [&](int ot, int im, auto slc_, f32x16& acc) __attribute__((always_inline)) {
             constexpr int sl_ = decltype(slc_)::value; (void)sl_;
             if (sl_ == 0) RT_STAMP(3)
-            if (ptile_of(unit, im) < n_tiles) tf_load_acc(t_y, ptile_of(unit, im), T0, ot, lane, au[sl_]);
+            if (ptile_of(unit, im) < n_tiles) tfmt_load_acc(t_y, ptile_of(unit, im), T0, ot, lane, au[sl_]);
             else {
 #pragma unroll
               for (int i = 0; i < 16; ++i) au[sl_][i] = 0.f;
@@ -621,7 +570,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
             float v[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = au[sl_][i] > 0.f ? acc[i] : 0.f;
-            if (ptile_of(unit, im) < n_tiles) tf_store_acc(t_d, ptile_of(unit, im), T0, ot, lane, v);
+            if (ptile_of(unit, im) < n_tiles) tfmt_store_acc(t_d, ptile_of(unit, im), T0, ot, lane, v);
             store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
             RT_STAMP(6)
           });
@@ -683,7 +632,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
         [&](int ot, int im, auto slc_, f32x16& acc) __attribute__((always_inline)) {
             constexpr int sl_ = decltype(slc_)::value; (void)sl_;
           if (sl_ == 0) RT_STAMP(3)
-          if (ptile_of(unit, im) < n_tiles) tf_load_acc(t_y, ptile_of(unit, im), n_ot, ot, lane, au[sl_]);
+          if (ptile_of(unit, im) < n_tiles) tfmt_load_acc(t_y, ptile_of(unit, im), n_ot, ot, lane, au[sl_]);
           else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) au[sl_][i] = 0.f;
@@ -698,7 +647,7 @@ __global__ __launch_bounds__(512, RT_WAVES_EU(NIMG)) void refl_train_bwd_x3_kern
 #pragma unroll
           for (int i = 0; i < 16; ++i) v[i] = acc[i];
           dact_mul(act, au[sl_], v);
-          if (ptile_of(unit, im) < n_tiles) tf_store_acc(t_d, ptile_of(unit, im), n_ot, ot, lane, v);
+          if (ptile_of(unit, im) < n_tiles) tfmt_store_acc(t_d, ptile_of(unit, im), n_ot, ot, lane, v);
           store_tile_x3(lds + (size_t)im * IS, X0 + 6 * ot, lane, v);
           RT_STAMP(6)
         });

@@ -155,9 +155,6 @@ extern "C" int vqn_reduce_partials(const float* ws, int n, int rows, int cols, f
   return VQN_OK;
 }
 
-int vqn_wgrad_partials_f32_internal(const float* A, int a_tiles, int a_t0, int a_nt, const float* B, int b_tiles, int b_t0, int b_nt,
-                                    int64_t n_point_tiles, int n_split, float* ws, float* rowsum_ws, void* stream);      // below
-
 extern "C" int vqn_wgrad_partials(const float* A, int a_tiles, int a_t0, int a_nt, const float* B, int b_tiles, int b_t0,
                                   int b_nt, int64_t n_point_tiles, int n_split, float* ws, float* rowsum_ws, void* stream) {
   return vqn_wgrad_partials_f32_internal(A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws, rowsum_ws, stream);
@@ -165,19 +162,17 @@ extern "C" int vqn_wgrad_partials(const float* A, int a_tiles, int a_t0, int a_n
 
 int vqn_wgrad_partials_f32_internal(const float* A, int a_tiles, int a_t0, int a_nt, const float* B, int b_tiles, int b_t0, int b_nt,
                                     int64_t n_point_tiles, int n_split, float* ws, float* rowsum_ws, void* stream) {
-  VQN_CHECK_ARG(A && B && ws, "null pointer");
-  VQN_CHECK_ARG(n_point_tiles >= 1 && n_split >= 1, "n_point_tiles >= 1, n_split >= 1");
-  VQN_CHECK_SHAPE(a_nt >= 1 && a_nt <= 8 && b_nt >= 1 && b_nt <= 8, "1..8 feature tiles per operand and call");
-  VQN_CHECK_SHAPE(a_t0 >= 0 && a_t0 + a_nt <= a_tiles && b_t0 >= 0 && b_t0 + b_nt <= b_tiles, "feature-tile range outside the tensor");
-  VQN_CHECK_SHAPE(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "operands must be 16-byte aligned");
+  const int rc = wgrad_check_problem(__func__, false, A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws);
+  if (rc != VQN_OK) return rc;
   long grid = n_split;
   if (grid > n_point_tiles) grid = n_point_tiles;
   hipStream_t s = (hipStream_t)stream;
 #define VQN_WGRAD(NOT_, BT_, D_)                                                                                       \
   hipLaunchKernelGGL((wgrad_kernel<NOT_, BT_, D_>), dim3((unsigned)grid), dim3(256), 0, s, A, a_tiles, a_t0, a_nt, B, \
                      b_tiles, b_t0, b_nt, (long)n_point_tiles, ws, rowsum_ws)
-  if (a_nt <= 4 && b_nt <= 4) VQN_WGRAD(1, 4, 6);
-  else if (a_nt <= 4) VQN_WGRAD(1, 8, 4);
+  const int cls = wgrad_class(a_nt, b_nt, 0, (long)n_point_tiles);
+  if (cls == 0) VQN_WGRAD(1, 4, 6);
+  else if (cls == 1) VQN_WGRAD(1, 8, 4);
   else VQN_WGRAD(2, 8, VQN_WGRAD_D);
 #undef VQN_WGRAD
   VQN_LAUNCH_CHECK();

@@ -9,11 +9,7 @@
 // (deterministic: fixed order, no atomics).
 #include "common.h"
 #include "wgrad_batch.h"
-#include <stdlib.h>
 #include <type_traits>
-
-int vqn_wgrad_partials_f32_internal(const float* A, int a_tiles, int a_t0, int a_nt, const float* B, int b_tiles, int b_t0, int b_nt,
-                                    int64_t n_point_tiles, int n_split, float* ws, float* rowsum_ws, void* stream);
 
 namespace {
 
@@ -51,104 +47,6 @@ __device__ __forceinline__ void split3(const f32x4 lo4, const f32x4 hi4, Pieces&
 
 __device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// wave w owns output tiles (w, w + 4) x (0..7); step q = (point tile, half u): 16 points
-template <bool FULL>          // FULL: a_nt == b_nt == 8 -- no guards in the instruction stream
-__global__ __launch_bounds__(256, 1) void wgrad_x3_kernel(const float* __restrict__ A, int a_tiles, int a_t0, int a_nt,
-                                                          const float* __restrict__ B, int b_tiles, int b_t0, int b_nt,
-                                                          long n_ptiles, float* __restrict__ ws, float* __restrict__ rowsum_ws) {
-  constexpr int NOT = 2, BT = 8;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int fi = lane & 31, kk = lane >> 5;
-  f32x16 acc[NOT][BT];
-#pragma unroll
-  for (int a = 0; a < NOT; ++a)
-#pragma unroll
-    for (int b = 0; b < BT; ++b)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-  f32x4 rs[NOT];
-#pragma unroll
-  for (int a = 0; a < NOT; ++a) rs[a] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const long my_tiles = (n_ptiles - blockIdx.x + gridDim.x - 1) / gridDim.x, n_q = 2 * my_tiles;
-  // unconditional clamped fetches, one step ahead (two register buffers): see wgrad.hip
-  auto fetch = [&](long q, f32x4 (&af)[NOT][2], f32x4 (&bf)[BT][2]) {
-    long t = blockIdx.x + (q >> 1) * (long)gridDim.x;
-    if (t >= n_ptiles) t = n_ptiles - 1;
-    const int u = (int)(q & 1);
-    const float* At = A + ((t * a_tiles + a_t0) * 32 + fi) * 32 + 8 * kk + 16 * u;
-    const float* Bt = B + ((t * b_tiles + b_t0) * 32 + fi) * 32 + 8 * kk + 16 * u;
-#pragma unroll
-    for (int a = 0; a < NOT; ++a) {
-      const float* p = At + (long)min(wave + 4 * a, a_nt - 1) * 1024;
-      af[a][0] = *reinterpret_cast<const f32x4*>(p);
-      af[a][1] = *reinterpret_cast<const f32x4*>(p + 4);
-    }
-#pragma unroll
-    for (int b = 0; b < BT; ++b) {
-      const float* p = Bt + (long)min(b, b_nt - 1) * 1024;
-      bf[b][0] = *reinterpret_cast<const f32x4*>(p);
-      bf[b][1] = *reinterpret_cast<const f32x4*>(p + 4);
-    }
-  };
-  auto multiply = [&](const f32x4 (&af)[NOT][2], const f32x4 (&bf)[BT][2]) {
-    Pieces pa[NOT];
-#pragma unroll
-    for (int a = 0; a < NOT; ++a) {
-      rs[a] += af[a][0] + af[a][1];
-      split3(af[a][0], af[a][1], pa[a]);
-    }
-#pragma unroll
-    for (int b = 0; b < BT; ++b) {
-      if (!FULL && b >= b_nt) continue;
-      Pieces pb;
-      split3(bf[b][0], bf[b][1], pb);
-#pragma unroll
-      for (int a = 0; a < NOT; ++a)
-        if (FULL || wave + 4 * a < a_nt) {
-          f32x16 c = acc[a][b];
-          c = mma(pa[a].p2, pb.p0, c);            // smallest terms first
-          c = mma(pa[a].p1, pb.p1, c);
-          c = mma(pa[a].p0, pb.p2, c);
-          c = mma(pa[a].p1, pb.p0, c);
-          c = mma(pa[a].p0, pb.p1, c);
-          c = mma(pa[a].p0, pb.p0, c);
-          acc[a][b] = c;
-        }
-    }
-  };
-  f32x4 af[2][NOT][2], bf[2][BT][2];
-  fetch(0, af[0], bf[0]);
-  for (long q = 0; q < n_q; q += 2) {
-    fetch(q + 1, af[1], bf[1]);
-    multiply(af[0], bf[0]);
-    fetch(q + 2, af[0], bf[0]);
-    if (q + 1 < n_q) multiply(af[1], bf[1]);
-  }
-  const int cols = b_nt * 32;
-  float* w = ws + (size_t)blockIdx.x * (size_t)(a_nt * 32) * cols;
-#pragma unroll
-  for (int a = 0; a < NOT; ++a) {
-    const int ot = wave + 4 * a;
-    if (ot >= a_nt) continue;
-#pragma unroll
-    for (int b = 0; b < BT; ++b) {
-      if (b >= b_nt) continue;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * kk;
-        w[(size_t)(ot * 32 + row) * cols + b * 32 + fi] = acc[a][b][e];
-      }
-    }
-    if (rowsum_ws != nullptr) {
-      float r = (rs[a][0] + rs[a][1]) + (rs[a][2] + rs[a][3]);
-      r += __shfl_xor(r, 32);
-      if (kk == 0) rowsum_ws[(size_t)blockIdx.x * (a_nt * 32) + ot * 32 + fi] = r;
-    }
-  }
 }
 
 // The 256 x 256 form with the B operand cut into pieces ONCE per workgroup: wave w fetches and splits B tiles 2 w and 2 w + 1 of
@@ -380,9 +278,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_lds_batched_narrow_kernel(con
 
 }  // namespace
 
-extern "C" int vqn_wgrad_partials_x3(const float* A, int a_tiles, int a_t0, int a_nt, const float* B, int b_tiles, int b_t0,
-                                     int b_nt, int64_t n_point_tiles, int n_split, float* ws, float* rowsum_ws, void* stream);
-
 // The contractions of a whole backward pass (same points, hence the same split) in as few launches as they have kernel shapes:
 // problem i is vqn_wgrad_partials (x3 == 0) / vqn_wgrad_partials_x3 (x3 != 0) of (A[i], a_tiles[i], ..., ws[i], rowsum_ws[i]) -- the
 // same kernels, hence the same partial blocks bit for bit -- grouped by kernel variant, a launch per group of up to 24.
@@ -393,10 +288,7 @@ extern "C" int vqn_wgrad_partials_batched(int count, const float* const* A, cons
   VQN_CHECK_ARG(n_point_tiles >= 1 && n_split >= 1, "n_point_tiles >= 1, n_split >= 1");
   long grid = n_split;
   if (grid > n_point_tiles) grid = n_point_tiles;
-  static const long small_from = [] { const char* e = getenv("VQN_WGRAD_X3_SMALL_TILES"); return (e && e[0]) ? atol(e) : 1024L; }();
-  static const int no_lds = [] { const char* e = getenv("VQN_WGRAD_X3_NO_LDS"); return (e != nullptr && atoi(e) != 0) ? 1 : 0; }();
-  // classes 0..2: the f32 kernels by shape; 3 / 4 / 5: the x3 LDS kernel, full / guarded / guarded with at most four A tiles
-  static const int no_narrow = [] { const char* e = getenv("VQN_WGRAD_X3_NO_NARROW"); return (e != nullptr && atoi(e) != 0) ? 1 : 0; }();
+  // problems by kernel class (wgrad_class, wgrad_batch.h), a launch per WG_MAX of a class
   WgProblem cls[6][WG_MAX];
   int n_cls[6] = {0, 0, 0, 0, 0, 0};
   auto flush = [&](int c) -> int {
@@ -417,18 +309,10 @@ extern "C" int vqn_wgrad_partials_batched(int count, const float* const* A, cons
     return rc;
   };
   for (int i = 0; i < count; ++i) {
-    VQN_CHECK_ARG(A[i] && B[i] && ws[i], "null pointer in problem");
-    VQN_CHECK_SHAPE(a_nt[i] >= 1 && a_nt[i] <= 8 && b_nt[i] >= 1 && b_nt[i] <= 8, "1..8 feature tiles per operand and problem");
-    VQN_CHECK_SHAPE(a_t0[i] >= 0 && a_t0[i] + a_nt[i] <= a_tiles[i] && b_t0[i] >= 0 && b_t0[i] + b_nt[i] <= b_tiles[i], "feature-tile range outside the tensor");
-    VQN_CHECK_SHAPE(((uintptr_t)A[i] & 15) == 0 && ((uintptr_t)B[i] & 15) == 0, "operands must be 16-byte aligned");
-    const bool f32 = !x3 || (a_nt[i] <= 4 && n_point_tiles < small_from);
-    if (!f32 && no_lds) {                                   // (diagnostic switch: the non-LDS x3 kernels have no batched form)
-      const int n = vqn_wgrad_partials_x3(A[i], a_tiles[i], a_t0[i], a_nt[i], B[i], b_tiles[i], b_t0[i], b_nt[i], n_point_tiles, n_split, ws[i],
-                                          rowsum_ws[i], stream);
-      if (n < 0) return n;
-      continue;
-    }
-    const int c = f32 ? ((a_nt[i] <= 4 && b_nt[i] <= 4) ? 0 : (a_nt[i] <= 4 ? 1 : 2)) : ((a_nt[i] == 8 && b_nt[i] == 8) ? 3 : ((a_nt[i] <= 4 && !no_narrow) ? 5 : 4));
+    const int rc = wgrad_check_problem(__func__, true, A[i], a_tiles[i], a_t0[i], a_nt[i], B[i], b_tiles[i], b_t0[i], b_nt[i], n_point_tiles,
+                                       n_split, ws[i]);
+    if (rc != VQN_OK) return rc;
+    const int c = wgrad_class(a_nt[i], b_nt[i], x3, (long)n_point_tiles);
     cls[c][n_cls[c]++] = WgProblem{A[i], B[i], ws[i], rowsum_ws[i], a_tiles[i], a_t0[i], a_nt[i], b_tiles[i], b_t0[i], b_nt[i]};
     if (n_cls[c] == WG_MAX) { const int rc = flush(c); if (rc != VQN_OK) return rc; }
   }
@@ -438,31 +322,17 @@ extern "C" int vqn_wgrad_partials_batched(int count, const float* const* A, cons
 
 extern "C" int vqn_wgrad_partials_x3(const float* A, int a_tiles, int a_t0, int a_nt, const float* B, int b_tiles, int b_t0,
                                      int b_nt, int64_t n_point_tiles, int n_split, float* ws, float* rowsum_ws, void* stream) {
-  VQN_CHECK_ARG(A && B && ws, "null pointer");
-  VQN_CHECK_ARG(n_point_tiles >= 1 && n_split >= 1, "n_point_tiles >= 1, n_split >= 1");
-  VQN_CHECK_SHAPE(a_nt >= 1 && a_nt <= 8 && b_nt >= 1 && b_nt <= 8, "1..8 feature tiles per operand and call");
-  VQN_CHECK_SHAPE(a_t0 >= 0 && a_t0 + a_nt <= a_tiles && b_t0 >= 0 && b_t0 + b_nt <= b_tiles, "feature-tile range outside the tensor");
-  VQN_CHECK_SHAPE(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "operands must be 16-byte aligned");
-  // small blocks (<= 128 output features) at the reference batch (64 point tiles) are latency-, not matrix-bound: the f32 kernels with
-  // their deeper rings -- no difference measured there (6.50 vs 6.52 ms per 2048-point step).  From 1024 point tiles on they take the
-  // x3 kernel too: 262,144-point reflectance step 22.9 -> 22.0 ms (A / B / A on one box).  VQN_WGRAD_X3_SMALL_TILES=<n> moves the switch.
-  static const long small_from = [] { const char* e = getenv("VQN_WGRAD_X3_SMALL_TILES"); return (e && e[0]) ? atol(e) : 1024L; }();
-  if (a_nt <= 4 && n_point_tiles < small_from)
-    return vqn_wgrad_partials_f32_internal(A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws, rowsum_ws, stream);
+  const int rc = wgrad_check_problem(__func__, false, A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws);
+  if (rc != VQN_OK) return rc;
+  const int cls = wgrad_class(a_nt, b_nt, 1, (long)n_point_tiles);
+  if (cls < 3) return vqn_wgrad_partials_f32_internal(A, a_tiles, a_t0, a_nt, B, b_tiles, b_t0, b_nt, n_point_tiles, n_split, ws, rowsum_ws, stream);
   long grid = n_split;
   if (grid > n_point_tiles) grid = n_point_tiles;
-  static const int no_lds = [] { const char* e = getenv("VQN_WGRAD_X3_NO_LDS"); return (e != nullptr && atoi(e) != 0) ? 1 : 0; }();
-  if (a_nt == 8 && b_nt == 8 && !no_lds)
+  if (cls == 3)
     hipLaunchKernelGGL(wgrad_x3_lds_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, A, a_tiles, a_t0, a_nt, B, b_tiles,
                        b_t0, b_nt, (long)n_point_tiles, ws, rowsum_ws);
-  else if (!no_lds)
+  else                                                      // (class 5 too: there is no single-problem narrow kernel)
     hipLaunchKernelGGL(wgrad_x3_lds_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, A, a_tiles, a_t0, a_nt, B, b_tiles,
-                       b_t0, b_nt, (long)n_point_tiles, ws, rowsum_ws);
-  else if (a_nt == 8 && b_nt == 8)
-    hipLaunchKernelGGL(wgrad_x3_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, A, a_tiles, a_t0, a_nt, B, b_tiles,
-                       b_t0, b_nt, (long)n_point_tiles, ws, rowsum_ws);
-  else
-    hipLaunchKernelGGL(wgrad_x3_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, A, a_tiles, a_t0, a_nt, B, b_tiles,
                        b_t0, b_nt, (long)n_point_tiles, ws, rowsum_ws);
   VQN_LAUNCH_CHECK();
   return (int)grid;
