@@ -461,7 +461,10 @@ int vqn_neus_composite_bwd(const float* rays_o, const float* rays_d, const float
  * sweep, SDF tangent pass + reverse sweep with second-order source terms.
  *   desc_dev / desc_host: the same descriptor in device and host memory (the host copy is validated);
  *   tensors[i] / tensor_ld[i]: device pointers and leading dims (VEC: row stride, TFMT: feature tiles; negative: see
- *   vqn_tile_program_grid). */
+ *   vqn_tile_program_grid).
+ * The host descriptor is checked against the row budget, the tensor table and the per-op contracts of vqn_vm_desc.h (store
+ * sizes, VEC widths, feature offsets, no GEMM dst over its K rows with several output tiles) before anything is launched:
+ * VQN_ESHAPE, nothing written. */
 int vqn_tile_program(const void* desc_dev, const int32_t* desc_host, const float* wbuf, float* const* tensors,
                      const int32_t* tensor_ld, int n_tensors, int64_t N, void* stream);
 /* Number of workgroups vqn_tile_program launches for this program and N points.  A tensor passed with a NEGATIVE tensor_ld

@@ -479,6 +479,11 @@ extern "C" int vqn_tile_program(const void* desc_dev, const int32_t* desc_host, 
     const VmOp& op = d->ops[i];
     auto row_ok = [&](int r0, int n) { return r0 >= 0 && n >= 0 && r0 + n <= d->total_rows; };
     auto t_ok = [&](int t, bool optional) { return (optional && t < 0) || (t >= 0 && t < n_tensors && tensors[t] != nullptr); };
+    // a VEC input the op reads three components of; a TFMT store that must hold the `rows` 8-feature rows the op writes
+    auto vec3_ok = [&](int t, bool optional) { return t_ok(t, optional) && (t < 0 || tensor_ld[t] >= 3); };
+    auto st_ok = [&](int t, int rows) { return t_ok(t, true) && (t < 0 || tensor_ld[t] * 4 >= rows); };
+    // rows [a0, a0 + an) and [b0, b0 + bn) share a row
+    auto overlap = [&](int a0, int an, int b0, int bn) { return an > 0 && bn > 0 && a0 < b0 + bn && b0 < a0 + an; };
     bool ok = true;
     switch (op.kind) {
       case VM_GEMM:
@@ -489,14 +494,37 @@ extern "C" int vqn_tile_program(const void* desc_dev, const int32_t* desc_host, 
              (!op.p[14] || op.p[7] >= 0);
         for (int k = 10; ok && k <= 13; ++k)
           if (op.p[k] >= 0) ok = tensor_ld[op.p[k]] >= op.p[0];
+        // a wave writes its first tile into dst while the other waves still read K: with more than one output tile dst must not
+        // share a row with either K segment
+        if (ok && op.p[7] >= 0 && op.p[0] > 1)
+          ok = !overlap(op.p[7], 4 * op.p[0], op.p[1], op.p[2]) && !overlap(op.p[7], 4 * op.p[0], op.p[3], op.p[4]);
         break;
-      case VM_LD_POSENC: ok = t_ok(op.p[0], false) && row_ok(op.p[1], (op.p[3] + 7) / 8) && op.p[3] == 3 + 6 * op.p[2] && t_ok(op.p[4], true); break;
-      case VM_LD_POSENC_JVP: ok = t_ok(op.p[0], false) && t_ok(op.p[1], false) && row_ok(op.p[2], (op.p[4] + 7) / 8) && op.p[4] == 3 + 6 * op.p[3] && t_ok(op.p[5], true); break;
+      case VM_LD_POSENC:
+        ok = vec3_ok(op.p[0], false) && op.p[2] >= 0 && op.p[3] == 3 + 6 * op.p[2] && row_ok(op.p[1], (op.p[3] + 7) / 8) &&
+             st_ok(op.p[4], (op.p[3] + 7) / 8);
+        break;
+      case VM_LD_POSENC_JVP:
+        ok = vec3_ok(op.p[0], false) && vec3_ok(op.p[1], false) && op.p[3] >= 0 && op.p[4] == 3 + 6 * op.p[3] &&
+             row_ok(op.p[2], (op.p[4] + 7) / 8) && st_ok(op.p[5], (op.p[4] + 7) / 8);
+        break;
       case VM_LD_T: ok = t_ok(op.p[0], false) && row_ok(op.p[1], op.p[2]) && tensor_ld[op.p[0]] * 4 >= op.p[2]; break;
-      case VM_LD_VEC: ok = t_ok(op.p[0], false) && op.p[2] >= 1 && op.p[2] <= 8 && op.p[5] >= 0 && row_ok(op.p[1], (op.p[5] + op.p[2] + 7) / 8) && t_ok(op.p[4], true) && tensor_ld[op.p[0]] >= op.p[2]; break;
-      case VM_LD_EXTRAS: ok = t_ok(op.p[0], false) && t_ok(op.p[1], false) && t_ok(op.p[2], true) && row_ok(op.p[3], (op.p[6] + 7) / 8) && t_ok(op.p[5], true); break;
-      case VM_ST_VEC: ok = row_ok(op.p[0], (op.p[1] + op.p[2] + 7) / 8) && op.p[2] >= 1 && op.p[2] <= 4 && t_ok(op.p[3], false) && tensor_ld[op.p[3]] >= op.p[2]; break;
-      case VM_POSENC_VJP: ok = row_ok(op.p[0], (3 + 6 * op.p[3] + 7) / 8) && t_ok(op.p[1], false) && t_ok(op.p[2], false) && tensor_ld[op.p[2]] >= 3; break;
+      case VM_LD_VEC:
+        ok = t_ok(op.p[0], false) && op.p[2] >= 1 && op.p[2] <= 8 && op.p[5] >= 0 && row_ok(op.p[1], (op.p[5] + op.p[2] + 7) / 8) &&
+             st_ok(op.p[4], (op.p[5] + op.p[2] + 7) / 8) && tensor_ld[op.p[0]] >= op.p[2];
+        break;
+      case VM_LD_EXTRAS:
+        ok = vec3_ok(op.p[0], false) && vec3_ok(op.p[1], false) && vec3_ok(op.p[2], true) && op.p[4] >= 0 &&
+             op.p[6] == 3 + (op.p[4] > 0 ? 3 + 6 * op.p[4] : 0) + (op.p[2] >= 0 ? 3 : 0) && row_ok(op.p[3], (op.p[6] + 7) / 8) &&
+             st_ok(op.p[5], (op.p[6] + 7) / 8);
+        break;
+      case VM_ST_VEC:
+        ok = op.p[1] >= 0 && op.p[2] >= 1 && op.p[2] <= 4 && row_ok(op.p[0], (op.p[1] + op.p[2] + 7) / 8) && t_ok(op.p[3], false) &&
+             tensor_ld[op.p[3]] >= op.p[2];
+        break;
+      case VM_POSENC_VJP:
+        ok = op.p[3] >= 0 && row_ok(op.p[0], (3 + 6 * op.p[3] + 7) / 8) && vec3_ok(op.p[1], false) && t_ok(op.p[2], false) &&
+             tensor_ld[op.p[2]] >= 3;
+        break;
       default: ok = false;
     }
     if (!ok) {
