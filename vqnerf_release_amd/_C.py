@@ -49,7 +49,7 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift, the material edit), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift, the material edit, the JPEG encoder), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
             'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
@@ -59,7 +59,8 @@ ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': (
             'vqn_seg_scratch_bytes': ('l', 'lii'), 'vqn_seg_contingency_rgb': ('i', 'pppflpipiplpp'),
             'vqn_seg_contingency_labels': ('i', 'pppliiplpp'), 'vqn_meanshift_seek': ('i', 'plplidipppp'),
             'vqn_meanshift_merge_scratch_bytes': ('l', 'li'), 'vqn_meanshift_merge': ('i', 'pplidplppp'),
-            'vqn_meanshift_assign': ('i', 'plpiidppp'), 'vqn_material_select_edit': ('i', 'pppiplppipipfppppppppppppp')}
+            'vqn_meanshift_assign': ('i', 'plpiidppp'), 'vqn_material_select_edit': ('i', 'pppiplppipipfppppppppppppp'),
+            'vqn_jpeg_plan': ('i', 'llliilppi'), 'vqn_jpeg_encode': ('i', 'pllliilplplpip')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -964,6 +965,38 @@ MEANSHIFT_POINTS_PER_TILE = 256    # points the seek kernel stages in LDS per pa
 MEANSHIFT_SEEDS_PER_GROUP = 64     # seeds a seek workgroup owns (kSeekSeeds)
 MEANSHIFT_ASSIGN_SPAN = 256        # points an assign workgroup labels per pass (kAssignThreads)
 MEANSHIFT_ASSIGN_CENTRES = 512     # centres the assign kernel holds in LDS at a time (kAssignCentres)
+
+
+# --------------------------------------------------------------------------------------
+# baseline JPEG of device frames (csrc/jpeg_encode.hip, csrc/jpeg_plan.h; decomp/nerfactor/util/mjpeg.py)
+JPEG_GEOM = ('n', 'h', 'w', 'quality', 'sub', 'ri', 'mcu', 'mcus_x', 'mcus_y', 'blocks_per_mcu', 'intervals', 'slot_bytes', 'by_y', 'bx_y',
+             'by_c', 'bx_c', 'off_cb', 'off_cr', 'off_slots', 'off_lens', 'off_dst', 'scratch_bytes', 'out_bytes', 'header_bytes')
+
+
+def jpeg_plan(n, h, w, quality, subsampling, restart_interval):
+    """The planner's view of a batch (host only): ({name: int} over JPEG_GEOM, the header bytes SOI .. SOS).  subsampling 420 or 444.
+    A batch it refuses raises ValueError with its reason."""
+    geom = np.zeros(len(JPEG_GEOM), np.int64)
+    header = np.zeros(1024, np.uint8)
+    rc = lib().vqn_jpeg_plan(int(n), int(h), int(w), int(quality), int(subsampling), int(restart_interval), geom.ctypes.data,
+                             header.ctypes.data, header.size)
+    if rc != 0:
+        raise ValueError(lib().vqn_last_error().decode())
+    g = {k: int(v) for k, v in zip(JPEG_GEOM, geom)}
+    return g, header[:g['header_bytes']].tobytes()
+
+
+def jpeg_encode(frames, g, scratch, out=None, meta=None):
+    """frames uint8 [n, h, w, 3] contiguous device tensor, g the plan of its batch, scratch a uint8 device buffer of g['scratch_bytes']
+    (g['off_slots'] when out is None: the coefficients only).  Fills scratch (the coefficient planes first), out and meta int64 [n, 2];
+    no host read."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or tuple(frames.shape) != (g['n'], g['h'], g['w'], 3) or not frames.is_contiguous():
+        raise VqnError(f"jpeg_encode: expected a contiguous uint8 [{g['n']}, {g['h']}, {g['w']}, 3] tensor, got {frames.dtype} "
+                       f'{tuple(frames.shape)} contiguous={frames.is_contiguous()}')
+    require_device(frames, 'jpeg_encode')
+    only = out is None
+    _call('vqn_jpeg_encode', _ptr(frames), g['n'], g['h'], g['w'], g['quality'], g['sub'], g['ri'], _ptr(scratch), scratch.numel(),
+          _ptr(out), 0 if only else out.numel(), _ptr(meta), int(only))
 
 
 def _f64_rows(t, name, D=None):

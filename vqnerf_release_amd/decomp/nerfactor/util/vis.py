@@ -40,6 +40,33 @@ def alpha_blend(a, alpha, b):
     return a * alpha + b * (1.0 - alpha)
 
 
+def threshold_alpha(alpha, alpha_thres):
+    """the stricter compositing alpha of vis_batch (vq_nfr.py:1039-1042): values below the threshold become 0.  numpy or torch."""
+    if torch.is_tensor(alpha):
+        return torch.where(alpha < alpha_thres, torch.zeros_like(alpha), alpha)
+    alpha = alpha.copy()
+    alpha[alpha < alpha_thres] = 0
+    return alpha
+
+
+def composite_uint8(v, alpha, white_bg):
+    """The 8-bit image vis_batch writes for a colour entry: v [H,W,3] over the white or black background with alpha [H,W] (already
+    thresholded), clipped to [0, 1], times 255, truncated.  One statement for host arrays (`_write_view`) and device tensors
+    (decomp/video.py): the same f32 operations in the same order, so the PNG and the video frame hold the same bytes."""
+    if torch.is_tensor(v):
+        a = alpha[:, :, None]
+        bg = torch.ones_like(v) if white_bg else torch.zeros_like(v)
+        return (torch.clamp(v * a + bg * (1.0 - a), 0.0, 1.0) * 255.0).to(torch.uint8)
+    return to_uint8(alpha_blend(v, alpha, np.ones_like(v) if white_bg else np.zeros_like(v)))
+
+
+def relit_names(key, n_maps, probe_names, olat_names, olat_first_n):
+    """[(index, light name)] of the relit images vis_batch writes for `pred_rgb_probes` / `pred_rgb_olat` with n_maps conditions: every
+    probe; of the OLAT maps the top half of the light grid only (vq_nfr.py:1049-1057)"""
+    names = olat_names if key == 'pred_rgb_olat' else probe_names
+    return [(i, lname) for i, lname in enumerate(names[:n_maps]) if not (key == 'pred_rgb_olat' and i >= olat_first_n)]
+
+
 def psnr_uint8(a, b):
     mse = np.mean((a.astype(np.float64) / 255.0 - b.astype(np.float64) / 255.0) ** 2)
     return float('inf') if mse == 0 else float(10.0 * np.log10(1.0 / mse))
@@ -147,8 +174,7 @@ def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_
         event.synchronize()
     d = _shape_views(host, hw)
     os.makedirs(outdir, exist_ok=True)
-    alpha = d['gt_alpha'].copy()
-    alpha[alpha < alpha_thres] = 0                               # stricter compositing (vq_nfr.py:1039-1042)
+    alpha = threshold_alpha(d['gt_alpha'], alpha_thres)
     full_vis = full_vis_path is not None
     jobs, written = [], {}
 
@@ -160,15 +186,17 @@ def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_
     def over_bg(v):
         return alpha_blend(v, alpha, np.ones_like(v) if white_bg else np.zeros_like(v))
 
+    def png_over_bg(key, v):
+        img = composite_uint8(v, alpha, white_bg)
+        written[key] = img
+        jobs.append(pool_submit(write_png, os.path.join(outdir, key + '.png'), img))
+
     for k, v in d.items():
         if k in ('pred_rgb_olat', 'pred_rgb_probes'):
-            names = olat_names if k == 'pred_rgb_olat' else probe_names
-            for i, lname in enumerate(names[:v.shape[2]]):
-                if k == 'pred_rgb_olat' and i >= olat_first_n:   # top half of the light grid only (:1049-1057)
-                    break
-                png(k + '_' + lname, over_bg(v[:, :, i, :]))
+            for i, lname in relit_names(k, v.shape[2], probe_names, olat_names, olat_first_n):
+                png_over_bg(k + '_' + lname, v[:, :, i, :])
         elif k.endswith(('rgb', 'diff')):
-            png(k, over_bg(v))
+            png_over_bg(k, v)
         elif k.endswith(('albedo', 'spec', 'rough', 'ks', 'basecolor')):
             jobs.append(pool_submit(np.save, os.path.join(outdir, k + '.npy'), v))
             png(k, v)

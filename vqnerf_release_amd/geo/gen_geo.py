@@ -132,29 +132,50 @@ class GeoExtractor:
         the view range with no collective -- `--num_p / --p_i` in the reference (README.md:45-53), by default rank /
         world_size of the process group here.  Training views use the ground-truth mask for visibility (the decomp stage
         trains on it) and alpha_thres 0.5; validation views use the predicted mask at `alpha_thres`.  Returns the indices done."""
+        return self._extract(dataset, scene_out_dir, 'train_' if is_train else 'val_', resolution_level, num_p, p_i, no_vis,
+                             0.5 if is_train else alpha_thres, gt_mask=is_train, metadata=None, log=log)
+
+    @torch.no_grad()
+    def extract_video(self, videoset, scene_out_dir, resolution_level=1, num_p=None, p_i=None, no_vis=False, alpha_thres=0.5, log=None):
+        """The loop of the reference's geo/NeuS-ours2/gen_video.py:134-179 over a camera path (models/videoset.py): the files of
+        `save_view` into `scene_out_dir/test_{idx:03d}/`, plus `metadata.json` {focal, cx, cy, cam_transform_mat} (:165-169), which
+        is what decomp/nerfactor/datasets/video_nfr.py makes its rays from.  There is no ground truth along a path: visibility is
+        always computed on the predicted mask at `alpha_thres`.  Same split of the view range and the same skipping of finished
+        views as extract_views (a view counts as finished only with its metadata.json)."""
+        return self._extract(videoset, scene_out_dir, 'test_', resolution_level, num_p, p_i, no_vis, alpha_thres, gt_mask=False,
+                             metadata=videoset.metadata, log=log)
+
+    def _extract(self, dataset, scene_out_dir, prefix, resolution_level, num_p, p_i, no_vis, alpha_thres, gt_mask, metadata, log):
+        """views p_i * ceil(n / num_p) ... of `dataset` that are not finished yet -> their directories; gt_mask: visibility on the set's
+        own masks where it has them at the rendered size; metadata: idx -> the dict of the view's metadata.json, or None for no file"""
+        import json
         import math
         from vqnerf_release_amd import parallel
         if num_p is None:
             num_p, p_i = parallel.world_size(), parallel.rank()
         n = dataset.n_images
         p_step = math.ceil(n / num_p)
-        prefix = 'train_' if is_train else 'val_'
         done = []
         for idx in range(p_i * p_step, min(n, (p_i + 1) * p_step)):
             view_dir = os.path.join(scene_out_dir, prefix + '{i:03d}'.format(i=idx))
-            if self.check_finished(view_dir, no_vis=no_vis):
+            meta_path = os.path.join(view_dir, 'metadata.json')
+            if self.check_finished(view_dir, no_vis=no_vis) and (metadata is None or os.path.exists(meta_path)):
                 continue
+            if metadata is not None:
+                os.makedirs(view_dir, exist_ok=True)
+                with open(meta_path, 'w') as f:
+                    json.dump(metadata(idx), f)
             rays = dataset.gen_rays_at(idx, resolution_level=resolution_level)
             rays_o, rays_d = rays[0], rays[1]
             H, W, _ = rays_o.shape
             o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
             near, far = dataset.near_far_from_sphere(o, d)
-            geo = self.compute_geo(o, d, near, far, alpha_thres=0.5 if is_train else alpha_thres)
+            geo = self.compute_geo(o, d, near, far, alpha_thres=alpha_thres)
             lvis = None
             if not no_vis:
                 mask = geo['mask']
                 gt = getattr(dataset, 'masks', None)
-                if is_train and gt is not None and tuple(gt.shape[1:3]) == (H, W):
+                if gt_mask and gt is not None and tuple(gt.shape[1:3]) == (H, W):
                     mask = (gt[idx, :, :, :1].reshape(-1, 1) > 0).float().to(o.device)
                 lvis = self.compute_vis(geo['surf'], geo['normal'], mask)
             self.save_view(view_dir, H, W, geo, lvis)
