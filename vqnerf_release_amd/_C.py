@@ -49,7 +49,7 @@ i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppi
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
 ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift, the material edit, the JPEG encoder), in the same code
+# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift, the material edit, the JPEG and the PNG encoder), in the same code
 # (tests/test_neus_fold_binding.py holds them to that header)
 ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
             'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
@@ -60,7 +60,8 @@ ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': (
             'vqn_seg_contingency_labels': ('i', 'pppliiplpp'), 'vqn_meanshift_seek': ('i', 'plplidipppp'),
             'vqn_meanshift_merge_scratch_bytes': ('l', 'li'), 'vqn_meanshift_merge': ('i', 'pplidplppp'),
             'vqn_meanshift_assign': ('i', 'plpiidppp'), 'vqn_material_select_edit': ('i', 'pppiplppipipfppppppppppppp'),
-            'vqn_jpeg_plan': ('i', 'llliilppi'), 'vqn_jpeg_encode': ('i', 'pllliilplplpip')}
+            'vqn_jpeg_plan': ('i', 'llliilppi'), 'vqn_jpeg_encode': ('i', 'pllliilplplpip'),
+            'vqn_png_plan': ('i', 'llllilppi'), 'vqn_png_encode': ('i', 'pllllilplplpip')}
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -997,6 +998,38 @@ def jpeg_encode(frames, g, scratch, out=None, meta=None):
     only = out is None
     _call('vqn_jpeg_encode', _ptr(frames), g['n'], g['h'], g['w'], g['quality'], g['sub'], g['ri'], _ptr(scratch), scratch.numel(),
           _ptr(out), 0 if only else out.numel(), _ptr(meta), int(only))
+
+
+# PNG files of device images (csrc/png_encode.hip, csrc/png_plan.h; decomp/nerfactor/util/png.py)
+PNG_GEOM = ('n', 'h', 'w', 'c', 'filter_mode', 'rows_per_segment', 'stride', 'segments', 'segment_bytes', 'slot_bytes', 'off_slots',
+            'off_lens', 'off_adler', 'off_dst', 'off_sums', 'scratch_bytes', 'out_bytes')
+PNG_FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': 5}
+PNG_SEGMENT_TARGET = 8192          # bytes a default segment holds at most, in whole rows (kPngSegmentTarget)
+
+
+def png_plan(n, h, w, c, filter_mode, rows_per_segment):
+    """The planner's view of a batch (host only): ({name: int} over PNG_GEOM, the 33 bytes of a file in front of IDAT).  filter_mode:
+    a value of PNG_FILTERS.  A batch it refuses raises ValueError with its reason."""
+    geom = np.zeros(len(PNG_GEOM), np.int64)
+    head = np.zeros(33, np.uint8)
+    rc = lib().vqn_png_plan(int(n), int(h), int(w), int(c), int(filter_mode), int(rows_per_segment), geom.ctypes.data, head.ctypes.data,
+                            head.size)
+    if rc != 0:
+        raise ValueError(lib().vqn_last_error().decode())
+    return {k: int(v) for k, v in zip(PNG_GEOM, geom)}, head.tobytes()
+
+
+def png_encode(images, g, scratch, out=None, meta=None):
+    """images uint8 [n, h, w, c] contiguous device tensor, g the plan of its batch, scratch a uint8 device buffer of g['scratch_bytes']
+    (n h stride when out is None: the filtered stream only).  Fills scratch (the filtered stream first), out and meta int64 [n, 2];
+    no host read."""
+    if images.dtype != torch.uint8 or tuple(images.shape) != (g['n'], g['h'], g['w'], g['c']) or not images.is_contiguous():
+        raise VqnError(f"png_encode: expected a contiguous uint8 [{g['n']}, {g['h']}, {g['w']}, {g['c']}] tensor, got {images.dtype} "
+                       f'{tuple(images.shape)} contiguous={images.is_contiguous()}')
+    require_device(images, 'png_encode')
+    only = out is None
+    _call('vqn_png_encode', _ptr(images), g['n'], g['h'], g['w'], g['c'], g['filter_mode'], g['rows_per_segment'], _ptr(scratch),
+          scratch.numel(), _ptr(out), 0 if only else out.numel(), _ptr(meta), int(only))
 
 
 def _f64_rows(t, name, D=None):

@@ -52,13 +52,14 @@ def _hw(to_vis):
 
 @torch.no_grad()
 def run(vq_model, dataset, outroot, selection, dst, ref_model=None, ref_dataset=None, opt_scale=None, relight_probes=True, dst_env=None,
-        name_fmt='batch{i:09d}', writer=None, num_p=None, p_i=None):
+        name_fmt='batch{i:09d}', writer=None, num_p=None, p_i=None, png='host'):
     """Every view of `dataset` (sharded as in train_nfr.render_views: process p_i of num_p takes views p_i, p_i + num_p, ...):
     vq_model.fast_render(edit_select=selection, edit_material=dst, opt_scale, relight_probes | dst_env) -> the mask and the edited
     stage-2 render; with ref_model (and ref_dataset, the same views with the stage-3 inputs; not under dst_env, as in edit.py:225-230)
     ref_model.fast_render(edit_rows=that mask, opt_scale).  Files: outroot/<name>/ by vis_batch (pred_edit_mask.png and embed_map.png
     among them; the two models write the files both know with the same content), outroot/auto_sel/<name>.npy and auto_sel/dst.json.  If a condition
     names rgb, a plain render of the view comes first (the stage-3 model's if given, else the stage-2 model's `call`) and feeds it.
+    png is handed to vis_batch ('device': the PNGs are encoded on the device).
     -> (writer, {name: selected pixels}), the counts read from the device once, at the end."""
     if not isinstance(selection, material_edit.Selection):
         raise ValueError(f'selection is a material_edit.Selection, got {type(selection).__name__}')
@@ -95,8 +96,8 @@ def run(vq_model, dataset, outroot, selection, dst, ref_model=None, ref_dataset=
         if ref_model is not None and dst_env is None:
             rows = (picked[:, 0] != 0).to(torch.uint8)
             _, _, _, ref_vis = ref_model.fast_render(ref_batch, mode='test', opt_scale=opt_scale, edit_material=dst, edit_rows=rows)
-            ref_model.vis_batch(ref_vis, outdir, mode='test', writer=writer)
-        vq_model.vis_batch(to_vis, outdir, mode='test', writer=writer)
+            ref_model.vis_batch(ref_vis, outdir, mode='test', writer=writer, png=png)
+        vq_model.vis_batch(to_vis, outdir, mode='test', writer=writer, png=png)
         host, ev = writer.fetch({'mask': picked})
         writer.submit(_save_selection, host, ev, _hw(to_vis), os.path.join(sel_dir, name + '.npy'))
         names.append(name)

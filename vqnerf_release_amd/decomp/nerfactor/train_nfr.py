@@ -391,10 +391,11 @@ def graph_default(device, model=None):
 
 
 def fit(config, outdir, dataset_train, dataset_vali=None, model=None, device='cuda', epochs=None, graph=None, seed=None,
-        log=print, metrics=False):
+        log=print, metrics=False, png='host'):
     """Train the VQ stage for `epochs` (config `epochs`) passes over the training views; returns (model, history).
     `graph`: None (default) = the captured step whenever it is eligible (`graph_default`), True / False force it.
     `metrics`: handed to `vis_batch` (device scores in every metadata.json it writes).
+    `png`: handed to `vis_batch` ('device': the validation views' PNGs are encoded on the device).
 
     history: {'loss': [mean step loss per epoch], 'vali': [{'step', 'drop_losses', 'main_vq', 'vis_dirs'} ...]}."""
     import json, os
@@ -502,7 +503,7 @@ def fit(config, outdir, dataset_train, dataset_vali=None, model=None, device='cu
                     vdir = os.path.join(edir, ('main_' + n_codes) if i == main_vq else n_codes, 'batch{b:09d}'.format(b=b))
                     full = os.path.join(outdir, 'vis_vali', 'vis_params', 'epoch{e:09d}'.format(e=step)) \
                         if (b == vis_view and i == len(val_thres_list) - 1) else None
-                    writer = model.vis_batch(to_vis, vdir, mode='vali', simp=True, full_vis_path=full, metrics=metrics)
+                    writer = model.vis_batch(to_vis, vdir, mode='vali', simp=True, full_vis_path=full, metrics=metrics, png=png)
                     vis_dirs.append(vdir)
             if writer is not None:
                 writer.flush()
@@ -514,13 +515,13 @@ def fit(config, outdir, dataset_train, dataset_vali=None, model=None, device='cu
 
 @torch.no_grad()
 def render_views(model, dataset, outroot, relight_olat=False, relight_probes=False, opt_scale=None, writer=None, log=None,
-                 num_p=None, p_i=None, metrics=False, **fast_render_kwargs):
+                 num_p=None, p_i=None, metrics=False, png='host', **fast_render_kwargs):
     """The inference loops of the reference's test.py (:180-266: `raw_test` / `pd_test` / `pd_relit` passes): every view of
     `dataset` through `model.fast_render(mode='test', ...)`, its files queued into `outroot/batch{i:09d}` (i = the view's
     index in the sorted set) by the asynchronous `vis_batch`.  Rendering of view i + 1 overlaps the encoding of view i; the
     returned writer's `.flush()` waits for the files.  Views are independent: with `num_p` processes (default: the ranks of
     the process group) process `p_i` takes views p_i, p_i + num_p, ... -- multi-GPU batched inference with no collective.
-    `metrics` is handed to `vis_batch`.  Returns (writer, number of views this process rendered)."""
+    `metrics` and `png` are handed to `vis_batch`.  Returns (writer, number of views this process rendered)."""
     import os
     if num_p is None:
         num_p, p_i = parallel.world_size(), parallel.rank()
@@ -531,7 +532,7 @@ def render_views(model, dataset, outroot, relight_olat=False, relight_probes=Fal
         batch = dataset.view(f)
         _, _, _, to_vis = model.fast_render(batch, mode='test', relight_olat=relight_olat, relight_probes=relight_probes,
                                             opt_scale=opt_scale, **fast_render_kwargs)
-        writer = model.vis_batch(to_vis, os.path.join(outroot, 'batch{i:09d}'.format(i=order[f])), mode='test', writer=writer, metrics=metrics)
+        writer = model.vis_batch(to_vis, os.path.join(outroot, 'batch{i:09d}'.format(i=order[f])), mode='test', writer=writer, metrics=metrics, png=png)
         n += 1
         if log is not None:
             log(f'view {order[f]} queued')
@@ -542,12 +543,13 @@ def render_views(model, dataset, outroot, relight_olat=False, relight_probes=Fal
 
 
 def fit_stage(config, outdir, dataset_train, dataset_vali=None, model=None, device='cuda', epochs=None, seed=None, log=print, graph=None,
-              metrics=False):
+              metrics=False, png='host'):
     """Epoch loop of the stage-1 (`nfr_unit`) and stage-3 (`ref_nfr`) models: the shape_unit branch of trainvali.py:201-318.
     One max-colour-difference pair sample and one step per training view and epoch; `pretrain=True` with `bias_weight` for
     the first `pretrain_epochs` epochs; checkpoints every `ckpt_period`; every `vali_period` the summed loss terms
     (`loss.json`) and the validation views through `vis_batch` into `vis_vali/epoch{e:09d}/batch{b:09d}`, then `metas.json`
-    (`metrics=True`: with the device's psnr, mse, psnr_luma, ssim, ssim_luma per view, so that `save_metas` has them to average).
+    (`metrics=True`: with the device's psnr, mse, psnr_luma, ssim, ssim_luma per view, so that `save_metas` has them to average;
+    `png` is handed to `vis_batch` as well).
     Returns (model, {'loss': [...], 'vali_dirs': [...]})."""
     import json, os
     from vqnerf_release_amd.decomp.nerfactor.models import get_model_class
@@ -615,7 +617,7 @@ def fit_stage(config, outdir, dataset_train, dataset_vali=None, model=None, devi
                 for b, view in enumerate(vali_views):
                     _, _, _, to_vis = model(view, mode='vali', **only({'pretrain': pre, 'bias_weight': 1.0}))
                     vdir = os.path.join(edir, 'batch{b:09d}'.format(b=b))
-                    writer = model.vis_batch(to_vis, vdir, mode='vali', metrics=metrics)
+                    writer = model.vis_batch(to_vis, vdir, mode='vali', metrics=metrics, png=png)
                     hist['vali_dirs'].append(vdir)
             if writer is not None:
                 writer.flush()

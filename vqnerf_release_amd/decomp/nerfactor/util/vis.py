@@ -12,6 +12,11 @@ What is different on purpose: nothing is written on the calling thread.  The ten
 pinned buffers on a side stream, and PNG / NPY encoding runs on worker threads (`AsyncWriter`), so a 16-probe relighting
 pass does not stall the kernels behind ~20 PNG encodes per view.  `writer.flush()` joins.
 
+`vis_batch(png='device')` goes one step further for views whose tensors are on the device: every 8-bit image the host path would
+write is formed there (the same f32 statements in the same order), all 3-channel images of the view are PNG-encoded as one batch and
+all 1-channel images as another (util/png.py, csrc/png_encode.hip), and only the compressed bytes and the `.npy` arrays cross to the
+host; the worker threads take the IDAT CRC and write.  The files decode to the same pixels.  `pred_light.png` stays on the host path.
+
 Third-party arithmetic restated (xiuminglib, not in the reference tree): `xm.io.img.write_arr(arr, path, clip=True)` clips to
 [0, 1] and casts `arr * 255` to uint8 (truncation); `xm.metric.PSNR('uint8')` = 10 log10(1 / mean((a/255 - b/255)^2)).
 """
@@ -144,6 +149,21 @@ def default_writer():
     return _default_writer
 
 
+def _view_shape(k, shape, hw):
+    """the image shape of entry k whose rows have `shape` (vq_nfr.py:1021-1034)"""
+    if k in ('pred_rgb_olat', 'pred_rgb_probes'):
+        return hw + (shape[1], 3)
+    if k.endswith(('rgb', 'albedo', 'normal', 'diff', 'spec', 'xyz', 'basecolor')):
+        return hw + (3,)
+    if k.endswith(('occu', 'depth', 'disp', 'alpha', 'rough', 'embed', 'ks')):
+        return hw
+    if k.endswith(('z',)):
+        return hw + (shape[1],)
+    if k.endswith('edit_mask'):                                  # the selection of fast_render(edit_select=...), 0 / 1
+        return hw
+    raise NotImplementedError(k)
+
+
 def _shape_views(host, hw):
     """Rows back to images (vq_nfr.py:1021-1034)."""
     out = {}
@@ -152,19 +172,7 @@ def _shape_views(host, hw):
             continue
         a = v.numpy() if torch.is_tensor(v) else np.asarray(v)
         a = a.astype(np.float32, copy=False) if a.dtype.kind == 'f' else a.astype(np.float32)
-        if k in ('pred_rgb_olat', 'pred_rgb_probes'):
-            a = a.reshape(hw + (a.shape[1], 3))
-        elif k.endswith(('rgb', 'albedo', 'normal', 'diff', 'spec', 'xyz', 'basecolor')):
-            a = a.reshape(hw + (3,))
-        elif k.endswith(('occu', 'depth', 'disp', 'alpha', 'rough', 'embed', 'ks')):
-            a = a.reshape(hw)
-        elif k.endswith(('z',)):
-            a = a.reshape(hw + (a.shape[1],))
-        elif k.endswith('edit_mask'):                                # the selection of fast_render(edit_select=...), 0 / 1
-            a = a.reshape(hw)
-        else:
-            raise NotImplementedError(k)
-        out[k] = a
+        out[k] = a.reshape(_view_shape(k, a.shape, hw))
     return out
 
 
@@ -229,6 +237,119 @@ def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_
         j.result()
 
 
+def _write_bytes(path, head, stream):
+    """a worker's share of a device-encoded PNG: the IDAT CRC and the file"""
+    from vqnerf_release_amd.decomp.nerfactor.util.png import png_file
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(png_file(head, stream))
+
+
+_png_encoder = None
+
+
+def _device_images(d, mode, white_bg, probe_names, olat_names, olat_first_n, alpha_thres, simp, full_vis_path, outdir):
+    """What `_write_view` writes for the view d = {key: f32 device tensor, shaped as an image}: ([(file name, uint8 device tensor
+    [H,W,3] | [H,W])], [(npy path, key)]), the images formed by the same f32 operations in the same order."""
+    alpha = threshold_alpha(d['gt_alpha'], alpha_thres)
+    full_vis = full_vis_path is not None
+    images, npy = [], []
+
+    def png(key, arr01):
+        images.append((key, (torch.clamp(arr01, 0.0, 1.0) * 255.0).to(torch.uint8)))
+
+    for k, v in d.items():
+        if k in ('pred_rgb_olat', 'pred_rgb_probes'):
+            for i, lname in relit_names(k, v.shape[2], probe_names, olat_names, olat_first_n):
+                images.append((k + '_' + lname, composite_uint8(v[:, :, i, :], alpha, white_bg)))
+        elif k.endswith(('rgb', 'diff')):
+            images.append((k, composite_uint8(v, alpha, white_bg)))
+        elif k.endswith(('albedo', 'spec', 'rough', 'ks', 'basecolor')):
+            npy.append((os.path.join(outdir, k + '.npy'), k))
+            png(k, v)
+        elif k.endswith(('embed',)):
+            if full_vis:
+                npy.append((os.path.join(full_vis_path, k + '.npy'), k))
+            lut = torch.zeros((19, 3), dtype=torch.uint8, device=v.device)
+            lut[1:] = torch.as_tensor(_EMBED_COLOURS[:, ::-1].copy(), device=v.device)
+            e = torch.round(v).to(torch.int64)
+            images.append(('embed_map', lut[torch.where((e >= 1) & (e <= 18), e, torch.zeros_like(e))]))
+        elif k.endswith(('z',)) and full_vis:
+            npy.append((os.path.join(full_vis_path, k + '.npy'), k))
+        elif k.endswith(('xyz',)):
+            npy.append((os.path.join(outdir, k + '.npy'), k))
+        elif k.endswith('normal'):
+            images.append((k, composite_uint8((v + 1.0) / 2.0, alpha, white_bg)))
+        elif k.endswith('edit_mask'):
+            png(k, v)
+        elif k.endswith(('z',)):
+            pass
+        elif mode != 'render' and not simp:
+            png(k, v)
+    return images, npy
+
+
+def _write_view_device(host, event, hw, id_, outdir, mode, simp, npy, files, pool_submit, scores=None):
+    if event is not None:
+        event.synchronize()
+    pair = [host.pop(k, None) for k in ('_gt_rgb_u8', '_pred_rgb_u8')]
+    d = _shape_views(host, hw)
+    os.makedirs(outdir, exist_ok=True)
+    jobs = [pool_submit(np.save, path, d[k]) for path, k in npy]
+    jobs += [pool_submit(_write_bytes, os.path.join(outdir, name + '.png'), head, stream) for name, head, stream in files]
+    meta = {'id': id_}
+    if not simp:
+        if mode not in ('test', 'render') and pair[0] is not None and pair[1] is not None:
+            meta['psnr'] = psnr_uint8(pair[0].numpy(), pair[1].numpy())
+            if scores is not None:
+                from vqnerf_release_amd.decomp.nerfactor.util.metric import KEYS
+                meta.update(zip(KEYS, scores.tolist()))
+        with open(os.path.join(outdir, 'metadata.json'), 'w') as f:
+            json.dump(meta, f)
+    for j in jobs:
+        j.result()
+
+
+def _vis_batch_device(model, data_dict, hw, id_, outdir, mode, alpha_thres, simp, full_vis_path, writer, scores):
+    """the view's images formed and PNG-encoded on the device; the bytes, the .npy arrays and metadata.json through the writer"""
+    global _png_encoder
+    from vqnerf_release_amd import _C
+    from vqnerf_release_amd.decomp.nerfactor.util.png import PngEncoder
+    d = {}
+    for k, v in data_dict.items():
+        if v is None:
+            continue
+        if not torch.is_tensor(v):
+            raise _C.VqnError(f"vis_batch(png='device'): entry {k!r} is a {type(v).__name__}, not a device tensor")
+        _C.require_device(v, "vis_batch(png='device')")
+        d[k] = v.detach().to(torch.float32).reshape(_view_shape(k, tuple(v.shape), hw))
+    probe_names = list(getattr(model, 'novel_probes', {}) or {})
+    olat_names = list(getattr(model, 'novel_olat', {}) or {})
+    light_res = getattr(model, 'light_res', (16, 32))
+    images, npy = _device_images(d, mode, bool(model.white_bg), probe_names, olat_names, int(np.prod(light_res)) // 2, alpha_thres, simp,
+                                 full_vis_path, outdir)
+    if _png_encoder is None:
+        _png_encoder = PngEncoder()
+    files = []
+    for rank in (3, 2):                                          # all [H,W,3] images as one batch, all [H,W] images as another
+        group = [(name, img) for name, img in images if img.dim() == rank]
+        if group:
+            head, streams = _png_encoder.streams(torch.stack([img for _, img in group]))
+            files += [(name, head, s) for (name, _), s in zip(group, streams)]
+    written = dict(images)
+    fetch = {k: data_dict[k] for _, k in npy}
+    if not simp and mode not in ('test', 'render') and 'gt_rgb' in written and 'pred_rgb' in written:
+        fetch['_gt_rgb_u8'], fetch['_pred_rgb_u8'] = written['gt_rgb'], written['pred_rgb']
+    if scores is not None:
+        fetch['_scores'] = scores
+    host, ev = writer.fetch(fetch)
+    scores = host.pop('_scores', None)
+    if full_vis_path is not None:
+        os.makedirs(full_vis_path, exist_ok=True)
+    writer.submit(_write_view_device, host, ev, hw, id_, outdir, mode, simp, npy, files, writer.pool.submit, scores)
+    return writer
+
+
 def vis_light_uint8(light, h=None):
     """[h0,w0,3] probe -> uint8 image, optionally resized to height h with antialiased bilinear filtering (light.py:30-50)."""
     t = torch.as_tensor(light, dtype=torch.float32).detach().cpu()
@@ -254,13 +375,18 @@ def _device_scores(data_dict, hw, white_bg, alpha_thres):
 
 
 def vis_batch(model, data_dict, outdir, mode='train', light_vis_h=256, alpha_thres=0.8, simp=False, full_vis_path=None,
-              writer=None, metrics=False):
+              writer=None, metrics=False, png='host'):
     """Model.vis_batch (vq_nfr.py:988-1134).  data_dict: the `to_vis` dict of `call` / `fast_render` / `vis_mat` (device
     tensors with N = H*W rows, plus 'hw' [N,2] and 'id').  Returns the AsyncWriter the files were queued on.
     metrics: where `metadata.json` gets its `psnr` (ground truth exists, not `simp`, not a test / render pass), also score the
     two images on the device before they are fetched (util/metric.py) and write `psnr`, `mse`, `psnr_luma`, `ssim`, `ssim_luma`
-    there; `psnr` is then the device's value.  Off (the default): every file is what it was."""
+    there; `psnr` is then the device's value.  Off (the default): every file is what it was.
+    png: 'host' (the default): PIL on the writer's threads, every file byte for byte what it was.  'device': the 8-bit images are formed
+    and PNG-encoded on the device (device tensors only; the files decode to the same pixels, the .npy files and metadata.json are the
+    same bytes); `pred_light.png` is written by the host path either way."""
     model._validate_mode(mode)
+    if png not in ('host', 'device'):
+        raise ValueError(f"vis_batch: png is 'host' or 'device', got {png!r}")
     writer = writer or default_writer()
     if mode == 'vali':
         root = os.path.dirname(outdir.rstrip('/'))
@@ -286,6 +412,8 @@ def vis_batch(model, data_dict, outdir, mode='train', light_vis_h=256, alpha_thr
     scores = None
     if metrics and not simp and mode not in ('test', 'render') and all(data_dict.get(k) is not None for k in ('gt_rgb', 'pred_rgb', 'gt_alpha')):
         scores = _device_scores(data_dict, hw, bool(model.white_bg), alpha_thres)
+    if png == 'device':
+        return _vis_batch_device(model, data_dict, hw, str(id_), outdir, mode, alpha_thres, simp, full_vis_path, writer, scores)
     host, ev = writer.fetch({k: v for k, v in dict(data_dict, **({} if scores is None else {'_scores': scores})).items() if v is not None})
     scores = host.pop('_scores', None)
     probe_names = list(getattr(model, 'novel_probes', {}) or {})

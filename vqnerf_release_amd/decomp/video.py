@@ -78,8 +78,9 @@ def _read_mask(mask_dir, i, n, device):
 
 @torch.no_grad()
 def run(model, dataset, outroot, mode, vq_model=None, opt_scale=None, selection=None, dst=None, mask_dir=None, fps=20, quality=75,
-        frames=False, scene=None, writer=None):
-    """-> {stream name: path of its AVI file}.  model: the stage-3 model; dataset: datasets/video_nfr.py; see the module text."""
+        frames=False, scene=None, writer=None, png='host'):
+    """-> {stream name: path of its AVI file}.  model: the stage-3 model; dataset: datasets/video_nfr.py; see the module text.
+    png: how the per-frame files of frames=True are encoded ('host' or 'device': vis.vis_batch)."""
     if mode not in MODES:
         raise ValueError(f'mode is one of {MODES}, got {mode!r}')
     if mode == 'edit':
@@ -148,9 +149,9 @@ def run(model, dataset, outroot, mode, vq_model=None, opt_scale=None, selection=
             sink.push(images)
             if frames:
                 name = 'test_{i:03d}'.format(i=i)
-                model.vis_batch(to_vis, os.path.join(outroot, name), mode='test', writer=writer)
+                model.vis_batch(to_vis, os.path.join(outroot, name), mode='test', writer=writer, png=png)
                 if vq_vis is not None:
-                    vq_model.vis_batch(vq_vis, os.path.join(outroot, 'vq', name), mode='test', writer=writer)
+                    vq_model.vis_batch(vq_vis, os.path.join(outroot, 'vq', name), mode='test', writer=writer, png=png)
     finally:
         if sink is not None:
             sink.close()
