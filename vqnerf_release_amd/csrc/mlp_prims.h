@@ -347,6 +347,130 @@ __device__ __forceinline__ void gemm_tiles2(const f32x4* __restrict__ lds, const
   }
 }
 
+// NIMG-image form of gemm_tiles2 for layers computed IN PLACE (the SDF-only kernel, neus_pointsN_kernel): a wave applies each weight
+// fragment to NIMG images (4 NIMG MFMAs per fetched float4), so a layer puts NIMG / 2 times the matrix work of the two-image form between
+// two barriers.  One output tile per wave (n_out_tiles <= NW): the wave's tile stays in `acc` -- epi_rq(ot, img, rq, acc) applies the
+// activation to row quad rq of acc IN the registers and stores nothing; the caller writes the rows over the layer's input after a
+// workgroup barrier.  `pre` / `next_wp`: the chain prefetch of gemm_tiles_chain, always on.  Operand pipeline, clamped unconditional
+// fetches and the one drain per tile as in gemm_tiles2; per image the accumulation order is gemm_tiles2's (init, then the K rows in
+// order), so the results are the same bits.  Peeled last block (K a whole number of double blocks): the LAST image's half of it is
+// issued one K group at a time between the epilogue quads of all earlier images.
+template <int NIMG, int NW = 8, class Init, class EpiRq>
+__device__ __forceinline__ void gemm_tilesN(const f32x4* __restrict__ lds, const int img_stride, const KSegs ks,
+                                            const f32x4* __restrict__ w, const int n_out_tiles, const int wave,
+                                            const int lane, f32x4 (&pre)[4], const f32x4* __restrict__ next_wp,
+                                            f32x16 (&acc)[NIMG], Init init, EpiRq epi_rq) {
+  static_assert(NIMG >= 2 && NIMG <= 4, "images per workgroup");
+  constexpr int LAST = NIMG - 1;
+  const int ng = ks.nA + ks.nB;
+  if (wave < n_out_tiles) {
+    const int ot = wave;
+    const f32x4* __restrict__ wp = w + (size_t)ot * ng * 64 + lane;
+    auto brow = [&](int g) { g = min(g, ng - 1); return ((g < ks.nA) ? (ks.rowA + g) : (ks.rowB + (g - ks.nA))) * 64 + lane; };
+    f32x4 a0[4], a1[4], bc[NIMG], bn[NIMG];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a0[i] = pre[i];
+    {
+      const int r = brow(0);
+#pragma unroll
+      for (int im = 0; im < NIMG; ++im) bc[im] = lds[r + im * img_stride];
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0) only (see gemm_tiles)
+#pragma unroll
+    for (int im = 0; im < NIMG; ++im) init(ot, im, acc[im]);
+    __builtin_amdgcn_s_setprio(1);
+    auto block = [&](const f32x4 (&a)[4], int g0) {          // groups g0 .. g0 + 3 with fragments a
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        {
+          const int r = brow(g0 + i + 1);
+#pragma unroll
+          for (int im = 0; im < NIMG; ++im) bn[im] = lds[r + im * img_stride];
+        }
+        if (g0 + i < ng) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int im = 0; im < NIMG; ++im) acc[im] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][j], bc[im][j], acc[im], 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int im = 0; im < NIMG; ++im) bc[im] = bn[im];
+      }
+    };
+    if ((ng & 7) == 0) {
+      for (int g = 0; g < ng - 8; g += 8) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a1[i] = wp[(g + 4 + i) * 64];
+        block(a0, g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a0[i] = wp[(g + 8 + i) * 64];
+        block(a1, g + 4);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a1[i] = wp[(ng - 4 + i) * 64];
+      block(a0, ng - 8);
+      if (next_wp != nullptr) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pre[i] = next_wp[i * 64];
+      }
+      // (Measured against this: the peeled block image after image, image im's four K groups between the epilogue quads of image
+      // im - 1 -- every epilogue but the last under 16 MFMAs of its own.  0.4 % slower, 545.7 vs 543.4 ms of SDF passes per step.)
+      f32x4 qt[4];                                           // the last image's operands of the peeled block
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        {
+          const int r = brow(ng - 4 + i + 1);
+#pragma unroll
+          for (int im = 0; im < NIMG; ++im) bn[im] = lds[r + im * img_stride];
+        }
+        qt[i] = bc[LAST];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+          for (int im = 0; im < LAST; ++im) acc[im] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i][j], bc[im][j], acc[im], 0, 0, 0);
+        }
+#pragma unroll
+        for (int im = 0; im < NIMG; ++im) bc[im] = bn[im];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[LAST] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i][j], qt[i][j], acc[LAST], 0, 0, 0);
+#pragma unroll
+        for (int im = 0; im < LAST; ++im) epi_rq(ot, im, i, acc[im]);
+      }
+      __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) epi_rq(ot, LAST, rq, acc[LAST]);
+    } else {
+      for (int g = 0; g < ng; g += 8) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a1[i] = wp[min(g + 4 + i, ng - 1) * 64];
+        block(a0, g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a0[i] = wp[min(g + 8 + i, ng - 1) * 64];
+        block(a1, g + 4);
+      }
+      if (next_wp != nullptr) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pre[i] = next_wp[i * 64];
+      }
+#pragma unroll
+      for (int im = 0; im < LAST; ++im) {
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) epi_rq(ot, im, rq, acc[im]);
+      }
+      __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) epi_rq(ot, LAST, rq, acc[LAST]);
+    }
+  } else if (next_wp != nullptr) {      // a wave without a tile in this layer still owes the next layer its fragments
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pre[i] = next_wp[i * 64];
+  }
+}
+
 __device__ __forceinline__ f32x4 acc_quad(const f32x16& acc, int rq) {
   // static rq only (callers unroll)
   return (f32x4){acc[4 * rq + 0], acc[4 * rq + 1], acc[4 * rq + 2], acc[4 * rq + 3]};

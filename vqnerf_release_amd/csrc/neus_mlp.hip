@@ -626,6 +626,96 @@ __global__ __launch_bounds__(512, 1) void neus_points2_kernel(
   FS_FLUSH
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// NIMG-image form of the SDF-only kernel (NIMG = 3, 4): the per-layer cost of the two-image form that is not matrix work (operand
+// pipeline fill, epilogue, barrier) stays what it is and NIMG / 2 times the matrix work goes between two barriers.  Without a stash, a
+// reverse sweep or a colour net an image needs no second activation buffer: a layer is computed IN PLACE -- K loop, epilogue into the
+// accumulator registers (gemm_tilesN), barrier, the tile's rows over the layer's input, barrier -- so an image is its embedding rows
+// (sd.emb_rows of them, not E_ROWS) plus 4 max_tiles activation rows.  One output tile per wave: max_tiles <= 8.  The VALU phases are
+// dealt over the eight waves as (image, row) and (image, quarter) units; per point the arithmetic and its order are those of
+// neus_points2_kernel<false>, so the outputs are the same bits.
+template <int NIMG>
+struct SmallsSdf {           // Smalls without what only the fine kernels use (grad, the rgb partials): what lets four images fit
+  float pts[NIMG][96], dirs[NIMG][96], part[NIMG][128];
+};
+
+template <int NIMG>
+__global__ __launch_bounds__(512, 1) void neus_pointsN_kernel(
+    const SdfDesc sd, const f32x4* __restrict__ wsdf, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+    const float* __restrict__ zv, const float* __restrict__ pts_direct, const long P, const int S, float* __restrict__ out_sdf) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
+  const int MT = sd.max_tiles;
+  const int X0 = sd.emb_rows, IS = (sd.emb_rows + 4 * MT) * 64;
+  SmallsSdf<NIMG>* sm = reinterpret_cast<SmallsSdf<NIMG>*>(lds + (size_t)NIMG * IS);
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n_lin = sd.n_lin;
+  const long n_tiles = (P + 31) >> 5, n_groups = (n_tiles + NIMG - 1) / NIMG;
+  f32x4 pre[4];
+  f32x16 acc[NIMG];
+
+  for (long grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+    // ---------------- points of the NIMG tiles (a tile past n_tiles: clamped points, nothing stored) ----------------
+    if (tid < 32 * NIMG) {
+      const int im = tid >> 5, t = tid & 31;
+      load_point<false>(((NIMG * grp + im) << 5) + t, P, S, rays_o, rays_d, zv, pts_direct, nullptr, sm->pts[im] + t * 3, sm->dirs[im] + t * 3);
+    }
+    __syncthreads();
+    for (int u = wave; u < NIMG * sd.emb_rows; u += 8) {                  // (image, embedding row) units
+      const int im = u / sd.emb_rows, r = u - im * sd.emb_rows;
+      const float xs = sm->pts[im][p * 3 + 0] * sd.scale, ys = sm->pts[im][p * 3 + 1] * sd.scale, zs = sm->pts[im][p * 3 + 2] * sd.scale;
+      f32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = emb_feat(row_feat(r, h, j), sd.emb_feats, xs, ys, zs);
+      lds[(size_t)im * IS + (E0 + r) * 64 + lane] = v;
+    }
+    __syncthreads();
+
+    // ---------------- SDF hidden layers, in place ----------------
+    if (wave < sd.layers[0].n_out_tiles) {
+      const f32x4* wp0 = wsdf + sd.layers[0].w_off + (size_t)wave * sd.emb_rows * 64 + lane;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pre[i] = wp0[min(i, sd.emb_rows - 1) * 64];
+    }
+    for (int l = 0; l < n_lin - 1; ++l) {
+      const LayerDesc L = sd.layers[l];
+      const f32x4* next_wp = nullptr;
+      if (l + 1 < n_lin - 1 && wave < sd.layers[l + 1].n_out_tiles)
+        next_wp = wsdf + sd.layers[l + 1].w_off + (size_t)wave * (4 * L.n_out_tiles + ((l + 1 == sd.skip) ? sd.emb_rows : 0)) * 64 + lane;
+      const KSegs ks = (l == 0) ? KSegs{E0, sd.emb_rows, 0, 0}
+                                : KSegs{X0, 4 * sd.layers[l - 1].n_out_tiles, E0, (l == sd.skip) ? sd.emb_rows : 0};
+      const f32x4* bp = wsdf + L.b_off;
+      gemm_tilesN<NIMG, 8>(lds, IS, ks, wsdf + L.w_off, L.n_out_tiles, wave, lane, pre, next_wp, acc,
+                           [&](int ot, int, f32x16& a) { init_bias(bp, ot, lane, a); },
+                           [&](int, int, int rq, f32x16& a) {
+#pragma unroll
+                             for (int j = 0; j < 4; ++j) a[4 * rq + j] = act_fwd<ACT_SOFTPLUS100>(a[4 * rq + j]);
+                           });
+      if (l > 0) __syncthreads();                      // every wave is done reading X (layer 0 reads the E rows only)
+      if (wave < L.n_out_tiles) {
+#pragma unroll
+        for (int im = 0; im < NIMG; ++im) {
+#pragma unroll
+          for (int rq = 0; rq < 4; ++rq) lds[(size_t)im * IS + (X0 + wave * 4 + rq) * 64 + lane] = acc_quad(acc[im], rq);
+        }
+      }
+      __syncthreads();
+    }
+    const int hid_rows = 4 * sd.layers[n_lin - 2].n_out_tiles;
+
+    // ---------------- last layer: sdf row (VALU dot), four partials per image ----------------
+    for (int u = wave; u < 4 * NIMG; u += 8)
+      rowdot<1>(lds + (size_t)(u >> 2) * IS, X0, hid_rows, wsdf + sd.last_w_off, sm->part[u >> 2], u & 3, lane);
+    __syncthreads();
+    if (tid < 32 * NIMG) {
+      const int im = tid >> 5, t = tid & 31;
+      const long pt = ((NIMG * grp + im) << 5) + t;
+      if (pt < P) out_sdf[pt] = sdf_raw(sm->part[im], t, sd.last_b_off, sd.last_bias, wsdf) / sd.scale;
+    }
+    __syncthreads();
+  }
+}
+
 int check_sdf_desc(const SdfDesc& d) {
   if (d.n_lin < 2 || d.n_lin > VQN_MAX_SDF_LAYERS) return 1;
   if (d.max_tiles < 1 || d.max_tiles > 16) return 2;
@@ -647,6 +737,34 @@ bool use_two_images(int MT) {
   return !forced32 && MT >= 5 && lds_bytes<2>(MT) <= 160 * 1024;
 }
 
+template <int NIMG>
+size_t lds_bytes_sdf(const SdfDesc& sd) { return (size_t)NIMG * (sd.emb_rows + 4 * sd.max_tiles) * 1024 + sizeof(SmallsSdf<NIMG>); }
+
+// Images per workgroup of the SDF-only entry: the most of {4, 3} that fit the 160 KB of LDS (neus_pointsN_kernel: 5 <= max_tiles <= 8,
+// one output tile per wave), else the two-image or one-image form as before.  VQN_NEUS_SDF_IMAGES=2|3|4 (read once) caps the count for
+// A/B runs and tests; a count that does not fit falls back to the next smaller form.
+constexpr int SDF_IMAGES_DEFAULT = 4;
+int sdf_images(const SdfDesc& sd) {
+  static const int cap = [] {
+    const char* e = getenv("VQN_NEUS_SDF_IMAGES");
+    const int v = e != nullptr ? atoi(e) : SDF_IMAGES_DEFAULT;
+    return v >= 2 && v <= 4 ? v : SDF_IMAGES_DEFAULT;
+  }();
+  if (!use_two_images(sd.max_tiles)) return 1;
+  if (sd.max_tiles <= 8) {
+    if (cap >= 4 && lds_bytes_sdf<4>(sd) <= 160 * 1024) return 4;
+    if (cap >= 3 && lds_bytes_sdf<3>(sd) <= 160 * 1024) return 3;
+  }
+  return 2;
+}
+
+template <int NIMG>
+int launch_sdf_images(const char* fn, const SdfDesc& sd, const f32x4* ws, const float* rays_o, const float* rays_d, const float* z,
+                      const float* pts, const int64_t P, const int S, float* out_sdf, void* stream) {
+  return neus_launch(fn, neus_pointsN_kernel<NIMG>, true, pair_grid((P + 31) / 32, NIMG, 0, 0), 512, lds_bytes_sdf<NIMG>(sd), stream, sd, ws,
+                     rays_o, rays_d, z, pts, (long)P, S, out_sdf);
+}
+
 bool extras_rows_ok(const ColDesc& cd) { return cd.extra_rows >= 1 && cd.extra_rows <= 8; }
 
 }  // namespace
@@ -662,7 +780,10 @@ extern "C" int vqn_neus_sdf_points(const int32_t* sdf_desc, const float* wbuf_sd
   memset(&cd, 0, sizeof(cd));
   const long n_tiles = (P + 31) / 32;
   const f32x4* ws = reinterpret_cast<const f32x4*>(wbuf_sdf);
-  if (use_two_images(sd.max_tiles))
+  const int images = sdf_images(sd);
+  if (images == 4) return launch_sdf_images<4>(__func__, sd, ws, rays_o, rays_d, z, pts, P, S, out_sdf, stream);
+  if (images == 3) return launch_sdf_images<3>(__func__, sd, ws, rays_o, rays_d, z, pts, P, S, out_sdf, stream);
+  if (images == 2)
     return neus_launch(__func__, neus_points2_kernel<false>, true, pair_grid(n_tiles, 2, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws,
                        nullptr, rays_o, rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
   const size_t lds = lds_bytes<1>(sd.max_tiles);
