@@ -1,9 +1,7 @@
-/* vqn_neus_fold.h -- the entry points of libvqnerf_hip.so that include/vqnerf_hip.h does not declare (its list of 91 is held fixed):
- * the folded colour pack of the f32 NeuS inference path (csrc/neus_fold.hip) and, below it, the mesh export of the NeuS surface
- * (csrc/marching_cubes.hip, csrc/marching_cubes_bricks.hip, csrc/mesh_components.hip) and the image and segmentation metrics
- * (csrc/image_metrics.hip, csrc/segmentation_metrics.hip), mean shift (csrc/meanshift.hip) and the material selection and edit
- * (csrc/material_edit.hip).  Same conventions as vqnerf_hip.h (device pointers owned by the caller,
- * host descriptors, `stream` a hipStream_t, negative return = error with vqn_last_error()). */
+/* vqn_neus_fold.h -- the folded colour pack of the f32 NeuS inference path (csrc/neus_fold.hip), one entry point of libvqnerf_hip.so.
+ * include/vqnerf_hip.h declares the library's first 91 functions and that list is held fixed; everything added since has a header
+ * per area beside it: this one, vqn_mesh.h, vqn_eval.h, vqn_material_edit.h, vqn_image_codec.h.  Same conventions as vqnerf_hip.h
+ * (device pointers owned by the caller, host descriptors, `stream` a hipStream_t, negative return = error with vqn_last_error()). */
 #ifndef VQN_NEUS_FOLD_H_
 #define VQN_NEUS_FOLD_H_
 #include <stdint.h>
@@ -28,245 +26,6 @@ int64_t vqn_neus_fold_pack(const int32_t* sdf_desc, const int32_t* col_desc, con
                            const float* sdf_w_last, const float* sdf_b_last, int sdf_hidden, int d_feature, const float* col_w0,
                            const float* col_b0, int col_hidden, float* wbuf_out, int64_t out_floats, int32_t* col_desc_out,
                            void* stream);
-
-/* ---- mesh export: marching cubes over a device field u[nx][ny][nz] (C order, f32) --------------------------------------------------
- * Conventions (csrc/mc_table.h, generated by tools/gen_mc_table.py): a grid point is INSIDE iff u > threshold (strict); grid point
- * (i, j, k), linear index p = (i * ny + j) * nz + k, owns the three grid edges leaving it in +x, +y, +z; a cell is named by its
- * minimum corner.  Both calls return -2 if any dimension is < 2 or nx * ny * nz >= 2^31, -1 for null pointers.
- *
- * vqn_mc_classify fills, for every grid point p, vert_count[p] = the number of crossing edges it owns (0..3; an edge is owned only
- * if its far end is inside the grid) and tri_count[p] = the triangle count of the cell whose minimum corner is p (0 where there is
- * no such cell).  Both arrays have nx * ny * nz entries.
- *
- * vqn_mc_emit takes their EXCLUSIVE prefix sums (vert_offset, tri_offset) and the two totals and writes verts [n_verts][3] and
- * tris [n_tris][3].  The vertex of the edge from point p (value u0) along axis a to its neighbour (value u1) sits at p + t e_a in
- * index coordinates, t = (threshold - u0) / (u1 - u0) in f32, and has id vert_offset[p] + the rank of a among p's owned crossing
- * edges: one vertex per crossing edge, shared by the cells around it.  Triangles go out in cell order, then table order, counter-
- * clockwise seen from the outside (normals towards decreasing u).  origin / step (HOST pointers to 3 floats, both or neither):
- * every coordinate is written as fma(index coordinate, step, origin); NULL = index coordinates.  n_verts = n_tris = 0 is a no-op;
- * nothing is written outside [0, n_verts) / [0, n_tris). */
-int vqn_mc_classify(const float* u, int nx, int ny, int nz, float threshold, int32_t* vert_count, int32_t* tri_count, void* stream);
-int vqn_mc_emit(const float* u, int nx, int ny, int nz, float threshold, const int32_t* vert_offset, const int32_t* tri_offset,
-                int64_t n_verts, int64_t n_tris, const float* origin, const float* step, float* verts, int32_t* tris, void* stream);
-
-/* ---- mesh clean-up: connected components and compaction of an indexed triangle mesh (csrc/mesh_components.hip) ---------------------
- * tris [n_tris][3] int32 vertex indices, all arrays on the device.  Both calls return -1 for null pointers, negative sizes,
- * n_verts >= 2^31 or 3 n_tris >= 2^31.  A vertex index outside [0, n_verts) is a caller error: such an edge connects nothing (remap
- * writes -1 for it) and no memory outside the arrays is touched.
- *
- * vqn_mesh_components fills labels [n_verts]: two vertices are connected when a triangle uses both, and labels[v] = the SMALLEST
- * vertex index of v's component -- a canonical form, so the output is the same from run to run and equals any other correct
- * implementation's.  A vertex no triangle uses is its own component.  n_tris = 0: labels[v] = v and tris is not read; n_verts = 0
- * is a no-op.  Lock-free union-find inside `labels` itself (parent[v] <= v throughout; the larger root is linked under the smaller
- * by compare-and-swap), three launches, no scratch, no host read.
- *
- * vqn_mesh_remap_tris writes the triangles t with keep_tri[t] != 0 (uint8), in their original order, to tris_out [n_out][3] at row
- * tri_offset[t] -- the EXCLUSIVE prefix sum of keep_tri, n_out its total -- with every vertex id v replaced by new_index[v]
- * (new_index [n_verts]).  One gather launch; rows outside [0, n_out) are not written; n_tris = 0 or n_out = 0 is a no-op. */
-int vqn_mesh_components(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t* labels, void* stream);
-int vqn_mesh_remap_tris(const int32_t* tris_in, int64_t n_tris, const uint8_t* keep_tri, const int32_t* tri_offset,
-                        const int32_t* new_index, int64_t n_verts, int32_t* tris_out, int64_t n_out, void* stream);
-
-/* ---- mesh export on a sparse set of bricks (csrc/marching_cubes_bricks.hip) ------------------------------------------------------
- * The mesh vqn_mc_classify / vqn_mc_emit give on the dense field u[nx][ny][nz], byte for byte, from the values on a list of
- * bricks alone, for grids the dense calls refuse and for fields that are expensive to evaluate.  The nx - 1 cells of an axis are
- * cut into nb = ceil((nx - 1) / 8) bricks of 8 cells, the last one clipped to 1..8.  Brick b STORES the grid points 8 b ..
- * min(8 b + 8, nx - 1) of that axis, up to 9, so a face between two bricks is stored by both.  Grid point i BELONGS to brick
- * min(i / 8, nb - 1): every point has one owner, the grid's last point goes to the last brick, and a cell (named by its minimum
- * corner) lies in its owner's brick with all 8 corners stored there.
- *   brick_ijk [n_bricks][3] int32: the bricks, sorted by linear index (bi * nby + bj) * nbz + bk, each at most once;
- *   ub [n_bricks][9][9][9] f32: their values, local index l = (li * 9 + lj) * 9 + lk; entries past a clipped brick's stored points
- *     are padding and never read; a point two bricks store must hold the same bits in both;
- *   slot [nbx * nby * nbz] int32: a brick's position in brick_ijk, or -1.
- * All three calls return -2 if a dimension is < 2, the brick grid has >= 2^31 entries or n_bricks * 729 >= 2^31, and -1 for
- * null pointers, negative sizes and totals outside int32.  A brick_ijk row outside the brick grid is a caller error: that brick is
- * skipped, no memory outside the arrays is touched.
- *
- * vqn_mc_brick_points writes the stored points [first, first + count) of the flattened [n_bricks][729] list as rows [x y z] of the
- * device axis arrays ax [nx], ay [ny], az [nz] to pts [count][3]; a padding entry repeats the brick's last stored point.
- *
- * vqn_mc_brick_classify fills, per entry of [n_bricks][729]: vert_count and tri_count as vqn_mc_classify does for the grid point
- * the entry is, if the brick owns it (0 otherwise), and keys = that point's dense linear index (i * ny + j) * nz + k as int64
- * (INT64_MAX otherwise).  Sorting by key gives the dense order; the caller turns the counts, taken in that order, into exclusive
- * prefix sums stored back at the entries.  leaks [1] receives the number of (brick, face) pairs where the neighbour across the face
- * is inside the brick grid, is not in the list, and the stored points of the face are not all on one side of the threshold: the
- * surface runs into a brick that was left out.  0 means every crossing edge and every cell the surface passes through that touches
- * a listed brick is in a listed brick.
- *
- * vqn_mc_brick_emit writes verts [n_verts][3] and tris [n_tris][3] exactly as vqn_mc_emit does.  The vertex of a triangle whose edge
- * is owned by a point of a neighbouring brick (local coordinate 8 on a face that is not the grid boundary) takes rank and offset from
- * that brick through slot; if it is not in the list (leaks > 0) index 0 is written in its place.  Nothing is written outside
- * [0, n_verts) / [0, n_tris). */
-int vqn_mc_brick_points(const float* ax, const float* ay, const float* az, int nx, int ny, int nz, const int32_t* brick_ijk,
-                        int64_t n_bricks, int64_t first, int64_t count, float* pts, void* stream);
-int vqn_mc_brick_classify(const float* ub, const int32_t* brick_ijk, int64_t n_bricks, const int32_t* slot, int nx, int ny, int nz,
-                          float threshold, int32_t* vert_count, int32_t* tri_count, int64_t* keys, int32_t* leaks, void* stream);
-int vqn_mc_brick_emit(const float* ub, const int32_t* brick_ijk, int64_t n_bricks, const int32_t* slot, int nx, int ny, int nz,
-                      float threshold, const int32_t* vert_offset, const int32_t* tri_offset, int64_t n_verts, int64_t n_tris,
-                      const float* origin, const float* step, float* verts, int32_t* tris, void* stream);
-
-/* ---- image metrics: PSNR, MSE, SSIM and their luma forms of B image pairs (csrc/image_metrics.hip) ---------------------------------
- * Replaces xiuminglib/metric.py (PSNR, PSNR_luma, SSIM, SSIM_luma, MSE; third party of the reference, its SSIM is tf.image.ssim) for
- * images that are already on the device.  a, b [B][H][W][C], C in {1, 3}: uint8 (_u8), or float32 rows in [0, 1] (_f32) that the
- * kernel quantises as the writer does, (uint8)(clip(x, 0, 1) * 255) in f32.  alpha (may be NULL): f32 plane(s) [H][W], pair i reads
- * alpha + i * alpha_stride (alpha_stride 0: one plane for all pairs, else H * W); every pixel that is NOT alpha > alpha_thres
- * (strict) becomes white in both images before scoring, the evaluator's standard background (metric_eval.py:735-744).
- * SSIM as tf.image.ssim with its defaults: window [11] = the normalised 1-D Gaussian (sigma 1.5) as HOST doubles, applied as its
- * outer product over the (H - 10)(W - 10) 'VALID' positions; c1 = (0.01 * 255)^2, c2 = (0.03 * 255)^2;
- *   luminance = (2 mx my + c1) / (mx^2 + my^2 + c1),  cs = (2 conv(xy) - 2 mx my + c2) / (conv(x^2 + y^2) - mx^2 - my^2 + c2),
- * a channel's score = mean of luminance * cs, the image's = mean over channels.  Luma = 0.2126 R + 0.7152 G + 0.0722 B
- * (xiuminglib/img.py:597-611) of the bytes, unrounded; for C = 1 it is the channel.  All sums and moments are float64.
- * out [B][16] 8-byte words per pair: 0..4 float64 psnr = 10 log10(255^2 / mse) (inf for mse = 0), mse (mean squared 8-bit
- * difference over pixels and channels, from the exact integer sum), psnr_luma, ssim, ssim_luma; 5..9 float64 the SSIM sums of R, G,
- * B and luma and the luma squared error; 10..14 int64 the squared-difference sums of R, G, B, H * W and (H - 10)(W - 10); 15 zero.
- * scratch: vqn_image_metrics_scratch_bytes(B, H, W) bytes (64 per 32 x 32 tile of positions; 0 for a shape the calls refuse); the
- * per-tile sums are added in a fixed order, without atomics: equal inputs give equal bits.  Two launches.  Returns -2 for
- * H < 11 or W < 11 (nothing is launched), C not in {1, 3}, B > 65535; -1 for null pointers or a scratch that is too small; B = 0 is
- * a no-op. */
-int64_t vqn_image_metrics_scratch_bytes(int64_t B, int H, int W);
-int vqn_image_metrics_u8(const uint8_t* a, const uint8_t* b, const float* alpha, int64_t alpha_stride, float alpha_thres, int64_t B,
-                         int H, int W, int C, const double* window, void* scratch, int64_t scratch_bytes, void* out, void* stream);
-int vqn_image_metrics_f32(const float* a, const float* b, const float* alpha, int64_t alpha_stride, float alpha_thres, int64_t B,
-                          int H, int W, int C, const double* window, void* scratch, int64_t scratch_bytes, void* out, void* stream);
-
-/* ---- segmentation scores: contingency table of two label images and the clustering scores (csrc/segmentation_metrics.hip) ---------
- * Replaces the reference's decomp/nerfvq_nfr3/cluster_eval.py (img_embed, correspond, purity and sklearn's f1_score /
- * precision_score / recall_score) for pixels that are on the device.  n pixels, the views of a scene flattened and concatenated;
- * coo[g][p] = counted pixels with ground-truth label g and predicted label p, R = n_gt + 1 rows, C = n_pd + 1 columns, R, C <= 65.
- * _rgb: gt_rgb, pd_rgb uint8 [n][3]; gt_palette [n_gt][3], pd_palette [n_pd][3] HOST bytes; a pixel's label is 1 + the index of the
- * first palette row it equals exactly, 0 when it equals none (class 0 takes part); alpha (may be NULL) f32 [n]: a pixel is counted
- * when alpha > alpha_thres (strict).  _labels: gt, pd int32 [n] with labels in [0, n_gt] and [0, n_pd]; mask (may be NULL) uint8
- * [n]: a pixel is counted when its byte is not 0; a counted pixel with a label outside its range is left out of the table and
- * added to `invalid`.
- * out: (42 + R * C) 8-byte words: 0..4 float64 purity, f1_micro, f1_macro, p_macro, r_macro; 5..8 int64 total (the table's sum),
- * invalid, the number of present rows, the number of present columns (present = non-zero sum); 9..41 int32 label_map[65] plus one
- * zero word of padding: label_map[p] = the row with the largest count in column p, ties to the lowest row, -1 for an absent column
- * and for p >= C; 42.. int64 coo[R][C].
- * Scores (float64, fixed order): purity = sum_p max_g coo[g][p] / total; with M[g][g'] = the sum of coo[g][p] over p with
- * label_map[p] = g', per present row g: tp = M[g][g], pred = sum_r M[r][g], true = sum_c M[g][c], precision = tp / pred (0 when
- * pred = 0), recall = tp / true, f1 = 2 tp / (2 tp + (pred - tp) + (true - tp)); the macro scores are the sums over present rows in
- * ascending order divided by their number; f1_micro = sum tp / total.  total = 0: the five scores are NaN.
- * scratch: vqn_seg_scratch_bytes(n, R, C) bytes (one table of R * C + 1 32-bit words per workgroup, at most 512 workgroups of 4096
- * pixels per pass; 0 for a shape the calls refuse).  No atomics across workgroups; the slots are summed in order: equal inputs give
- * equal bits.  Two launches.  Returns -2 for R or C outside 1 .. 65 or n outside [0, 2^31) (nothing is launched), -1 for null
- * pointers or a scratch that is too small. */
-int64_t vqn_seg_scratch_bytes(int64_t n, int R, int C);
-int vqn_seg_contingency_rgb(const uint8_t* gt_rgb, const uint8_t* pd_rgb, const float* alpha, float alpha_thres, int64_t n,
-                            const uint8_t* gt_palette, int n_gt, const uint8_t* pd_palette, int n_pd, void* scratch,
-                            int64_t scratch_bytes, void* out, void* stream);
-int vqn_seg_contingency_labels(const int32_t* gt, const int32_t* pd, const uint8_t* mask, int64_t n, int n_gt, int n_pd,
-                               void* scratch, int64_t scratch_bytes, void* out, void* stream);
-
-/* ---- mean-shift clustering: the baseline of the segmentation table (csrc/meanshift.hip) ---------------------------------------------
- * Replaces sklearn.cluster.MeanShift as the reference's decomp/nerfvq_nfr3/meanshift.py calls it (flat kernel, every sample a seed
- * unless seeds are given, cluster_all) for features that are on the device.  All features are float64, row-major [rows][D],
- * 1 <= D <= 8, rows >= 1, rows * D < 2^31.  The arithmetic is fixed: d2(x, m) = the sum over d = 0 .. D-1, in that order, of
- * (x_d - m_d) * (x_d - m_d), product and sum rounded separately (no FMA).
- * _seek: every seed to convergence in ONE launch.  Per seed, from m = the seed: neighbours = the points with d2(x, m) <= b * b; none:
- * the seed is dropped (count 0, its mean stays); else m' = sum(neighbours) / their number (a division); it stops when
- * sqrt(d2(m', m)) <= 1e-3 * b or when max_iter iterations are complete, else m = m' and one more iteration is complete.
- * means [n_seeds][D] = the last m', counts = the size of the last neighbour set, iters = the completed iterations.  A seed's
- * neighbour sum is added in an order that depends on the point indices alone (points i with (i mod 256) / 32 = w in ascending i for
- * w = 0 .. 7, then the eight partial sums in that order; no atomics): seeds with equal last neighbour sets get bit-identical means.
- * _merge: candidates [n_candidates][D] with their counts, SORTED by the caller descending by (count, coordinates) (count 0 = dropped,
- * last; exact duplicates may stay).  Walks them in order: a candidate with count > 0 that is not suppressed is kept and suppresses
- * every later one with d2 <= b * b.  kept [n_candidates] bytes 0 / 1, *n_kept their number K (one workgroup, K rounds).
- * scratch: vqn_meanshift_merge_scratch_bytes(n_candidates, D) bytes (a state byte per candidate; 0 for a shape the call refuses).
- * _assign: labels [n] = the index of the centre [K][D] with the least d2, ties to the lowest index; dist (may be NULL) [n] =
- * sqrt of that d2; bandwidth > 0: label -1 where that distance is > bandwidth (cluster_all=False); <= 0: every point is labelled.
- * Return -2 for a shape outside the above (nothing is launched), -1 for null pointers, bandwidth <= 0 (seek, merge), max_iter < 0 or
- * a scratch that is too small. */
-int vqn_meanshift_seek(const double* points, int64_t n, const double* seeds, int64_t n_seeds, int D, double bandwidth, int max_iter,
-                       double* means, int32_t* counts, int32_t* iters, void* stream);
-int64_t vqn_meanshift_merge_scratch_bytes(int64_t n_candidates, int D);
-int vqn_meanshift_merge(const double* candidates, const int32_t* cand_counts, int64_t n_candidates, int D, double bandwidth,
-                        void* scratch, int64_t scratch_bytes, uint8_t* kept, int32_t* n_kept, void* stream);
-int vqn_meanshift_assign(const double* points, int64_t n, const double* centres, int K, int D, double bandwidth, int32_t* labels,
-                         double* dist, void* stream);
-
-/* ---- material selection and editing: pick rows by VQ code and property bounds, replace their material (csrc/material_edit.hip) ------
- * Replaces the selection rule of the reference's decomp/nerfvq_nfr3/ui4_offline.py (map_f) and the six blend statements of its
- * vq_nfr.py:325-330 for rows that are on the device: selection, edit, opt_scale scaling and counts in ONE launch over n rows.
- * planes: HOST array of 8 device pointers, float32 [n][plane_ch[p]] contiguous, plane_ch [8] HOST ints in 1 .. 3 (read for non-null
- * planes), any plane may be NULL.  embed (may be NULL): the code label of a row, int32 [n], or float32 [n] (embed_is_float != 0) rounded
- * to nearest-even as np.rint; labels 0 .. 64 are valid.  mask_in (may be NULL) uint8 [n].
- * Program (all HOST): terms_i [n_terms][4] = plane, channel, denominator channel or -1, condition id; terms_f [n_terms][2] = lo, hi;
- * n_terms <= 32; ops [n_conds - 1], 0 = 'and', 1 = 'or'; n_conds <= 8; codes: 65 bytes, non-zero = the label is in the set, or NULL
- * (no membership test).  A term holds when lo < v < hi, both strict (a NaN fails), v = plane[channel], or with a denominator
- * v = plane[channel] / (plane[denominator] + eps): one correctly rounded f32 add and one correctly rounded f32 divide.  A condition
- * holds when all of its terms hold (each condition has at least one).  m = cond_0, then m = m | cond_i or m & cond_i for i = 1 ..,
- * strictly left to right; then m &= (the row's label is valid and in the set) when codes is given (needs embed); then m &= mask_in != 0
- * when mask_in is given.  Without conditions and codes, m = mask_in != 0; without all three the call is refused.
- * mask_out (may be NULL) uint8 [n]: 0 / 1.
- * Edit (albedo_out NULL: none): albedo, spec [n][3], rough [n][1]; dst HOST [7] = diff[3], spec[3], rough[1]; a material whose FIRST
- * component is negative is left alone; otherwise a selected row takes the constant, any other row keeps its value; written to
- * albedo_out, spec_out, rough_out.  opt_scale (HOST [3], may be NULL; given together with both scaled outputs): albedo_scaled =
- * albedo_out * opt_scale and spec_scaled = spec_out * opt_scale, one rounded f32 multiply.  The selection reads its planes before the
- * edit; outputs must not overlap inputs.
- * counts: int64 [3 + 65]: selected rows, n, invalid (rows whose label is outside 0 .. 64, whenever embed is given; such rows fail the
- * membership test), then the selected rows of each label 0 .. 64 (zero when embed is NULL; an invalid row enters none).  The entry
- * zeroes the row on the stream ahead of the launch; each workgroup (1024 rows per pass, at most 1024 workgroups) reduces in LDS and
- * issues one 64-bit integer atomic per non-zero word.  No scratch, no host read.  n = 0: the row is zeroed, nothing is launched.
- * 16-byte loads and stores when every pointer is 16-byte aligned, row by row otherwise.
- * Returns -2 for n outside [0, 2^31), more than 8 conditions, more than 32 terms or a plane of more than 3 channels; -1 for a term that
- * names a null plane or a channel out of range, a condition without a term, a code set without embed, nothing that selects, or an
- * incomplete edit. */
-int vqn_material_select_edit(const void* const* planes, const int32_t* plane_ch, const void* embed, int embed_is_float,
-                             const uint8_t* mask_in, int64_t n, const int32_t* terms_i, const float* terms_f, int n_terms,
-                             const int32_t* ops, int n_conds, const uint8_t* codes, float eps, const float* albedo, const float* spec,
-                             const float* rough, const float* dst, const float* opt_scale, float* albedo_out, float* spec_out,
-                             float* rough_out, float* albedo_scaled, float* spec_scaled, uint8_t* mask_out, int64_t* counts,
-                             void* stream);
-
-/* ---- baseline JPEG of 8-bit frames that are on the device (csrc/jpeg_encode.hip; host side csrc/jpeg_plan.h) -------------------------
- * Replaces the per-frame image files and cv2.VideoWriter('MJPG') of the reference's cv2_render.py for frames that the render left on
- * the device (decomp/nerfactor/util/mjpeg.py, decomp/video.py).  SOF0, 8 bit, Y Cb Cr, JFIF; subsampling 420 (MCU 16 x 16: Y00 Y01 Y10
- * Y11 Cb Cr) or 444 (MCU 8 x 8); frames padded to whole MCUs by repeating their last row and column; JFIF full-range BT.601 in f32, planes
- * not rounded, 420 chroma the mean of each 2 x 2 square; level shift, orthonormal 8 x 8 DCT-II in f32; the Annex K tables scaled by
- * `quality` with the IJG rule, rounding half away from zero; the Annex K Huffman tables; a restart interval of `restart_interval` MCUs,
- * every interval coded on its own (predictors 0, padded with 1-bits, byte-stuffed), RSTm between the intervals of a frame.
- * vqn_jpeg_plan (host only, no device): geom (may be NULL) receives the 24 int64 words of JpegGeom (csrc/jpeg_plan.h: among them the
- * block counts of the planes, the restart intervals of a frame, the slot size, the byte offsets of the scratch regions, scratch_bytes,
- * out_bytes, header_bytes); header (may be NULL) the bytes of a file from SOI through SOS, header_cap >= 1024 always suffices.
- * vqn_jpeg_encode: rgb uint8 [n][h][w][3]; scratch: 16-byte aligned, scratch_bytes of the plan (with coefficients_only != 0 the bytes
- * in front of off_slots suffice, only the first kernel runs, and out / meta may be NULL).  It then holds the quantised coefficients,
- * int16 in zigzag order: Y [n][by_y][bx_y][64] at 0, Cb and Cr [n][by_c][bx_c][64] at off_cb and off_cr.  out: out_bytes of the plan
- * (the worst case: no content needs more); meta int64 [n][2] = offset and length of each frame's bytes in `out`, the bytes between
- * the SOS segment and EOI, RST markers included.  Five launches, no host read; equal frames give equal bytes.
- * Refused with the reason in vqn_last_error and nothing launched: -1 for n < 1, a zero side, quality outside 1 .. 100, a
- * restart interval outside 1 .. 65535, an unknown subsampling, buffers smaller than the plan's; -2 for a side over 65535 (and, by
- * vqn_jpeg_encode, for more than 65535 frames in one batch: the grid's second dimension). */
-int vqn_jpeg_plan(int64_t n, int64_t h, int64_t w, int quality, int subsampling, int64_t restart_interval, int64_t* geom, uint8_t* header,
-                  int header_cap);
-int vqn_jpeg_encode(const uint8_t* rgb, int64_t n, int64_t h, int64_t w, int quality, int subsampling, int64_t restart_interval,
-                    void* scratch, int64_t scratch_bytes, uint8_t* out, int64_t out_bytes, int64_t* meta, int coefficients_only,
-                    void* stream);
-
-/* ---- PNG files of 8-bit images that are on the device (csrc/png_encode.hip; host side csrc/png_plan.h) -------------------------------
- * Replaces the host PNG writer (PIL) on the output path for images the render left on the device (decomp/nerfactor/util/png.py,
- * vis.vis_batch(png='device')).  8 bit, c = 1 / 2 / 3 / 4 channels (colour type 0 / 4 / 2 / 6), no interlace.  filter_mode 0 .. 4
- * forces none / sub / up / average / paeth for every row, 5 picks per row the type with the smallest sum of |residual as int8| (the
- * lower type on a tie).  The filtered stream of an image (row y: the type, then w c bytes) is cut into segments of rows_per_segment
- * whole rows (more rows than the image has: the image); a segment is one deflate block, coded alone: greedy tokens from the
- * distances 1, 2, 3, 4, 6, 8, stride - c, stride, stride + c (the longest match, the earlier candidate on a tie, at least 3 bytes),
- * under the cheapest of the 14 prefabricated dynamic tables of csrc/png_plan.h, fixed Huffman or stored (the earlier on a tie); a
- * Huffman block is followed by an empty stored block, so every segment ends on a byte boundary; BFINAL on the last block of the image.
- * vqn_png_plan (host only, no device): geom (may be NULL) receives the 17 int64 words of PngGeom (csrc/png_plan.h: the row stride, the
- * segments of an image, the slot size, the byte offsets of the scratch regions, scratch_bytes, out_bytes); head (may be NULL) the 33
- * bytes of a file in front of its IDAT chunk (signature, IHDR with its CRC), head_cap >= 33.
- * vqn_png_encode: pix uint8 [n][h][w][c]; scratch: 16-byte aligned, scratch_bytes of the plan (with filtered_only != 0 the n h stride
- * bytes of the filtered stream suffice, only the first kernel runs, and out / meta may be NULL).  It then holds the filtered stream
- * [n][h][stride] at 0.  out: out_bytes of the plan (every segment stored: no content needs more); meta int64 [n][2] = offset and
- * length of each image's zlib stream in `out` (78 01, the blocks, the Adler-32): the data of its IDAT chunk, whose CRC the caller
- * takes.  Four launches, no host read; equal images give equal bytes.
- * Refused with the reason in vqn_last_error and nothing launched: -1 for n < 1, a zero side, c outside 1 .. 4, an unknown filter mode,
- * rows_per_segment < 1, buffers smaller than the plan's; -2 for a segment (so also a row) over 65535 bytes, more than 65535 images in
- * a batch (the grids' second dimension), more than 2^24 rows. */
-int vqn_png_plan(int64_t n, int64_t h, int64_t w, int64_t c, int filter_mode, int64_t rows_per_segment, int64_t* geom, uint8_t* head,
-                 int head_cap);
-int vqn_png_encode(const uint8_t* pix, int64_t n, int64_t h, int64_t w, int64_t c, int filter_mode, int64_t rows_per_segment,
-                   void* scratch, int64_t scratch_bytes, uint8_t* out, int64_t out_bytes, int64_t* meta, int filtered_only,
-                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,10 @@
  *     vqn_last_error() returns the thread-local message of the last failure
  *   - re-entrant; no global mutable state besides that thread-local string
  *   - all floating point is fp32, indices are int64, tensors are dense row-major
+ *
+ * This header declares the library's first 91 functions and stays at that.  The later areas have a header each, under the same
+ * conventions: vqn_neus_fold.h (the folded colour pack), vqn_mesh.h (mesh export), vqn_eval.h (image metrics, segmentation scores,
+ * mean shift), vqn_material_edit.h, vqn_image_codec.h (JPEG and PNG of device frames).
  */
 #ifndef VQNERF_HIP_H_
 #define VQNERF_HIP_H_

@@ -1,24 +1,16 @@
 """CPU: the C-ABI library builds, loads, and exports every symbol include/vqnerf_hip.h declares."""
 import ctypes
 import os
-import re
 
+from tests import abi_headers
 from vqnerf_release_amd import _C
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared():
-    txt = open(os.path.join(ROOT, 'include', 'vqnerf_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    return sorted(set(re.findall(r'\b(vqn_[a-z0-9_]+)\s*\(', txt)))
 
 
 def test_library_exports_every_declared_symbol():
     if not os.path.exists(_C.LIB_PATH):
         _C.build()
     lib = ctypes.CDLL(_C.LIB_PATH)
-    names = _declared()
+    names = sorted(abi_headers.prototypes('vqnerf_hip.h'))
     assert len(names) >= 4
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing

@@ -1,36 +1,15 @@
 """CPU: the package's ctypes binding (vqnerf_release_amd/_C.py) -- its signature table against include/vqnerf_hip.h, and the one scratch
 policy of the fused kernels."""
 import os
-import re
 
 import torch
 
+from tests import abi_headers
 from vqnerf_release_amd import _C
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _kind(decl, is_return=False):
-    """kind code of a C type (a parameter declaration with or without its name)"""
-    if '*' in decl:
-        return 's' if is_return and 'char' in decl else 'p'
-    words = decl.replace('const', ' ').split()
-    return {'int': 'i', 'int32_t': 'i', 'int64_t': 'l', 'float': 'f', 'double': 'd', 'void': 'v'}[words[0]]
-
-
-def _prototypes():
-    txt = open(os.path.join(ROOT, 'include', 'vqnerf_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', ' ', txt, flags=re.S)
-    txt = re.sub(r'^\s*#.*$', ' ', txt, flags=re.M)
-    out = {}
-    for ret, name, params in re.findall(r'([\w\s*]+?)\s*\b(vqn_\w+)\s*\(([^)]*)\)\s*;', txt):
-        params = [p for p in params.split(',') if p.strip() not in ('', 'void')]
-        out[name] = (_kind(ret, True), ''.join(_kind(p) for p in params))
-    return out
 
 
 def test_signature_table_matches_the_header():
-    declared = _prototypes()
+    declared = abi_headers.prototypes('vqnerf_hip.h')
     assert len(declared) == 91
     assert sorted(_C.ABI) == sorted(declared)
     wrong = {n: (_C.ABI[n], declared[n]) for n in declared if _C.ABI[n] != declared[n]}

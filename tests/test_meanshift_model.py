@@ -85,8 +85,9 @@ def test_duplicate_points_count_as_often_as_they_occur():
 
 def test_binding_table_has_the_mean_shift_rows():
     from vqnerf_release_amd import _C
-    assert _C.ABI_FOLD['vqn_meanshift_seek'] == ('i', 'plplidipppp') and _C.ABI_FOLD['vqn_meanshift_merge_scratch_bytes'] == ('l', 'li')
-    assert _C.ABI_FOLD['vqn_meanshift_merge'] == ('i', 'pplidplppp') and _C.ABI_FOLD['vqn_meanshift_assign'] == ('i', 'plpiidppp')
+    table = _C.ABI_BY_HEADER['vqn_eval.h']
+    assert table['vqn_meanshift_seek'] == ('i', 'plplidipppp') and table['vqn_meanshift_merge_scratch_bytes'] == ('l', 'li')
+    assert table['vqn_meanshift_merge'] == ('i', 'pplidplppp') and table['vqn_meanshift_assign'] == ('i', 'plpiidppp')
     assert (_C.MEANSHIFT_POINTS_PER_TILE, _C.MEANSHIFT_SEEDS_PER_GROUP, _C.MEANSHIFT_MAX_DIM) == (256, 64, 8)
 
 

@@ -65,10 +65,10 @@ def test_centres_are_grid_points_and_the_radius_covers_every_stored_point(R):
 
 
 def test_the_new_entry_points_are_declared_in_both_places():
-    from tests.test_neus_fold_binding import _prototypes
-    declared = _prototypes('vqn_neus_fold.h')
+    from tests import abi_headers
+    declared = abi_headers.prototypes('vqn_mesh.h')
     for name in ('vqn_mc_brick_points', 'vqn_mc_brick_classify', 'vqn_mc_brick_emit'):
-        assert name in declared and _C.ABI_FOLD[name] == declared[name] and name not in _C.ABI
+        assert name in declared and _C.ABI_BY_HEADER['vqn_mesh.h'][name] == declared[name] and name not in _C.ABI
 
 
 def test_sparse_needs_the_device_route():

@@ -129,14 +129,14 @@ def test_statement_against_scikit_learn(seed):
 
 
 def test_the_three_prototypes_equal_their_abi_rows():
-    from tests.test_neus_fold_binding import _prototypes
+    from tests import abi_headers
     from vqnerf_release_amd import _C
-    declared = _prototypes('vqn_neus_fold.h')
+    declared, table = abi_headers.prototypes('vqn_eval.h'), _C.ABI_BY_HEADER['vqn_eval.h']
     names = ('vqn_seg_scratch_bytes', 'vqn_seg_contingency_rgb', 'vqn_seg_contingency_labels')
     for name in names:
-        assert declared[name] == _C.ABI_FOLD[name], name
-    assert _C.ABI_FOLD['vqn_seg_scratch_bytes'] == ('l', 'lii')
-    assert _C.ABI_FOLD['vqn_seg_contingency_rgb'][1].endswith('p') and _C.ABI_FOLD['vqn_seg_contingency_labels'][0] == 'i'
+        assert declared[name] == table[name], name
+    assert table['vqn_seg_scratch_bytes'] == ('l', 'lii')
+    assert table['vqn_seg_contingency_rgb'][1].endswith('p') and table['vqn_seg_contingency_labels'][0] == 'i'
 
 
 def test_the_package_palettes_are_the_statement_s():

@@ -1,8 +1,8 @@
-"""ctypes binding of libvqnerf_hip.so (include/vqnerf_hip.h, include/vqn_neus_fold.h).
+"""ctypes binding of libvqnerf_hip.so (include/vqnerf_hip.h and the area headers beside it: ABI_BY_HEADER).
 
 There is NO fallback: if the library is missing or a call fails this raises.  Tensors are passed as
 raw device pointers (tensor.data_ptr()) plus sizes; work is enqueued on torch's current HIP stream.
-This is the package's only door to the library: every entry point is declared in ABI (ABI_FOLD) and launched through _call.
+This is the package's only door to the library: every entry point is declared in a table of ABI_BY_HEADER and launched through _call.
 """
 import contextlib
 import ctypes
@@ -18,7 +18,7 @@ _lib = None
 
 # Every function of include/vqnerf_hip.h as `R name(A...)`, one code per type: p pointer (device or host, None = NULL), i int /
 # int32_t, l int64_t, f float, d double, and for returns s const char* and v void.  lib() installs them as restype / argtypes;
-# tests/test_binding.py holds the table to the header.
+# tests/test_abi_headers.py holds every table to its header.
 _ABI = """
 i vqn_version()  s vqn_last_error()  i vqn_vq_assign(plipipppppp)  i vqn_vq_assign_variant(iiii)  i vqn_vq_ema_stats(ppliippplp)
 l vqn_vq_ema_stats_ws_bytes(lii)  i vqn_vq_ste_loss(pplfpppp)  i vqn_vq_ema_update(pppiidfpppppppp)
@@ -48,20 +48,26 @@ i vqn_ks_split_bwd(ppilppppp)  i vqn_wgrad_thin_batched(ippppppppplippp)  i vqn_
 i vqn_refl_train_fwd_x3(ppppplpippiip)  i vqn_refl_train_fwd_x3_zx(pppppplpipppiip)  l vqn_refl_train_bwd_x3_scratch_bytes(p)
 i vqn_refl_train_bwd_x3(ppplpppipipippiiiplp)  i vqn_adam_step(ippppppppdddddiip)
 """
-ABI = {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', _ABI)}
-# ... and the functions of include/vqn_neus_fold.h (the fold pack, the mesh export, dense and on bricks, the image and the segmentation metrics, mean shift, the material edit, the JPEG and the PNG encoder), in the same code
-# (tests/test_neus_fold_binding.py holds them to that header)
-ABI_FOLD = {'vqn_neus_fold_pack': ('l', 'ppplppiippiplpp'), 'vqn_mc_classify': ('i', 'piiifppp'), 'vqn_mc_emit': ('i', 'piiifppllppppp'),
-            'vqn_mesh_components': ('i', 'pllpp'), 'vqn_mesh_remap_tris': ('i', 'plppplplp'),
-            'vqn_mc_brick_points': ('i', 'pppiiiplllpp'), 'vqn_mc_brick_classify': ('i', 'pplpiiifppppp'),
-            'vqn_mc_brick_emit': ('i', 'pplpiiifppllppppp'), 'vqn_image_metrics_scratch_bytes': ('l', 'lii'),
-            'vqn_image_metrics_u8': ('i', 'ppplfliiipplpp'), 'vqn_image_metrics_f32': ('i', 'ppplfliiipplpp'),
-            'vqn_seg_scratch_bytes': ('l', 'lii'), 'vqn_seg_contingency_rgb': ('i', 'pppflpipiplpp'),
-            'vqn_seg_contingency_labels': ('i', 'pppliiplpp'), 'vqn_meanshift_seek': ('i', 'plplidipppp'),
-            'vqn_meanshift_merge_scratch_bytes': ('l', 'li'), 'vqn_meanshift_merge': ('i', 'pplidplppp'),
-            'vqn_meanshift_assign': ('i', 'plpiidppp'), 'vqn_material_select_edit': ('i', 'pppiplppipipfppppppppppppp'),
-            'vqn_jpeg_plan': ('i', 'llliilppi'), 'vqn_jpeg_encode': ('i', 'pllliilplplpip'),
-            'vqn_png_plan': ('i', 'llllilppi'), 'vqn_png_encode': ('i', 'pllllilplplpip')}
+# One table per public header of include/, in the same notation.  A new header is one more entry here: lib() installs whatever
+# ABI_BY_HEADER holds.
+_ABI_TEXT = {
+    'vqnerf_hip.h': _ABI,
+    'vqn_neus_fold.h': 'l vqn_neus_fold_pack(ppplppiippiplpp)',
+    'vqn_mesh.h': """
+i vqn_mc_classify(piiifppp)  i vqn_mc_emit(piiifppllppppp)  i vqn_mesh_components(pllpp)  i vqn_mesh_remap_tris(plppplplp)
+i vqn_mc_brick_points(pppiiiplllpp)  i vqn_mc_brick_classify(pplpiiifppppp)  i vqn_mc_brick_emit(pplpiiifppllppppp)""",
+    'vqn_eval.h': """
+l vqn_image_metrics_scratch_bytes(lii)  i vqn_image_metrics_u8(ppplfliiipplpp)  i vqn_image_metrics_f32(ppplfliiipplpp)
+l vqn_seg_scratch_bytes(lii)  i vqn_seg_contingency_rgb(pppflpipiplpp)  i vqn_seg_contingency_labels(pppliiplpp)
+i vqn_meanshift_seek(plplidipppp)  l vqn_meanshift_merge_scratch_bytes(li)  i vqn_meanshift_merge(pplidplppp)
+i vqn_meanshift_assign(plpiidppp)""",
+    'vqn_material_edit.h': 'i vqn_material_select_edit(pppiplppipipfppppppppppppp)',
+    'vqn_image_codec.h': """
+i vqn_jpeg_plan(llliilppi)  i vqn_jpeg_encode(pllliilplplpip)  i vqn_png_plan(llllilppi)  i vqn_png_encode(pllllilplplpip)""",
+}
+ABI_BY_HEADER = {header: {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', text)}
+                 for header, text in _ABI_TEXT.items()}
+ABI = ABI_BY_HEADER['vqnerf_hip.h']
 _CTYPES = dict(p=ctypes.c_void_p, i=ctypes.c_int, l=ctypes.c_int64, f=ctypes.c_float, d=ctypes.c_double, s=ctypes.c_char_p, v=None)
 
 
@@ -85,9 +91,10 @@ def lib():
             raise VqnError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                            '(or `make -C vqnerf_release_amd/csrc`). There is no non-HIP fallback.')
         L = ctypes.CDLL(LIB_PATH)
-        for name, (ret, args) in list(ABI.items()) + list(ABI_FOLD.items()):
-            f = getattr(L, name)
-            f.restype, f.argtypes = _CTYPES[ret], [_CTYPES[a] for a in args]
+        for table in ABI_BY_HEADER.values():
+            for name, (ret, args) in table.items():
+                f = getattr(L, name)
+                f.restype, f.argtypes = _CTYPES[ret], [_CTYPES[a] for a in args]
         _lib = L
     return _lib
 
@@ -706,7 +713,10 @@ def mesh_remap_tris(triangles, keep_tri, tri_offset, new_index, n_out):
 
 
 # mesh export on a sparse set of bricks (csrc/marching_cubes_bricks.hip; geo/mesh.py)
-BRICK_POINTS = 729            # stored points of a brick: 9^3
+# (this and every block of constants below: the #defines of the area's header, include/vqn_mesh.h here; tests/test_abi_headers.py
+# holds them equal)
+BRICK_CELLS = 8               # cells per brick and axis (VQN_MC_BRICK_CELLS)
+BRICK_POINTS = 729            # stored points of a brick: 9^3 (VQN_MC_BRICK_POINTS)
 
 
 def _mc_bricks(ub, brick_ijk, slot, dims):
@@ -724,7 +734,7 @@ def _mc_bricks(ub, brick_ijk, slot, dims):
     if slot is not None:
         n_slots = 1
         for d in (nx, ny, nz):
-            n_slots *= max(1, -(-(d - 1) // 8))                          # (a dimension < 2 is the library's to refuse)
+            n_slots *= max(1, -(-(d - 1) // BRICK_CELLS))                         # (a dimension < 2 is the library's to refuse)
         if slot.dtype != torch.int32 or not slot.is_contiguous() or slot.device != brick_ijk.device or slot.numel() != n_slots:
             raise VqnError(f'marching cubes on bricks: slot must be a contiguous int32 tensor with one entry per brick of the grid '
                            f'({n_slots}) on the device of brick_ijk')
@@ -782,7 +792,11 @@ def mc_brick_emit(ub, brick_ijk, slot, dims, threshold, vert_offset, tri_offset,
 
 
 # --------------------------------------------------------------------------------------
-# image metrics (csrc/image_metrics.hip; decomp/nerfactor/util/metric.py)
+# image metrics (csrc/image_metrics.hip, include/vqn_eval.h; decomp/nerfactor/util/metric.py)
+IMAGE_METRICS_WINDOW = 11      # weights of the SSIM window (VQN_IMAGE_METRICS_WINDOW)
+IMAGE_METRICS_OUT_WORDS = 16   # 8-byte words of the output per image pair (VQN_IMAGE_METRICS_OUT_WORDS)
+
+
 def image_metrics(a, b, window, alpha=None, alpha_thres=0.0):
     """a, b [B,H,W,C] contiguous device tensors, both uint8 or both float32 (rows in [0, 1], quantised by the kernel), C in {1, 3};
     window: the 11 normalised weights (host doubles); alpha: float32 [H,W] (one plane for all pairs) or [B,H,W], pixels that are
@@ -799,7 +813,7 @@ def image_metrics(a, b, window, alpha=None, alpha_thres=0.0):
         if alpha.device != a.device or tuple(alpha.shape) not in ((H, W), (B, H, W)):
             raise VqnError(f'image_metrics: alpha must be [H, W] or [B, H, W] on the device of the images, got {tuple(alpha.shape)}')
         stride = H * W if alpha.dim() == 3 else 0
-    out = torch.empty((B, 16), dtype=torch.int64, device=a.device)
+    out = torch.empty((B, IMAGE_METRICS_OUT_WORDS), dtype=torch.int64, device=a.device)
     entry = 'vqn_image_metrics_u8' if a.dtype == torch.uint8 else 'vqn_image_metrics_f32'
     need = lib().vqn_image_metrics_scratch_bytes(B, H, W)
     buf = _scratch('image_metrics', max(need, 64), a.device)           # (need = 0: a shape the call itself refuses, with the reason)
@@ -809,11 +823,11 @@ def image_metrics(a, b, window, alpha=None, alpha_thres=0.0):
 
 
 # --------------------------------------------------------------------------------------
-# segmentation scores (csrc/segmentation_metrics.hip; decomp/nerfactor/util/segmentation.py)
-SEG_PIXELS_PER_PASS = 4096     # pixels a workgroup takes per pass (kPass of the kernel)
-SEG_GRID_CAP = 512             # workgroups at most (kGridCap)
-SEG_MAX_SIDE = 65              # table sides R = n_gt + 1, C = n_pd + 1 at most
-SEG_HEAD_WORDS = 42            # 8-byte words of the output row ahead of the table
+# segmentation scores (csrc/segmentation_metrics.hip, include/vqn_eval.h; decomp/nerfactor/util/segmentation.py)
+SEG_PIXELS_PER_PASS = 4096     # pixels a workgroup takes per pass (VQN_SEG_PIXELS_PER_PASS)
+SEG_GRID_CAP = 512             # workgroups at most (VQN_SEG_GRID_CAP)
+SEG_MAX_SIDE = 65              # table sides R = n_gt + 1, C = n_pd + 1 at most (VQN_SEG_MAX_SIDE)
+SEG_HEAD_WORDS = 42            # 8-byte words of the output row ahead of the table (VQN_SEG_HEAD_WORDS)
 
 
 def segmentation_counts(gt, pd, sel=None, alpha_thres=0.0, gt_palette=None, pd_palette=None, n_gt=None, n_pd=None):
@@ -821,7 +835,7 @@ def segmentation_counts(gt, pd, sel=None, alpha_thres=0.0, gt_palette=None, pd_p
     Colour form: gt, pd uint8 [n, 3] contiguous device tensors, gt_palette [n_gt, 3] and pd_palette [n_pd, 3] host uint8 arrays,
     sel = alpha float32 [n] or None (counted: alpha > alpha_thres, strict).  Label form: gt, pd int32 [n], n_gt and n_pd the largest
     labels, sel = mask uint8 [n] or None (counted: mask != 0).
-    -> int64 [42 + R * C], the words of vqn_seg_contingency_rgb's `out` (include/vqn_neus_fold.h)."""
+    -> int64 [42 + R * C], the words of vqn_seg_contingency_rgb's `out` (include/vqn_eval.h)."""
     colour = gt.dtype == torch.uint8
     want = 2 if colour else 1
     if gt.dtype != pd.dtype or gt.dtype not in (torch.uint8, torch.int32) or gt.shape != pd.shape or gt.dim() != want \
@@ -856,14 +870,14 @@ def segmentation_counts(gt, pd, sel=None, alpha_thres=0.0, gt_palette=None, pd_p
 
 
 # --------------------------------------------------------------------------------------
-# material selection and editing (csrc/material_edit.hip; decomp/nerfactor/util/material_edit.py)
-MATEDIT_ROWS_PER_PASS = 1024   # rows a workgroup takes per pass (kPass of the kernel)
-MATEDIT_GRID_CAP = 1024        # workgroups at most (kGridCap)
-MATEDIT_MAX_PLANES = 8         # property planes at most, of 1 .. 3 channels each
-MATEDIT_MAX_TERMS = 32         # terms of a program at most
-MATEDIT_MAX_CONDS = 8          # conditions of a program at most
-MATEDIT_HEAD_WORDS = 3         # words of the counts row ahead of the 65 per-code counts: selected, rows, invalid
-MATEDIT_CODES = 65             # code labels 0 .. 64
+# material selection and editing (csrc/material_edit.hip, include/vqn_material_edit.h; decomp/nerfactor/util/material_edit.py)
+MATEDIT_ROWS_PER_PASS = 1024   # rows a workgroup takes per pass (VQN_MATEDIT_ROWS_PER_PASS)
+MATEDIT_GRID_CAP = 1024        # workgroups at most (VQN_MATEDIT_GRID_CAP)
+MATEDIT_MAX_PLANES = 8         # property planes at most, of 1 .. 3 channels each (VQN_MATEDIT_MAX_PLANES)
+MATEDIT_MAX_TERMS = 32         # terms of a program at most (VQN_MATEDIT_MAX_TERMS)
+MATEDIT_MAX_CONDS = 8          # conditions of a program at most (VQN_MATEDIT_MAX_CONDS)
+MATEDIT_HEAD_WORDS = 3         # words of the counts row ahead of the 65 per-code counts: selected, rows, invalid (VQN_MATEDIT_HEAD_WORDS)
+MATEDIT_CODES = 65             # code labels 0 .. 64 (VQN_MATEDIT_CODES)
 
 
 def _overlap(a, b):
@@ -874,7 +888,7 @@ def _overlap(a, b):
 
 def material_select_edit(n, planes=(), embed=None, mask_in=None, terms=(), ops=(), n_conds=0, codes=None, eps=5e-6, edit=None, dst=None,
                          opt_scale=None, out=None, want_mask=True, device=None):
-    """Selection, material edit, opt_scale scaling and counts of n rows in ONE launch (include/vqn_neus_fold.h), no host read.
+    """Selection, material edit, opt_scale scaling and counts of n rows in ONE launch (include/vqn_material_edit.h), no host read.
     planes: up to 8 float32 [n, ch] (ch <= 3) contiguous device tensors or None; embed: int32 [n] or float32 [n] or None; mask_in:
     uint8 [n] or None.  terms: rows (plane, channel, denominator channel or -1, lo, hi, condition id); ops: 0 'and' / 1 'or', one
     fewer than n_conds; codes: the labels of the set (each in 0 .. 64) or None.  edit = (albedo [n, 3], spec [n, 3], rough [n, 1])
@@ -960,16 +974,18 @@ def material_select_edit(n, planes=(), embed=None, mask_in=None, terms=(), ops=(
 
 
 # --------------------------------------------------------------------------------------
-# mean-shift clustering (csrc/meanshift.hip; decomp/nerfactor/util/meanshift.py)
-MEANSHIFT_MAX_DIM = 8              # features per point at most (kMaxD)
-MEANSHIFT_POINTS_PER_TILE = 256    # points the seek kernel stages in LDS per pass (kSeekTile)
-MEANSHIFT_SEEDS_PER_GROUP = 64     # seeds a seek workgroup owns (kSeekSeeds)
-MEANSHIFT_ASSIGN_SPAN = 256        # points an assign workgroup labels per pass (kAssignThreads)
-MEANSHIFT_ASSIGN_CENTRES = 512     # centres the assign kernel holds in LDS at a time (kAssignCentres)
+# mean-shift clustering (csrc/meanshift.hip, include/vqn_eval.h; decomp/nerfactor/util/meanshift.py)
+MEANSHIFT_MAX_DIM = 8              # features per point at most (VQN_MEANSHIFT_MAX_DIM)
+MEANSHIFT_POINTS_PER_TILE = 256    # points the seek kernel stages in LDS per pass (VQN_MEANSHIFT_POINTS_PER_TILE)
+MEANSHIFT_SEEDS_PER_GROUP = 64     # seeds a seek workgroup owns (VQN_MEANSHIFT_SEEDS_PER_GROUP)
+MEANSHIFT_ASSIGN_SPAN = 256        # points an assign workgroup labels per pass (VQN_MEANSHIFT_ASSIGN_SPAN)
+MEANSHIFT_ASSIGN_CENTRES = 512     # centres the assign kernel holds in LDS at a time (VQN_MEANSHIFT_ASSIGN_CENTRES)
 
 
 # --------------------------------------------------------------------------------------
-# baseline JPEG of device frames (csrc/jpeg_encode.hip, csrc/jpeg_plan.h; decomp/nerfactor/util/mjpeg.py)
+# baseline JPEG of device frames (csrc/jpeg_encode.hip, csrc/jpeg_plan.h, include/vqn_image_codec.h; decomp/nerfactor/util/mjpeg.py)
+JPEG_HEADER_CAP = 1024             # bytes a header never reaches (VQN_JPEG_HEADER_CAP)
+# the fields of struct VqnJpegGeom, in order
 JPEG_GEOM = ('n', 'h', 'w', 'quality', 'sub', 'ri', 'mcu', 'mcus_x', 'mcus_y', 'blocks_per_mcu', 'intervals', 'slot_bytes', 'by_y', 'bx_y',
              'by_c', 'bx_c', 'off_cb', 'off_cr', 'off_slots', 'off_lens', 'off_dst', 'scratch_bytes', 'out_bytes', 'header_bytes')
 
@@ -978,7 +994,7 @@ def jpeg_plan(n, h, w, quality, subsampling, restart_interval):
     """The planner's view of a batch (host only): ({name: int} over JPEG_GEOM, the header bytes SOI .. SOS).  subsampling 420 or 444.
     A batch it refuses raises ValueError with its reason."""
     geom = np.zeros(len(JPEG_GEOM), np.int64)
-    header = np.zeros(1024, np.uint8)
+    header = np.zeros(JPEG_HEADER_CAP, np.uint8)
     rc = lib().vqn_jpeg_plan(int(n), int(h), int(w), int(quality), int(subsampling), int(restart_interval), geom.ctypes.data,
                              header.ctypes.data, header.size)
     if rc != 0:
@@ -1000,18 +1016,20 @@ def jpeg_encode(frames, g, scratch, out=None, meta=None):
           _ptr(out), 0 if only else out.numel(), _ptr(meta), int(only))
 
 
-# PNG files of device images (csrc/png_encode.hip, csrc/png_plan.h; decomp/nerfactor/util/png.py)
+# PNG files of device images (csrc/png_encode.hip, csrc/png_plan.h, include/vqn_image_codec.h; decomp/nerfactor/util/png.py)
+# the fields of struct VqnPngGeom, in order
 PNG_GEOM = ('n', 'h', 'w', 'c', 'filter_mode', 'rows_per_segment', 'stride', 'segments', 'segment_bytes', 'slot_bytes', 'off_slots',
             'off_lens', 'off_adler', 'off_dst', 'off_sums', 'scratch_bytes', 'out_bytes')
-PNG_FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': 5}
-PNG_SEGMENT_TARGET = 8192          # bytes a default segment holds at most, in whole rows (kPngSegmentTarget)
+PNG_FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': 5}    # 'adaptive': VQN_PNG_FILTER_ADAPTIVE
+PNG_SEGMENT_TARGET = 8192          # bytes a default segment holds at most, in whole rows (VQN_PNG_SEGMENT_TARGET)
+PNG_HEAD_BYTES = 33                # bytes of a file in front of IDAT (VQN_PNG_HEAD_BYTES)
 
 
 def png_plan(n, h, w, c, filter_mode, rows_per_segment):
     """The planner's view of a batch (host only): ({name: int} over PNG_GEOM, the 33 bytes of a file in front of IDAT).  filter_mode:
     a value of PNG_FILTERS.  A batch it refuses raises ValueError with its reason."""
     geom = np.zeros(len(PNG_GEOM), np.int64)
-    head = np.zeros(33, np.uint8)
+    head = np.zeros(PNG_HEAD_BYTES, np.uint8)
     rc = lib().vqn_png_plan(int(n), int(h), int(w), int(c), int(filter_mode), int(rows_per_segment), geom.ctypes.data, head.ctypes.data,
                             head.size)
     if rc != 0:

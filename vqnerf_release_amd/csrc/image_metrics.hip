@@ -24,20 +24,20 @@
 // All LDS accesses of the two passes are lane-consecutive 8-byte words (ds_read_b64 / ds_write_b64: conflict-free within each
 // 32-lane half whatever the row stride).
 #include "common.h"
-#include "vqn_neus_fold.h"
+#include "vqn_eval.h"
 
 // every product and sum below is rounded on its own (the statement's PSNR is matched bit for bit); fma() is written where wanted
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kWin = 11, kHalo = kWin - 1;
+constexpr int kWin = VQN_IMAGE_METRICS_WINDOW, kHalo = kWin - 1;
 constexpr int kTile = 32;                    // window positions per tile edge
 constexpr int kIn = kTile + kHalo;           // 42 pixels per tile edge
 constexpr int kThreads = 256;
 constexpr int kPix = (kIn * kIn + kThreads - 1) / kThreads;      // 7 pixels per thread
 constexpr int kSlots = 8;                    // 8-byte words per tile in scratch: ssim[4], luma se, sse[3]
-constexpr int kOutWords = 16;                // 8-byte words per pair in `out`
+constexpr int kOutWords = VQN_IMAGE_METRICS_OUT_WORDS;   // 8-byte words per pair in `out`
 
 struct ImArgs {
   const void* a;

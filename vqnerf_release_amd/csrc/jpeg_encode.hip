@@ -28,7 +28,7 @@
 // Everything is integer work or f32 arithmetic in a fixed order: equal frames give equal bytes.
 #include "common.h"
 #include "jpeg_plan.h"
-#include "vqn_neus_fold.h"
+#include "vqn_image_codec.h"
 
 #pragma clang fp contract(off)
 
@@ -395,7 +395,7 @@ int plan_or_refuse(const char* fn, int64_t n, int64_t h, int64_t w, int quality,
 
 }  // namespace
 
-static_assert(kJpegGeomWords == 24, "include/vqn_neus_fold.h and _C.JPEG_GEOM state 24 words");
+static_assert(kJpegGeomWords == 24, "include/vqn_image_codec.h documents VqnJpegGeom as 24 words");
 
 extern "C" int vqn_jpeg_plan(int64_t n, int64_t h, int64_t w, int quality, int subsampling, int64_t restart_interval, int64_t* geom,
                              uint8_t* header, int header_cap) {

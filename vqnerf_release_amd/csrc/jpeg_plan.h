@@ -9,10 +9,12 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "../../include/vqn_image_codec.h"  // (by path: the stand-alone build of this header names no include directory)
+
 constexpr int kJpegMaxSide = 65535;
 constexpr int kJpegBlockBits = 64 * 26;                  // the most a block codes to: 64 coefficients of a 16-bit code + 10 bits
 constexpr int kJpegBlockBytes = kJpegBlockBits / 8 * 2;  // ... in bytes, doubled: every byte may be an FF that is stuffed
-constexpr int kJpegHeaderCap = 1024;                     // bytes a header never reaches (it has 629)
+constexpr int kJpegHeaderCap = VQN_JPEG_HEADER_CAP;      // bytes a header never reaches (it has 629)
 
 // zigzag position -> natural index (row * 8 + column)
 static const uint8_t kJpegZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -58,16 +60,9 @@ struct JpegHuff {
   uint32_t ac[2][256];
 };
 
-// The geometry of a batch, as int64 words (vqn_jpeg_plan hands them to the caller in this order).
-struct JpegGeom {
-  int64_t n, h, w, quality, sub, ri;
-  int64_t mcu, mcus_x, mcus_y, blocks_per_mcu;           // MCU side in pixels; MCUs per row and column; blocks of an MCU (6 or 3)
-  int64_t intervals;                                     // restart intervals of a frame
-  int64_t slot_bytes;                                    // bytes of an interval's slot (a multiple of 16)
-  int64_t by_y, bx_y, by_c, bx_c;                        // blocks of the Y plane and of a chroma plane
-  int64_t off_cb, off_cr, off_slots, off_lens, off_dst;  // byte offsets into the scratch: Y coefficients are at 0
-  int64_t scratch_bytes, out_bytes, header_bytes;
-};
+// The geometry of a batch is the public struct VqnJpegGeom (include/vqn_image_codec.h): vqn_jpeg_plan hands its words to the caller
+// as they lie.
+using JpegGeom = VqnJpegGeom;
 constexpr int kJpegGeomWords = sizeof(JpegGeom) / sizeof(int64_t);
 
 // IJG scaling of a base table: s = 5000 / q below 50, else 200 - 2 q; entry clamp((base s + 50) / 100, 1, 255).  Natural order.

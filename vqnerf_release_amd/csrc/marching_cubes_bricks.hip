@@ -1,7 +1,7 @@
 // Marching cubes over a sparse set of bricks: the same mesh as marching_cubes.hip gives on the dense field, byte for byte, from the
 // field on the bricks the surface passes through alone (geo/mesh.py: marching_cubes_bricks, extract_geometry_sparse).  A brick is
 // 8^3 cells = 9^3 stored points (faces shared with its neighbours are stored on both sides); the layout, the ownership rule and the
-// leak count are stated in include/vqn_neus_fold.h, the per-point statements in mc_bricks_core.h.  Same table and conventions as the
+// leak count are stated in include/vqn_mesh.h, the per-point statements in mc_bricks_core.h.  Same table and conventions as the
 // dense kernels: strict u > threshold, t from the _rn intrinsics, one fma per coordinate, vertex id = owner's offset + rank of the axis.
 //  * vqn_mc_brick_points: the stored points of a range of brick slots as [x y z] rows, for the SDF kernel;
 //  * vqn_mc_brick_classify: per slot of an active brick the owned crossing edges, the triangles of its cell and its dense linear
@@ -11,7 +11,7 @@
 // waves loop over the points, consecutive lanes along z.  Edges owned by a point of a neighbouring brick (local coordinate 8 on an
 // inner face) are resolved through `slot` from that brick's values in global memory: only the outermost layer of cells does that.
 #include "common.h"
-#include "vqn_neus_fold.h"
+#include "vqn_mesh.h"
 
 #define VQN_MC_TABLE_QUAL __constant__
 #include "mc_table.h"

@@ -7,7 +7,7 @@
 // that a lane's share of a plane of ch channels is ch whole 16-byte pieces (16-byte loads and stores when every pointer is 16-byte
 // aligned; the ragged last lane and unaligned tensors go row by row), passes blockIdx.x, blockIdx.x + gridDim.x, ...; the grid is
 // min(kGridCap, passes), kGridCap = 1024 = 4 workgroups per CU of the 256-CU chip.  Per pass:
-//   1. selection.  The program (include/vqn_neus_fold.h; packed by csrc/material_edit_plan.h, its terms sorted by plane) arrives in the
+//   1. selection.  The program (include/vqn_material_edit.h; packed by csrc/material_edit_plan.h, its terms sorted by plane) arrives in the
 //      kernel arguments and is copied into LDS once per workgroup: its terms are read at a runtime index, which LDS takes and
 //      registers do not.  The planes are walked one by one (spelled out, so that the plane is a constant); a plane with terms is
 //      loaded once into registers and its terms (a wave-uniform loop, each LDS word moved to a scalar register) set, per row, the bit
@@ -23,7 +23,7 @@
 //      The selection read the planes before this point, and outputs never alias inputs: it is the pre-edit selection.
 #include "common.h"
 #include "material_edit_plan.h"
-#include "vqn_neus_fold.h"
+#include "vqn_material_edit.h"
 
 // The only arithmetic is v / (d + eps) and x * scale.  __fadd_rn, __fdiv_rn and __fmul_rn are the plain IEEE operators here, which
 // hipcc rounds correctly by default (f32 denormals on, -fhip-fp32-correctly-rounded-divide-sqrt); the Makefile passes no flag that
@@ -36,10 +36,11 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kRows = 4;                     // consecutive rows per lane and pass
-constexpr int kPass = kThreads * kRows;      // 1024 rows per workgroup pass
-constexpr int kGridCap = 1024;               // workgroups at most: 4 per CU of a 256-CU MI355X
-constexpr int kHead = 3;                     // words of the output row ahead of the per-code counts: selected, rows, invalid
+constexpr int kPass = VQN_MATEDIT_ROWS_PER_PASS;   // 1024 rows per workgroup pass
+constexpr int kRows = kPass / kThreads;      // consecutive rows per lane and pass: 4
+constexpr int kGridCap = VQN_MATEDIT_GRID_CAP;     // workgroups at most: 4 per CU of a 256-CU MI355X
+static_assert(kRows * kThreads == kPass, "a pass is whole lanes");
+constexpr int kHead = VQN_MATEDIT_HEAD_WORDS;      // words of the output row ahead of the per-code counts: selected, rows, invalid
 constexpr int kWords = kHead + kMatCodes;
 constexpr int kMinMerge = 8;                 // keep merging across the wave while a round absorbed this many lanes
 

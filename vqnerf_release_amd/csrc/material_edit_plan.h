@@ -6,11 +6,13 @@
 #include <stdio.h>
 #include <string.h>
 
-constexpr int kMatPlanes = 8;        // property planes at most
-constexpr int kMatMaxCh = 3;         // channels of a plane at most
-constexpr int kMatTerms = 32;        // terms of a program at most
-constexpr int kMatConds = 8;         // conditions of a program at most
-constexpr int kMatCodes = 65;        // code labels 0 .. 64
+#include "../../include/vqn_material_edit.h"  // (by path: the stand-alone build of this header names no include directory)
+
+constexpr int kMatPlanes = VQN_MATEDIT_MAX_PLANES;   // property planes at most
+constexpr int kMatMaxCh = VQN_MATEDIT_MAX_CHANNELS;  // channels of a plane at most
+constexpr int kMatTerms = VQN_MATEDIT_MAX_TERMS;     // terms of a program at most
+constexpr int kMatConds = VQN_MATEDIT_MAX_CONDS;     // conditions of a program at most
+constexpr int kMatCodes = VQN_MATEDIT_CODES;         // code labels 0 .. 64
 constexpr int kMatNoDen = 255;       // MatEditProgram::den of a term without a denominator
 
 // A term is one channel test lo < v < hi (both strict) of v = plane[ch], or v = plane[ch] / (plane[den] + eps); a condition holds when

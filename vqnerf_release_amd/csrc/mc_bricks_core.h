@@ -1,9 +1,11 @@
 // Per-point statements of the brick marching cubes (marching_cubes_bricks.hip): which points a brick stores and owns, what one owned
 // point counts and what it writes.  Kept apart from the kernels so that the same text also compiles as plain C++ (no __HIPCC__): the
 // kernels only stage a brick's 9^3 values in LDS and loop these functions over its points.  Conventions: mc_table.h, which the
-// includer brings in first (with VQN_MC_TABLE_QUAL set for its side); layout and ownership: include/vqn_neus_fold.h.  Not public.
+// includer brings in first (with VQN_MC_TABLE_QUAL set for its side); layout and ownership: include/vqn_mesh.h.  Not public.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/vqn_mesh.h"  // (by path: the stand-alone build of this header names no include directory)
 
 #ifdef __HIPCC__
 #define VQN_BRK_FN __device__ __forceinline__
@@ -16,8 +18,8 @@ static inline float __fdiv_rn(float a, float b) { return a / b; }
 static inline float __fmaf_rn(float a, float b, float c) { return fmaf(a, b, c); }
 #endif
 
-#define VQN_BRK 8                              // cells per brick and axis
-#define VQN_BRK_N 729                          // stored points per brick: 9^3, local index l = (li * 9 + lj) * 9 + lk
+#define VQN_BRK VQN_MC_BRICK_CELLS             // cells per brick and axis
+#define VQN_BRK_N VQN_MC_BRICK_POINTS          // stored points per brick: 9^3, local index l = (li * 9 + lj) * 9 + lk
 #define VQN_BRK_NOKEY INT64_MAX                // sort key of a slot that is not an owned point
 
 struct BrickGrid {

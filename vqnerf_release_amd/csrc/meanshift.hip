@@ -25,22 +25,23 @@
 //  * meanshift_assign_kernel<D>: one point per lane against the centres held in LDS (chunks of kAssignCentres = 512), nearest by
 //    d2 with ties to the lowest index (strict <); optionally the distance sqrt(d2) and, for b > 0, label -1 where it is > b.
 #include "common.h"
-#include "vqn_neus_fold.h"
+#include "vqn_eval.h"
 
 // every product, sum and quotient below is rounded on its own, as the statement's are
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kMaxD = 8;
+constexpr int kMaxD = VQN_MEANSHIFT_MAX_DIM;
 constexpr int kSeekWaves = 8;
-constexpr int kSeekSeeds = 64;                               // seeds per workgroup: one per lane
+constexpr int kSeekSeeds = VQN_MEANSHIFT_SEEDS_PER_GROUP;    // seeds per workgroup: one per lane
 constexpr int kSeekThreads = kSeekWaves * 64;
-constexpr int kSeekSlice = 32;                               // points of a tile per wave
-constexpr int kSeekTile = kSeekWaves * kSeekSlice;           // 256 points staged per pass
+constexpr int kSeekTile = VQN_MEANSHIFT_POINTS_PER_TILE;     // 256 points staged per pass
+constexpr int kSeekSlice = kSeekTile / kSeekWaves;           // points of a tile per wave: 32
 constexpr int kMergeThreads = 1024;
-constexpr int kAssignThreads = 256;                          // points per workgroup and pass
-constexpr int kAssignCentres = 512;                          // centres staged in LDS at a time
+constexpr int kAssignThreads = VQN_MEANSHIFT_ASSIGN_SPAN;    // points per workgroup and pass
+constexpr int kAssignCentres = VQN_MEANSHIFT_ASSIGN_CENTRES; // centres staged in LDS at a time
+static_assert(kSeekSlice * kSeekWaves == kSeekTile, "a tile is whole slices");
 constexpr int kAssignGridCap = 4096;
 constexpr int kUndecided = 0, kKept = 1, kSuppressed = 2;
 

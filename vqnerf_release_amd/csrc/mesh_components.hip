@@ -24,7 +24,7 @@
 // A vertex index outside [0, n_verts) is a caller error; the kernels skip such an edge (remap: write -1) instead of touching
 // memory outside the arrays.
 #include "common.h"
-#include "vqn_neus_fold.h"
+#include "vqn_mesh.h"
 
 namespace {
 

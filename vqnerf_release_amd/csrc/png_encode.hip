@@ -23,7 +23,7 @@
 // Integer work throughout: equal images give equal bytes.
 #include "common.h"
 #include "png_plan.h"
-#include "vqn_neus_fold.h"
+#include "vqn_image_codec.h"
 
 namespace {
 
@@ -479,7 +479,7 @@ int plan_or_refuse(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, i
 
 }  // namespace
 
-static_assert(kPngGeomWords == 17, "include/vqn_neus_fold.h and _C.PNG_GEOM state 17 words");
+static_assert(kPngGeomWords == 17, "include/vqn_image_codec.h documents VqnPngGeom as 17 words");
 
 extern "C" int vqn_png_plan(int64_t n, int64_t h, int64_t w, int64_t c, int filter_mode, int64_t rows_per_segment, int64_t* geom,
                             uint8_t* head, int head_cap) {

@@ -39,7 +39,7 @@
 //   9..41  int32    label_map[65] (entries >= C are -1) and one zero word of padding
 //   42..   int64    coo[R][C]
 #include "common.h"
-#include "vqn_neus_fold.h"
+#include "vqn_eval.h"
 
 // every quotient and sum below is rounded on its own, as the statement's are
 #pragma clang fp contract(off)
@@ -47,13 +47,14 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPix = 16;                     // consecutive pixels per lane and pass
-constexpr int kPass = kThreads * kPix;       // 4096 pixels per workgroup pass
-constexpr int kGridCap = 512;                // workgroups at most: 2 per CU of a 256-CU MI355X
-constexpr int kMaxSide = 65;                 // R, C <= 65: the K = 64 codebook plus class 0
+constexpr int kPass = VQN_SEG_PIXELS_PER_PASS;   // 4096 pixels per workgroup pass
+constexpr int kPix = kPass / kThreads;       // consecutive pixels per lane and pass: 16
+constexpr int kGridCap = VQN_SEG_GRID_CAP;   // workgroups at most: 2 per CU of a 256-CU MI355X
+constexpr int kMaxSide = VQN_SEG_MAX_SIDE;   // R, C <= 65: the K = 64 codebook plus class 0
+static_assert(kPix * kThreads == kPass, "a pass is whole lanes");
 constexpr int kMinMerge = 8;                 // keep merging across the wave while a round absorbed this many lanes
 constexpr int kFinThreads = 1024;
-constexpr int kHeadWords = 42;               // 8-byte words of `out` ahead of the table
+constexpr int kHeadWords = VQN_SEG_HEAD_WORDS;   // 8-byte words of `out` ahead of the table
 constexpr int kSkip = -1;                    // key of a pixel that is not counted
 
 struct SegArgs {

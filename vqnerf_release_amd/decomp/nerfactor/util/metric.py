@@ -20,7 +20,7 @@ import torch
 
 from vqnerf_release_amd import _C
 
-WINDOW_SIZE, WINDOW_SIGMA = 11, 1.5
+WINDOW_SIZE, WINDOW_SIGMA = _C.IMAGE_METRICS_WINDOW, 1.5
 KEYS = ('psnr', 'mse', 'psnr_luma', 'ssim', 'ssim_luma')         # words 0..4 of the library's output row
 
 
@@ -48,7 +48,7 @@ def _device_batch(im, device):
 
 
 def image_metrics_raw(a, b, alpha=None, alpha_thres=None):
-    """-> the library's output rows, int64 [B, 16] (include/vqn_neus_fold.h: scores, sums, integer sums and counts)"""
+    """-> the library's output rows, int64 [B, 16] (include/vqn_eval.h: scores, sums, integer sums and counts)"""
     dev = next((t.device for t in (a, b) if torch.is_tensor(t) and t.is_cuda), torch.device('cuda'))
     a, b = _device_batch(a, dev), _device_batch(b, dev)
     if (alpha is None) != (alpha_thres is None):

@@ -48,7 +48,7 @@ def _labels(t, dev):
 
 
 def contingency_raw(gt, pd, alpha=None, alpha_thres=0.8, mask=None, gt_palette=GT_PALETTE, pd_palette=PD_PALETTE, n_gt=None, n_pd=None):
-    """-> (the library's output row, int64 [42 + R * C] (include/vqn_neus_fold.h), R, C)"""
+    """-> (the library's output row, int64 [42 + R * C] (include/vqn_eval.h), R, C)"""
     dev = _device_of(gt, pd, alpha, mask)
     gt, pd = torch.as_tensor(gt), torch.as_tensor(pd)
     colour = gt.dtype == torch.uint8 and pd.dtype == torch.uint8 and gt.dim() >= 1 and gt.shape[-1] == 3 and pd.shape[-1] == 3

@@ -74,7 +74,7 @@ def extract_geometry_device(bound_min, bound_max, resolution, threshold, sdf_net
 
 
 # ---- the sparse route: only the bricks the surface can pass through (csrc/marching_cubes_bricks.hip) --------
-BRICK = 8                     # cells per brick and axis; a brick stores (BRICK + 1)^3 points, its faces on both sides
+BRICK = _C.BRICK_CELLS        # 8 cells per brick and axis; a brick stores (BRICK + 1)^3 points, its faces on both sides
 
 
 def plan_bricks(resolution, brick=BRICK, axes=None):
