@@ -50,3 +50,22 @@ def make_batch(pts, device, bg_every=0):
     if 'lvis' in pts:
         batch = batch + (T(pts['lvis']),)
     return batch
+
+
+def shipped_chain_programs(model):
+    """The layer programs vq_nfr.Model runs through the Dense-stack kernels, from the model's own builders:
+    [(engine, name, (wbuf, desc), output widths)] -- encoder and the two head families per engine, encoder + heads (f32)."""
+    out, was = [], model.matrix_mode
+    families = {suf: [h + '_' + suf for h in model.HEADS] for suf in ('main', 'vq')}
+    widths = lambda names: [model.net[n].widths[-1] for n in names]
+    for mode in ('f32', 'f16s'):
+        model.matrix_mode = mode
+        out.append((mode, 'enc', model._program_pack('enc:' + mode, model._enc_program(), ['fine_enc', 'bottleneck']), [model.z_dim]))
+        for suf, names in families.items():
+            out.append((mode, 'heads_' + suf, model._program_pack(f'heads:{mode}:{suf}', model._head_program(names), names), widths(names)))
+    model.matrix_mode = 'f32'
+    for suf, names in families.items():
+        pack = model._program_pack('enc+heads:' + suf, model._enc_heads_program(names), ['fine_enc', 'bottleneck'] + names)
+        out.append(('f32', 'enc_heads_' + suf, pack, [model.z_dim] + widths(names)))
+    model.matrix_mode = was
+    return out

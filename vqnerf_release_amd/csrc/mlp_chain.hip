@@ -7,8 +7,8 @@
 //   decomp/nerfvq_nfr3/nerfactor/models/shape.py:169-179    (chunk_apply: disappears)
 // The layer program (which LDS rows feed a layer, where its output goes, which outputs leave for HBM) is built
 // on the host (vqnerf_release_amd/decomp/packing.py) -- the kernel is a small interpreter over it.
-#include "mlp_prims.h"
-#include "vqn_chain_desc.h"
+#include "chain_phases.h"
+#include "vq_step.h"
 #include "vqnerf_hip.h"
 #include <math.h>
 
@@ -17,19 +17,6 @@ using namespace eng;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
-
-struct ChainSmalls {
-  float part[8 * 32 * 4];
-};
-
-__device__ __forceinline__ float act_rt(int act, float x) {
-  switch (act) {
-    case ACT_RELU: return fmaxf(x, 0.f);
-    case ACT_SIGMOID: return fast_rcp(1.f + fast_exp(-x));
-    case ACT_SOFTPLUS100: return act_fwd<ACT_SOFTPLUS100>(x);
-    default: return x;
-  }
-}
 
 // One output tile through its activation into the LDS image.  The activation is a run-time field of the layer record, but it is
 // resolved ONCE per tile here: with the switch inside the element loops every accumulator element went through its own chain of
@@ -51,23 +38,6 @@ __device__ __forceinline__ void store_tile(int act, f32x4* lds, int row0, int la
     case ACT_SOFTPLUS100: store_tile_act<ACT_SOFTPLUS100>(lds, row0, lane, acc); break;
     default: store_tile_act<ACT_NONE>(lds, row0, lane, acc); break;
   }
-}
-
-struct OutPtrs {
-  float* p[VQN_CHAIN_MAX_OUTS];
-  int ld[VQN_CHAIN_MAX_OUTS];
-};
-
-// the <= 4-output layers' weight images are tiny and the same for every point tile: one LDS copy per workgroup (their
-// VALU dots would otherwise wait on an L2 round trip per row)
-template <int NW>
-__device__ __forceinline__ void chain_stage_smalls(const ChainDesc& d, const f32x4* __restrict__ wbuf, f32x4* smallw) {
-  const int tid = threadIdx.x;
-  for (int l = 0; l < d.n_layers; ++l)
-    if (d.layers[l].kind == 1) {
-      const int n4 = d.layers[l].n_out_tiles * (d.layers[l].kA_rows + d.layers[l].kB_rows) * 2;
-      for (int i = tid; i < n4; i += NW * 64) smallw[d.layers[l].dst_row0 + i] = wbuf[d.layers[l].w_off + i];
-    }
 }
 
 // One point tile through one layer program.  `resident`: the input image already stands in rows [in_row0, +in_rows) (written by the
@@ -199,12 +169,7 @@ __device__ __forceinline__ void chain_tile(const ChainDesc& d, const f32x4* __re
               s[o] = fmaf(b[2], wv[2], s[o]); s[o] = fmaf(b[3], wv[3], s[o]);
             }
         }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-          s[o] += __shfl_xor(s[o], 32);
-          if (h == 0) sm->part[(wave * 32 + p) * 4 + o] = s[o];
-        }
-        __syncthreads();
+        chain_small_join(s, sm, h, p, wave);
         if (tid < 128) {
           const int pp = tid & 31, o = tid >> 5;
           if (o < nout && p0 + pp < N) {
@@ -243,7 +208,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void mlp_chain_kernel(con
 
 // ---- encoder + continuous heads -> VQ step -> VQ heads in ONE launch (vq_nfr.py:534-692, inference, K <= 16, z_dim = 256) --------
 // Program A leaves z in LDS rows [z_row0, +32); waves 0 / 1 each take 16 of the tile's 32 points through EXACTLY the arithmetic of
-// vq_assign_kernel<1, false, FUSE> (csrc/vq.hip; oracle/vq_strict.c): the A operand of the 16x16x4 MFMA chain is gathered from the
+// vq_assign_kernel<KT, false, FUSE> (csrc/vq.hip; oracle/vq_strict.c; csrc/vq_step.h says why most of it stands twice): the A
+// operand of the 16x16x4 MFMA chain is gathered from the
 // image (feature f of point p: row f >> 3, lane p + 32 (f & 1), component (f & 7) >> 1), rows are l2-normalised in registers, the
 // codebook comes as B fragments + |c|^2 from vqn_vq_codebook_frags (global, L2-resident: 16 KB), and the straight-through rows
 // x^ + (q - x^) go back into the image where program B expects its input.  z and the quantised rows never leave the chip; indices,
@@ -289,8 +255,7 @@ __device__ __noinline__ float vq_tail(f32x4* lds, const int z_row0, const int ds
       if (!rvalid) av[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       pr = fmaf(av[i][0], av[i][0], pr); pr = fmaf(av[i][1], av[i][1], pr); pr = fmaf(av[i][2], av[i][2], pr); pr = fmaf(av[i][3], av[i][3], pr);
     }
-    pr = pr + __shfl_xor(pr, 16);
-    pr = pr + __shfl_xor(pr, 32);
+    pr = vq_sum_quarters(pr);
     const float sc = 1.0f / sqrtf(fmaxf(pr, vq.eps));
 #pragma unroll
     for (int i = 0; i < 16; ++i) av[i] = av[i] * sc;
@@ -311,8 +276,7 @@ __device__ __noinline__ float vq_tail(f32x4* lds, const int z_row0, const int ds
       // (this step is 1 % of a tile's time: keep the compiler from hoisting all 16 KT fragment loads -- 64 KT registers, spilled)
       if (KT > 1 || (t & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
-    p = p + __shfl_xor(p, 16);
-    p = p + __shfl_xor(p, 32);
+    p = vq_sum_quarters(p);
     float c2c[KT];
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) c2c[kt] = vq.c2[16 * kt + col];
@@ -326,8 +290,7 @@ __device__ __noinline__ float vq_tail(f32x4* lds, const int z_row0, const int ds
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
         const int code = 16 * kt + col;
-        const float t1 = x2 - 2.0f * acc[kt][j];
-        const float dv = t1 + c2c[kt];
+        const float dv = vq_dist(x2, acc[kt][j], c2c[kt]);
         if (code < vq.K) {
           if (dv < best_v[j] || best_i[j] == 0x7fffffff) { best_v[j] = dv; best_i[j] = code; }
         }
@@ -359,8 +322,7 @@ __device__ __noinline__ float vq_tail(f32x4* lds, const int z_row0, const int ds
       if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
     if (!rvalid) lr = 0.f;
-    lr = lr + __shfl_xor(lr, 16);
-    lr = lr + __shfl_xor(lr, 32);
+    lr = vq_sum_quarters(lr);
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1) lr += __shfl_xor(lr, m);
     wave_loss += lr;
@@ -420,42 +382,6 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_vq_kernel(const ChainDesc da
   if ((int)threadIdx.x < vq.K && hist[threadIdx.x]) atomicAdd(&vq.counts[threadIdx.x], (float)hist[threadIdx.x]);
 }
 
-int check_desc(const ChainDesc& d) {
-  if (d.n_layers < 1 || d.n_layers > VQN_CHAIN_MAX_LAYERS) return 1;
-  if (d.n_waves != 4 && d.n_waves != 8) return 2;
-  if (d.total_rows < 1 || d.small_w4 < 0 || (size_t)d.total_rows * 1024 + sizeof(ChainSmalls) + (size_t)d.small_w4 * 16 > 160 * 1024) return 3;
-  if (d.in_rows < 1 || d.in_row0 < 0 || d.in_row0 + d.in_rows > d.total_rows) return 4;
-  if (d.in_mode == 1 && (d.in_feats != 3 + 6 * d.n_freqs || d.n_freqs > 16)) return 5;
-  if (d.in_feats < 1 || d.in_feats > 8 * d.in_rows || d.in_stride < 1) return 6;
-  for (int l = 0; l < d.n_layers; ++l) {
-    const ChainLayer& L = d.layers[l];
-    if (L.kind == 2) {
-      if (L.dst_row0 < 0 || L.dst_row0 + d.in_rows > d.total_rows) return 20;
-      continue;
-    }
-    if (L.kA_rows < 0 || L.kB_rows < 0 || L.kA_rows + L.kB_rows < 1) return 10;
-    if (L.kA_row0 < 0 || L.kA_row0 + L.kA_rows > d.total_rows) return 11;
-    if (L.kB_rows > 0 && (L.kB_row0 < 0 || L.kB_row0 + L.kB_rows > d.total_rows)) return 12;
-    if (L.out_slot >= VQN_CHAIN_MAX_OUTS) return 13;
-    if (L.kind == 0) {
-      if (L.n_out_tiles < 1 || L.dst_row0 < 0 || L.dst_row0 + 4 * L.n_out_tiles > d.total_rows) return 14;
-      if (L.out_slot >= 0 && (L.out_feats < 1 || L.out_feats > 32 * L.n_out_tiles)) return 15;
-      // a layer must not overwrite its own K rows -- unless it writes after a barrier (bit 8 of act), one tile per wave
-      const int d0 = L.dst_row0, d1 = L.dst_row0 + 4 * L.n_out_tiles;
-      if (L.act & 0x100) {
-        if (L.n_out_tiles > d.n_waves) return 22;
-      } else {
-        if (d0 < L.kA_row0 + L.kA_rows && L.kA_row0 < d1) return 16;
-        if (L.kB_rows > 0 && d0 < L.kB_row0 + L.kB_rows && L.kB_row0 < d1) return 17;
-      }
-    } else if (L.kind == 1) {
-      if (L.n_out_tiles < 1 || L.n_out_tiles > 4 || L.out_slot < 0) return 18;
-      if (L.dst_row0 < 0 || L.dst_row0 + L.n_out_tiles * (L.kA_rows + L.kB_rows) * 2 > d.small_w4) return 21;
-    } else return 19;
-  }
-  return 0;
-}
-
 }  // namespace
 
 int vqn_internal_finish_loss(const float* part, int n, float scale, float* loss, hipStream_t s);      // csrc/vq.hip
@@ -480,8 +406,8 @@ extern "C" int vqn_mlp_chain_vq_fwd(const int32_t* desc_a, const float* wbuf_a, 
   ChainDesc da, db;
   memcpy(&da, desc_a, sizeof(ChainDesc));
   memcpy(&db, desc_b, sizeof(ChainDesc));
-  int bad = check_desc(da);
-  if (!bad) bad = check_desc(db) ? 100 + check_desc(db) : 0;
+  int bad = chain_check_desc(da, kChainRulesF32);
+  if (!bad && (bad = chain_check_desc(db, kChainRulesF32)) != 0) bad += 100;
   if (bad) {
     vqn_set_error("vqn_mlp_chain_vq_fwd: unsupported shape: invalid chain descriptor (check %d)", bad);
     return VQN_ESHAPE;
@@ -509,29 +435,15 @@ extern "C" int vqn_mlp_chain_vq_fwd(const int32_t* desc_a, const float* wbuf_a, 
   }
   OutPtrs oa, ob;
   for (int i = 0; i < VQN_CHAIN_MAX_OUTS; ++i) { oa.p[i] = outs_a[i]; oa.ld[i] = ld_a[i]; ob.p[i] = outs_b[i]; ob.ld[i] = ld_b[i]; }
-  for (int which = 0; which < 2; ++which) {
-    const ChainDesc& d = which ? db : da;
-    const OutPtrs& o = which ? ob : oa;
-    for (int l = 0; l < d.n_layers; ++l) {
-      const int sl = d.layers[l].out_slot;
-      if (sl < 0) continue;
-      if (which == 0 && sl == 0 && o.p[0] == nullptr) continue;                 // z stays on the chip
-      VQN_CHECK_ARG(o.p[sl] != nullptr, "an output a descriptor writes is null");
-      VQN_CHECK_ARG(o.ld[sl] >= (d.layers[l].kind == 0 ? d.layers[l].out_feats : d.layers[l].n_out_tiles),
-                    "output leading dimension smaller than the layer's width");
-      if (d.layers[l].kind == 0 && (o.ld[sl] & 3) == 0)
-        VQN_CHECK_ARG(((uintptr_t)o.p[sl] & 15) == 0, "outputs with ld % 4 == 0 must be 16-byte aligned");
-    }
-  }
+  const char* null_msg = "an output a descriptor writes is null";
+  if (int rc = chain_check_outs(__func__, da, oa, true, null_msg)) return rc;       // (a null slot 0: z stays on the chip)
+  if (int rc = chain_check_outs(__func__, db, ob, false, null_msg)) return rc;
   const int rows = da.total_rows > db.total_rows ? da.total_rows : db.total_rows;
   const size_t lds = (size_t)rows * 1024 + sizeof(ChainSmalls) + (size_t)(da.small_w4 > db.small_w4 ? da.small_w4 : db.small_w4) * 16 + (size_t)KT * 16 * 4 + 4 * 4;
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "the two programs do not fit in 160 KB of LDS");
-  const long n_tiles = (N + 31) / 32;
   const void* kern = KT == 1 ? (const void*)mlp_chain_vq_kernel<1> : (KT == 2 ? (const void*)mlp_chain_vq_kernel<2> : (const void*)mlp_chain_vq_kernel<4>);
   if (lds > 64 * 1024) VQN_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int per_cu = (2 * lds <= 160 * 1024) ? 2 : 1;
-  long grid = (long)vqn_num_cus() * per_cu;
-  if (grid > n_tiles) grid = n_tiles;
+  const long grid = chain_grid(4, lds, (N + 31) / 32);
   VQN_CHECK_SHAPE(grid + 1 <= VQN_QUANT_WS_FLOATS, "workspace too small for this device");
   VqTail vq;
   vq.frags = reinterpret_cast<const f32x4*>(cb_frags);
@@ -555,50 +467,12 @@ extern "C" int vqn_mlp_chain_vq_fwd(const int32_t* desc_a, const float* wbuf_a, 
 extern "C" int vqn_mlp_chain_fwd(const int32_t* desc, const float* wbuf, const float* in, int64_t N, float* out0,
                                  int ld0, float* out1, int ld1, float* out2, int ld2, float* out3, int ld3,
                                  void* stream) {
-  VQN_CHECK_ARG(desc && wbuf, "desc and wbuf must be non-null");
-  VQN_CHECK_ARG(N >= 0, "N >= 0");
-  if (N == 0) return VQN_OK;
-  VQN_CHECK_ARG(in != nullptr, "in must be non-null");
+  const OutPtrs o = {{out0, out1, out2, out3}, {ld0, ld1, ld2, ld3}};
   ChainDesc d;
-  memcpy(&d, desc, sizeof(ChainDesc));
-  const int bad = check_desc(d);
-  if (bad) {
-    vqn_set_error("vqn_mlp_chain_fwd: unsupported shape: invalid chain descriptor (check %d)", bad);
-    return VQN_ESHAPE;
-  }
-  OutPtrs o;
-  o.p[0] = out0; o.p[1] = out1; o.p[2] = out2; o.p[3] = out3;
-  o.ld[0] = ld0; o.ld[1] = ld1; o.ld[2] = ld2; o.ld[3] = ld3;
-  for (int l = 0; l < d.n_layers; ++l) {
-    const int s = d.layers[l].out_slot;
-    if (s >= 0) {
-      VQN_CHECK_ARG(o.p[s] != nullptr, "an output the descriptor writes is null");
-      VQN_CHECK_ARG(o.ld[s] >= (d.layers[l].kind == 0 ? d.layers[l].out_feats : d.layers[l].n_out_tiles),
-                    "output leading dimension smaller than the layer's width");
-      if (d.layers[l].kind == 0 && (o.ld[s] & 3) == 0)
-        VQN_CHECK_ARG(((uintptr_t)o.p[s] & 15) == 0, "outputs with ld % 4 == 0 must be 16-byte aligned");
-    }
-  }
-  if (d.in_mode == 0 && (d.in_stride & 3) == 0) VQN_CHECK_ARG(((uintptr_t)in & 15) == 0, "in must be 16-byte aligned");
-  const size_t lds = (size_t)d.total_rows * 1024 + sizeof(ChainSmalls) + (size_t)d.small_w4 * 16;
-  const long n_tiles = (N + 31) / 32;
-  hipStream_t s = (hipStream_t)stream;
-  if (d.n_waves == 4) {
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)mlp_chain_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per_cu = (2 * lds <= 160 * 1024) ? 2 : 1;
-    long grid = (long)vqn_num_cus() * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(mlp_chain_kernel<4>, dim3((unsigned)grid), dim3(256), lds, s, d,
-                       reinterpret_cast<const f32x4*>(wbuf), in, (long)N, o);
-  } else {
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)mlp_chain_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    long grid = (long)vqn_num_cus();
-    if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(mlp_chain_kernel<8>, dim3((unsigned)grid), dim3(512), lds, s, d,
-                       reinterpret_cast<const f32x4*>(wbuf), in, (long)N, o);
-  }
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  const int rc = chain_fwd_args(__func__, kChainRulesF32, desc, wbuf, in, N, o, &d);
+  if (rc != VQN_OK || N == 0) return rc;
+  const f32x4* w = reinterpret_cast<const f32x4*>(wbuf);
+  const size_t lds = chain_lds_bytes(d);
+  if (d.n_waves == 4) return chain_launch<4>(__func__, mlp_chain_kernel<4>, lds, N, stream, d, w, in, (long)N, o);
+  return chain_launch<8>(__func__, mlp_chain_kernel<8>, lds, N, stream, d, w, in, (long)N, o);
 }

@@ -5,29 +5,11 @@
 // the host builds programs and packs for it with ChainBuilder(mode='f16s').
 #include "mlp_prims_f16s.h"
 #include <type_traits>
-#include "vqn_chain_desc.h"
+#include "chain_phases.h"
 
 using namespace eng;
 
 namespace {
-
-struct ChainSmalls {
-  float part[8 * 32 * 4];
-};
-
-__device__ __forceinline__ float act_rt(int act, float x) {
-  switch (act) {
-    case ACT_RELU: return fmaxf(x, 0.f);
-    case ACT_SIGMOID: return fast_rcp(1.f + fast_exp(-x));
-    case ACT_SOFTPLUS100: return act_fwd<ACT_SOFTPLUS100>(x);
-    default: return x;
-  }
-}
-
-struct OutPtrs {
-  float* p[VQN_CHAIN_MAX_OUTS];
-  int ld[VQN_CHAIN_MAX_OUTS];
-};
 
 template <int NW>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void mlp_chain_f16s_kernel(const ChainDesc d,
@@ -40,13 +22,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void mlp_chain_f16s_kerne
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform by construction: let the compiler know
   const long n_tiles = (N + 31) >> 5;
-  // the <= 4-output layers' weight images are tiny and the same for every point tile: one LDS copy per workgroup (their
-  // VALU dots would otherwise wait on an L2 round trip per row)
-  for (int l = 0; l < d.n_layers; ++l)
-    if (d.layers[l].kind == 1) {
-      const int n4 = d.layers[l].n_out_tiles * (d.layers[l].kA_rows + d.layers[l].kB_rows) * 2;
-      for (int i = tid; i < n4; i += NW * 64) smallw[d.layers[l].dst_row0 + i] = wbuf[d.layers[l].w_off + i];
-    }
+  chain_stage_smalls<NW>(d, wbuf, smallw);
   __syncthreads();
 
   // this wave's weight stream: the next GEMM layer (program order, wrapping to the next point tile) in which it owns a tile
@@ -190,12 +166,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void mlp_chain_f16s_kerne
               s[o] = fmaf(x[6], w1[2], s[o]); s[o] = fmaf(x[7], w1[3], s[o]);
             }
         }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-          s[o] += __shfl_xor(s[o], 32);
-          if (h == 0) sm->part[(wave * 32 + p) * 4 + o] = s[o];
-        }
-        __syncthreads();
+        chain_small_join(s, sm, h, p, wave);
         if (tid < 128) {
           const int pp = tid & 31, o = tid >> 5;
           if (o < nout && p0 + pp < N) {
@@ -215,86 +186,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void mlp_chain_f16s_kerne
   }
 }
 
-int check_desc(const ChainDesc& d) {
-  if (d.n_layers < 1 || d.n_layers > VQN_CHAIN_MAX_LAYERS) return 1;
-  if (d.n_waves != 4 && d.n_waves != 8) return 2;
-  if (d.total_rows < 1 || d.small_w4 < 0 || (size_t)d.total_rows * 1024 + sizeof(ChainSmalls) + (size_t)d.small_w4 * 16 > 160 * 1024) return 3;
-  if (d.in_rows < 2 || (d.in_rows & 1) || d.in_row0 < 0 || d.in_row0 + d.in_rows > d.total_rows) return 4;
-  if (d.in_mode == 1 && (d.in_feats != 3 + 6 * d.n_freqs || d.n_freqs > 16)) return 5;
-  if (d.in_feats < 1 || d.in_feats > 8 * d.in_rows || d.in_stride < 1) return 6;
-  for (int l = 0; l < d.n_layers; ++l) {
-    const ChainLayer& L = d.layers[l];
-    if (L.kind == 2) {
-      if (L.dst_row0 < 0 || L.dst_row0 + d.in_rows > d.total_rows) return 20;
-      continue;
-    }
-    if (L.kA_rows < 0 || L.kB_rows < 0 || L.kA_rows + L.kB_rows < 2 || (L.kA_rows & 1) || (L.kB_rows & 1)) return 10;
-    if (L.kA_row0 < 0 || L.kA_row0 + L.kA_rows > d.total_rows) return 11;
-    if (L.kB_rows > 0 && (L.kB_row0 < 0 || L.kB_row0 + L.kB_rows > d.total_rows)) return 12;
-    if (L.out_slot >= VQN_CHAIN_MAX_OUTS) return 13;
-    if (L.kind == 0) {
-      if (L.n_out_tiles < 1 || L.dst_row0 < 0 || L.dst_row0 + 4 * L.n_out_tiles > d.total_rows) return 14;
-      if (L.out_slot >= 0 && (L.out_feats < 1 || L.out_feats > 32 * L.n_out_tiles)) return 15;
-      const int d0 = L.dst_row0, d1 = L.dst_row0 + 4 * L.n_out_tiles;
-      if (d0 < L.kA_row0 + L.kA_rows && L.kA_row0 < d1) return 16;
-      if (L.kB_rows > 0 && d0 < L.kB_row0 + L.kB_rows && L.kB_row0 < d1) return 17;
-    } else if (L.kind == 1) {
-      if (L.n_out_tiles < 1 || L.n_out_tiles > 4 || L.out_slot < 0) return 18;
-      if (L.dst_row0 < 0 || L.dst_row0 + L.n_out_tiles * (L.kA_rows + L.kB_rows) * 2 > d.small_w4) return 21;
-    } else return 19;
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int vqn_mlp_chain_fwd_f16s(const int32_t* desc, const float* wbuf, const float* in, int64_t N, float* out0,
                                       int ld0, float* out1, int ld1, float* out2, int ld2, float* out3, int ld3,
                                       void* stream) {
-  VQN_CHECK_ARG(desc && wbuf, "desc and wbuf must be non-null");
-  VQN_CHECK_ARG(N >= 0, "N >= 0");
-  if (N == 0) return VQN_OK;
-  VQN_CHECK_ARG(in != nullptr, "in must be non-null");
+  const OutPtrs o = {{out0, out1, out2, out3}, {ld0, ld1, ld2, ld3}};
   ChainDesc d;
-  memcpy(&d, desc, sizeof(ChainDesc));
-  const int bad = check_desc(d);
-  if (bad) {
-    vqn_set_error("vqn_mlp_chain_fwd_f16s: unsupported shape: invalid chain descriptor (check %d)", bad);
-    return VQN_ESHAPE;
-  }
-  OutPtrs o;
-  o.p[0] = out0; o.p[1] = out1; o.p[2] = out2; o.p[3] = out3;
-  o.ld[0] = ld0; o.ld[1] = ld1; o.ld[2] = ld2; o.ld[3] = ld3;
-  for (int l = 0; l < d.n_layers; ++l) {
-    const int s = d.layers[l].out_slot;
-    if (s >= 0) {
-      VQN_CHECK_ARG(o.p[s] != nullptr, "an output the descriptor writes is null");
-      VQN_CHECK_ARG(o.ld[s] >= (d.layers[l].kind == 0 ? d.layers[l].out_feats : d.layers[l].n_out_tiles),
-                    "output leading dimension smaller than the layer's width");
-      if (d.layers[l].kind == 0 && (o.ld[s] & 3) == 0)
-        VQN_CHECK_ARG(((uintptr_t)o.p[s] & 15) == 0, "outputs with ld % 4 == 0 must be 16-byte aligned");
-    }
-  }
-  if (d.in_mode == 0 && (d.in_stride & 3) == 0) VQN_CHECK_ARG(((uintptr_t)in & 15) == 0, "in must be 16-byte aligned");
-  const size_t lds = (size_t)d.total_rows * 1024 + sizeof(ChainSmalls) + (size_t)d.small_w4 * 16;
-  const long n_tiles = (N + 31) / 32;
-  hipStream_t s = (hipStream_t)stream;
-  if (d.n_waves == 4) {
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)mlp_chain_f16s_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per_cu = (2 * lds <= 160 * 1024) ? 2 : 1;
-    long grid = (long)vqn_num_cus() * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(mlp_chain_f16s_kernel<4>, dim3((unsigned)grid), dim3(256), lds, s, d,
-                       reinterpret_cast<const f32x4*>(wbuf), in, (long)N, o);
-  } else {
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)mlp_chain_f16s_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    long grid = (long)vqn_num_cus();
-    if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(mlp_chain_f16s_kernel<8>, dim3((unsigned)grid), dim3(512), lds, s, d,
-                       reinterpret_cast<const f32x4*>(wbuf), in, (long)N, o);
-  }
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  const int rc = chain_fwd_args(__func__, kChainRulesF16s, desc, wbuf, in, N, o, &d);
+  if (rc != VQN_OK || N == 0) return rc;
+  const f32x4* w = reinterpret_cast<const f32x4*>(wbuf);
+  const size_t lds = chain_lds_bytes(d);
+  if (d.n_waves == 4) return chain_launch<4>(__func__, mlp_chain_f16s_kernel<4>, lds, N, stream, d, w, in, (long)N, o);
+  return chain_launch<8>(__func__, mlp_chain_f16s_kernel<8>, lds, N, stream, d, w, in, (long)N, o);
 }

@@ -12,7 +12,7 @@
 //     c2[k]     : fmaf chain over d = 0..D-1
 //     dist      : (x2 - 2 dot) + c2 ; argmin, lowest index wins ties.
 // The codebook lives in LDS already laid out as MFMA B-fragments (one ds_read_b128 per 4 MFMAs).
-#include "common.h"
+#include "vq_step.h"
 #include "vqnerf_hip.h"
 #include <math.h>
 
@@ -136,9 +136,7 @@ __global__ __launch_bounds__(256) void vq_assign_kernel(const float* __restrict_
         }
       }
     }
-    // x2 for row (lane&15): (p0+p1)+(p2+p3)
-    p = p + __shfl_xor(p, 16);
-    p = p + __shfl_xor(p, 32);
+    p = vq_sum_quarters(p);                             // x2 for row (lane & 15)
     float best_v[4];
     int best_i[4];
 #pragma unroll
@@ -150,8 +148,7 @@ __global__ __launch_bounds__(256) void vq_assign_kernel(const float* __restrict_
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
         const int code = 16 * kt + col;
-        float t1 = x2 - 2.0f * acc[kt][j];
-        float dv = t1 + c2[code];
+        float dv = vq_dist(x2, acc[kt][j], c2[code]);
         if (MAXONLY) {
           if (row_ok && code < K) wmax = fmaxf(wmax, dv);
         } else {
@@ -195,12 +192,13 @@ __global__ __launch_bounds__(256) void vq_assign_kernel(const float* __restrict_
             if (rvalid && fuse.xnorm != nullptr) *reinterpret_cast<f32x4*>(fuse.xnorm + (size_t)(row0 + col) * D + 16 * i + 4 * q) = av[i];
           }
         }
-        if (!rvalid) lr = 0.f;
-        lr = lr + __shfl_xor(lr, 16);                     // the row's four quarter sums: (l0 + l1) + (l2 + l3)
-        lr = lr + __shfl_xor(lr, 32);
+        float lg = lr;
+        if (!rvalid) lg = 0.f;
+        lg = lg + __shfl_xor(lg, 16);                     // the row's four quarter sums: (l0 + l1) + (l2 + l3)
+        lg = lg + __shfl_xor(lg, 32);
 #pragma unroll
-        for (int m = 1; m < 16; m <<= 1) lr += __shfl_xor(lr, m);      // the group's 16 rows, fixed xor tree
-        wave_loss += lr;
+        for (int m = 1; m < 16; m <<= 1) lg += __shfl_xor(lg, m);      // the group's 16 rows, fixed xor tree
+        wave_loss += lg;
         if (q == 0 && rvalid) atomicAdd(&hist[kr], 1);
       } else if (quant != nullptr) {
         const int nchunk = (D + 255) >> 8;
