@@ -64,6 +64,10 @@ i vqn_meanshift_assign(plpiidppp)""",
     'vqn_material_edit.h': 'i vqn_material_select_edit(pppiplppipipfppppppppppppp)',
     'vqn_image_codec.h': """
 i vqn_jpeg_plan(llliilppi)  i vqn_jpeg_encode(pllliilplplpip)  i vqn_png_plan(llllilppi)  i vqn_png_encode(pllllilplplpip)""",
+    'vqn_geometry_eval.h': """
+i vqn_geom_tri_areas(plplpp)  i vqn_geom_sample_surface(plplpplpppp)  i vqn_geom_grid_plan(pplfp)  i vqn_geom_cell_ids(plppp)
+i vqn_geom_pack_sorted(plppp)  i vqn_geom_nearest(plppplpfppp)  l vqn_geom_reduce_scratch_bytes(l)
+i vqn_geom_reduce(pplpplpiplpp)""",
 }
 ABI_BY_HEADER = {header: {name: (ret, args) for ret, name, args in re.findall(r'(\w) (\w+)\((\w*)\)', text)}
                  for header, text in _ABI_TEXT.items()}
@@ -1096,6 +1100,125 @@ def meanshift_assign(points, centres, bandwidth=0.0, want_dist=False):
     dist = torch.empty((n,), dtype=torch.float64, device=points.device) if want_dist else None
     _call('vqn_meanshift_assign', _ptr(points), n, _ptr(centres), int(centres.shape[0]), D, float(bandwidth), _ptr(labels), _ptr(dist))
     return labels, dist
+
+
+# --------------------------------------------------------------------------------------
+# geometry scores (csrc/geometry_eval.hip, include/vqn_geometry_eval.h; geo/geometry_eval.py)
+GEOM_MAX_CELLS = 1 << 24           # cells of a grid at most (VQN_GEOM_MAX_CELLS)
+GEOM_MAX_AXIS = 1024               # cells per axis at most (VQN_GEOM_MAX_AXIS)
+GEOM_MAX_THRESHOLDS = 8            # distance thresholds of one reduction at most (VQN_GEOM_MAX_THRESHOLDS)
+GEOM_OUT_WORDS = 16                # 8-byte words of the reduction's output (VQN_GEOM_OUT_WORDS)
+GEOM_THREADS = 256                 # threads of every workgroup (VQN_GEOM_THREADS)
+GEOM_REDUCE_GRID_CAP = 1024        # workgroups of the reduction's first launch at most (VQN_GEOM_REDUCE_GRID_CAP)
+
+
+class GeomGrid(ctypes.Structure):
+    """struct VqnGeomGrid: its fields, in order"""
+    _fields_ = [('origin', ctypes.c_float * 3), ('h', ctypes.c_float), ('dims', ctypes.c_int32 * 3), ('cells', ctypes.c_int32)]
+
+
+def _rows3(t, name, dtype=torch.float32, rows=None):
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or not t.is_cuda or (rows is not None and t.shape[0] != rows):
+        raise VqnError(f'{name}: expected a contiguous {dtype} device tensor [{"n" if rows is None else rows}, 3], got {t.dtype} '
+                       f'{tuple(t.shape)} contiguous={t.is_contiguous()} device={t.device}')
+    return t
+
+
+def geom_grid_plan(lo, hi, n, cell=None):
+    """The grid over n reference points of bounding box lo .. hi (three floats each; host only) -> GeomGrid.  cell: its size, None for
+    the default.  A plan the library refuses raises ValueError with its reason."""
+    grid = GeomGrid()
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float32).reshape(3), np.ascontiguousarray(hi, dtype=np.float32).reshape(3)
+    rc = lib().vqn_geom_grid_plan(lo.ctypes.data, hi.ctypes.data, int(n), 0.0 if cell is None else float(cell), ctypes.addressof(grid))
+    if rc != 0:
+        raise ValueError(lib().vqn_last_error().decode())
+    return grid
+
+
+def geom_tri_areas(vertices, triangles):
+    """vertices f32 [V,3], triangles int32 [T,3] -> float64 [T] (vqn_geom_tri_areas)."""
+    _rows3(vertices, 'vertices')
+    _rows3(triangles, 'triangles', torch.int32)
+    areas = torch.empty((triangles.shape[0],), dtype=torch.float64, device=vertices.device)
+    _call('vqn_geom_tri_areas', _ptr(vertices), int(vertices.shape[0]), _ptr(triangles), int(triangles.shape[0]), _ptr(areas))
+    return areas
+
+
+def geom_sample_surface(vertices, triangles, cum, u):
+    """cum float64 [T] = the inclusive prefix sum of the areas, u f32 [n,3] in [0,1) -> (points f32 [n,3], normals f32 [n,3], face
+    int32 [n]) (vqn_geom_sample_surface)."""
+    _rows3(vertices, 'vertices')
+    _rows3(triangles, 'triangles', torch.int32)
+    _rows3(u, 'u')
+    T, n = int(triangles.shape[0]), int(u.shape[0])
+    if cum.dtype != torch.float64 or tuple(cum.shape) != (T,) or not cum.is_contiguous() or cum.device != vertices.device:
+        raise VqnError(f'geom_sample_surface: cum must be a contiguous float64 [{T}] on the device of the vertices')
+    points = torch.empty((n, 3), dtype=torch.float32, device=vertices.device)
+    normals = torch.empty((n, 3), dtype=torch.float32, device=vertices.device)
+    face = torch.empty((n,), dtype=torch.int32, device=vertices.device)
+    _call('vqn_geom_sample_surface', _ptr(vertices), int(vertices.shape[0]), _ptr(triangles), T, _ptr(cum), _ptr(u), n, _ptr(points),
+          _ptr(normals), _ptr(face))
+    return points, normals, face
+
+
+def geom_cell_ids(points, grid):
+    """points f32 [n,3] -> int32 [n], the id of each point's cell of `grid` (vqn_geom_cell_ids)."""
+    _rows3(points, 'points')
+    ids = torch.empty((points.shape[0],), dtype=torch.int32, device=points.device)
+    _call('vqn_geom_cell_ids', _ptr(points), int(points.shape[0]), ctypes.addressof(grid), _ptr(ids))
+    return ids
+
+
+def geom_pack_sorted(points, order):
+    """points f32 [n,3], order int64 [n] (a permutation) -> f32 [n,4]: record j = (x, y, z, the bits of order[j]) of point order[j]
+    (vqn_geom_pack_sorted)."""
+    _rows3(points, 'points')
+    n = int(points.shape[0])
+    if order.dtype != torch.int64 or tuple(order.shape) != (n,) or not order.is_contiguous() or order.device != points.device:
+        raise VqnError(f'geom_pack_sorted: order must be a contiguous int64 [{n}] on the device of the points')
+    packed = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+    _call('vqn_geom_pack_sorted', _ptr(points), n, _ptr(order), _ptr(packed))
+    return packed
+
+
+def geom_nearest(query, packed, cell_start, grid, max_d2=float('inf'), q_order=None):
+    """query f32 [n_q,3]; packed f32 [n_ref,4], cell_start int32 [cells + 1] and grid: the sorted reference -> (d2 f32 [n_q], idx int32
+    [n_q], the original index; -1 / +inf where the nearest d2 > max_d2).  q_order int32 [n_q]: the order in which threads take the
+    queries.  One launch (vqn_geom_nearest)."""
+    _rows3(query, 'query')
+    n_q, n_ref = int(query.shape[0]), int(packed.shape[0])
+    if packed.dtype != torch.float32 or packed.dim() != 2 or packed.shape[1] != 4 or not packed.is_contiguous() or packed.device != query.device:
+        raise VqnError('geom_nearest: packed must be the contiguous float32 [n_ref, 4] of geom_pack_sorted on the device of the queries')
+    if cell_start.dtype != torch.int32 or tuple(cell_start.shape) != (grid.cells + 1,) or not cell_start.is_contiguous() \
+            or cell_start.device != query.device:
+        raise VqnError(f'geom_nearest: cell_start must be a contiguous int32 [{grid.cells + 1}] on the device of the queries')
+    if q_order is not None and (q_order.dtype != torch.int32 or tuple(q_order.shape) != (n_q,) or not q_order.is_contiguous()
+                                or q_order.device != query.device):
+        raise VqnError(f'geom_nearest: q_order must be a contiguous int32 [{n_q}] on the device of the queries')
+    d2 = torch.empty((n_q,), dtype=torch.float32, device=query.device)
+    idx = torch.empty((n_q,), dtype=torch.int32, device=query.device)
+    _call('vqn_geom_nearest', _ptr(query), n_q, _ptr(q_order), _ptr(packed), _ptr(cell_start), n_ref, ctypes.addressof(grid), float(max_d2),
+          _ptr(d2), _ptr(idx))
+    return d2, idx
+
+
+def geom_reduce(d2, idx, n_ref, thresholds=(), q_normals=None, ref_normals=None):
+    """The directed sums of one nearest-neighbour result -> int64 [16], the words of vqn_geom_reduce's `out` (view 10..13 as float64).
+    Two launches, no host read."""
+    n = int(d2.shape[0])
+    if d2.dtype != torch.float32 or idx.dtype != torch.int32 or d2.dim() != 1 or tuple(idx.shape) != (n,) or not (d2.is_cuda and idx.is_cuda) \
+            or not (d2.is_contiguous() and idx.is_contiguous()):
+        raise VqnError('geom_reduce: expected contiguous device tensors d2 float32 [n] and idx int32 [n]')
+    if q_normals is not None:
+        _rows3(q_normals, 'q_normals', rows=n)
+    if ref_normals is not None:
+        _rows3(ref_normals, 'ref_normals', rows=int(n_ref))
+    out = torch.empty((GEOM_OUT_WORDS,), dtype=torch.int64, device=d2.device)
+    need = lib().vqn_geom_reduce_scratch_bytes(n)
+    buf = _scratch('geom_reduce', max(need, 64), d2.device)             # (need = 0: a shape the call itself refuses, with the reason)
+    _call('vqn_geom_reduce', _ptr(d2), _ptr(idx), n, _ptr(q_normals), _ptr(ref_normals), int(n_ref), _host(thresholds, np.float64),
+          len(thresholds), _ptr(buf), buf.numel(), _ptr(out))
+    return out
 
 
 # --------------------------------------------------------------------------------------

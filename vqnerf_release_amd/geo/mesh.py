@@ -11,6 +11,9 @@ Clean-up and attributes, also on the device: connected com
 The sparse route (`plan_bricks`, `marching_cubes_bricks`, `extract_geometry_sparse`; csrc/marching_cubes_bricks.hip) evaluates the
 network only on the 8^3-cell bricks the surface can pass through and returns the same bytes, also at resolutions the dense route
 refuses; it reads the host twice.
+
+For scoring a mesh (geo/geometry_eval.py): `read_ply` reads what `write_ply` writes and point-cloud files,
+`sample_surface` draws points of the surface uniformly by area through csrc/geometry_eval.hip.
 """
 import numpy as np
 import torch
@@ -383,3 +386,117 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
         f.write(header.encode('ascii'))
         f.write(rows.tobytes())
         f.write(faces.tobytes())
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def _ply_header(f, path):
+    """-> (binary?, [(element, count, [(property, type) or (property, count type, item type)])])"""
+    if f.readline().strip() != b'ply':
+        raise _C.VqnError(f'read_ply: {path} is not a PLY file')
+    fmt, elements = None, []
+    for _ in range(1 << 16):                                               # (a header is tens of lines)
+        raw = f.readline()
+        if not raw:
+            raise _C.VqnError(f'read_ply: {path}: the header does not end')
+        w = raw.decode('ascii', 'replace').split()
+        if not w or w[0] in ('comment', 'obj_info'):
+            continue
+        if w[0] == 'end_header':
+            break
+        if w[0] == 'format' and len(w) >= 2:
+            fmt = w[1]
+        elif w[0] == 'element' and len(w) == 3 and w[2].isdigit():
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == 'property' and elements and len(w) == 5 and w[1] == 'list' and w[2] in _PLY_TYPES and w[3] in _PLY_TYPES:
+            elements[-1][2].append((w[4], _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]))
+        elif w[0] == 'property' and elements and len(w) == 3 and w[1] in _PLY_TYPES:
+            elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
+        else:
+            raise _C.VqnError(f'read_ply: {path}: header line not understood: {raw!r}')
+    else:
+        raise _C.VqnError(f'read_ply: {path}: the header does not end')
+    if fmt not in ('ascii', 'binary_little_endian'):
+        raise _C.VqnError(f'read_ply: {path}: format {fmt} is not read (ascii and binary_little_endian are)')
+    return fmt != 'ascii', elements
+
+
+def _ply_rows(f, path, binary, name, count, props):
+    """the rows of one element as {property: array [count] or, for a list of a fixed length, [count, length]}"""
+    lists = [p for p in props if len(p) == 3]
+    if lists and (len(props) != 1 or name != 'face'):
+        raise _C.VqnError(f'read_ply: {path}: element {name}: a list property is read only as the single property of `face`')
+    if binary:
+        if lists:
+            _, ct, it = props[0]
+            dt = np.dtype([('n', '<' + ct), ('v', '<' + it, (3,))])
+        else:
+            dt = np.dtype([(p, '<' + t) for p, t in props])
+        buf = f.read(dt.itemsize * count)
+        rows = np.frombuffer(buf, dt, len(buf) // dt.itemsize)
+        if lists and (rows['n'] != 3).any():                               # (read as rows of three: the first other face shows here)
+            raise _C.VqnError(f'read_ply: {path}: only triangle faces are read')
+        if len(rows) != count:
+            raise _C.VqnError(f'read_ply: {path}: element {name} is cut short')
+        if lists:
+            return {props[0][0]: rows['v']}
+        return {p: rows[p] for p, _ in props}
+    width = 4 if lists else len(props)
+    vals = []
+    for _ in range(count):
+        w = f.readline().split()
+        if lists and w and w[0] != b'3':
+            raise _C.VqnError(f'read_ply: {path}: only triangle faces are read')
+        if len(w) != width:
+            raise _C.VqnError(f'read_ply: {path}: element {name}: a row of {len(w)} values, expected {width}')
+        vals.append(w)
+    a = np.array(vals, dtype=np.float64).reshape(count, width)
+    if lists:
+        return {props[0][0]: a[:, 1:]}
+    return {p: a[:, i] for i, (p, _) in enumerate(props)}
+
+
+def read_ply(path, device='cuda'):
+    """-> (vertices f32 [V,3], triangles int32 [T,3] or None, normals f32 [V,3] or None), tensors on `device`.  Reads ASCII and binary
+    little-endian files whose `vertex` element has x y z and perhaps nx ny nz (colours and other scalar properties are skipped) and
+    whose `face` element, if any, is one list `vertex_indices` / `vertex_index` of three: what write_ply writes, and point clouds
+    without faces (DTU's scans).  Anything else -- big-endian data, faces that are not triangles -- raises VqnError."""
+    with open(path, 'rb') as f:
+        binary, elements = _ply_header(f, path)
+        vert = tri = None
+        for name, count, props in elements:
+            rows = _ply_rows(f, path, binary, name, count, props)
+            if name == 'vertex':
+                vert = rows
+            elif name == 'face':
+                key = next((k for k in ('vertex_indices', 'vertex_index') if k in rows), None)
+                if key is None:
+                    raise _C.VqnError(f'read_ply: {path}: element face has no vertex_indices / vertex_index list')
+                tri = rows[key]
+    if vert is None or not all(k in vert for k in 'xyz'):
+        raise _C.VqnError(f'read_ply: {path}: no vertex element with x, y and z')
+    xyz = np.stack([vert[k] for k in 'xyz'], 1).astype(np.float32)
+    nrm = np.stack([vert[k] for k in ('nx', 'ny', 'nz')], 1).astype(np.float32) if all(k in vert for k in ('nx', 'ny', 'nz')) else None
+    if tri is not None:
+        if len(tri) and (tri.min() < 0 or tri.max() >= len(xyz)):
+            raise _C.VqnError(f'read_ply: {path}: a face names a vertex outside 0 .. {len(xyz) - 1}')
+        tri = torch.as_tensor(np.array(tri, dtype=np.int32).reshape(-1, 3), device=device)        # (a copy: the file's bytes are read-only)
+    return (torch.as_tensor(np.ascontiguousarray(xyz), device=device), tri,
+            None if nrm is None else torch.as_tensor(np.ascontiguousarray(nrm), device=device))
+
+
+def sample_surface(vertices, triangles, n, generator=None, u=None):
+    """n points of the surface, uniform by area (csrc/geometry_eval.hip: the face by binary search of the area prefix sum, the point
+    (1 - sqrt(u1)) v0 + sqrt(u1) (1 - u2) v1 + sqrt(u1) u2 v2) -> (points f32 [n,3], unit face normals f32 [n,3], face int32 [n]).
+    The randomness is an input: u f32 [n,3] in [0,1), or drawn from `generator` (a device generator; None: torch's global one)."""
+    _C.require_device(vertices, 'sample_surface')
+    vertices = vertices.detach().to(torch.float32).contiguous()
+    triangles = triangles.to(torch.int32).contiguous()
+    if u is None:
+        u = torch.rand((int(n), 3), dtype=torch.float32, device=vertices.device, generator=generator)
+    elif tuple(u.shape) != (int(n), 3):
+        raise _C.VqnError(f'sample_surface: u must be [{int(n)}, 3], got {tuple(u.shape)}')
+    cum = torch.cumsum(_C.geom_tri_areas(vertices, triangles), 0)
+    return _C.geom_sample_surface(vertices, triangles, cum, u.contiguous())

@@ -350,6 +350,15 @@ class Runner:
         mesh.write_ply(path, vertices, triangles, normals=nrm, colors=col)
         return path
 
+    def evaluate_mesh(self, gt_path, mesh_path=None, **kw):
+        """Scores a mesh validate_mesh wrote -- mesh_path, or the newest `meshes/{iter:08d}.ply` -- against the PLY file gt_path (a mesh
+        or a point cloud such as DTU's scans): Chamfer, F-score, normal consistency (geo/geometry_eval.py, **kw to its
+        surface_scores), on the device.  Writes `meshes/{iter:08d}_geometry.json` beside the mesh and returns the dict."""
+        from vqnerf_release_amd.geo import geometry_eval
+        if mesh_path is None:
+            mesh_path = geometry_eval.newest_mesh(os.path.join(self.base_exp_dir, 'meshes'))
+        return geometry_eval.evaluate(mesh_path, gt_path, out_json=mesh_path[:-4] + '_geometry.json', device=self.device, **kw)
+
     # ---- checkpoints: same keys / file names as nerf_runner.py:210-232 ----
     def save_checkpoint(self):
         ckpt = {'nerf': self.nerf_outside.state_dict(), 'sdf_network_fine': self.sdf_network.state_dict(),
