@@ -53,7 +53,8 @@ def one_row(W, subsampling):
 
 def encoder_cases():
     """(id, content, H, W, N, quality, subsampling, Ri or None).  Every size with every subsampling and every interval on noise, three
-    different frames a batch; every quality on the two larger sizes; every content; N = 1."""
+    different frames a batch; every quality on the two larger sizes; every content; N = 1; batches of more restart intervals than
+    the 256 threads of the one-workgroup scan that places them (csrc/codec_stream.h), so that a thread takes a run of them."""
     out = []
     for H, W in SIZES:
         for sub in SUBSAMPLINGS:
@@ -76,4 +77,8 @@ def encoder_cases():
         out.append(('checker', 64, 64, 3, 100, sub, None))
         out.append(('checker', 17, 23, 3, 75, sub, 1))
         out.append(('checker', 40, 56, 1, 50, sub, 3))
+    out.append(('noise', 8, 2056, 1, 75, '444', 1))                      # 257 intervals: runs of 2, one of 1, empty threads behind
+    out.append(('noise', 72, 72, 4, 75, '444', 1))                       # 4 x 81: frames begin and end in the middle of a run
+    out.append(('noise', 16, 128, 16, 75, '444', 1))                     # 16 x 32 = 512: every thread a full run of 2
+    out.append(('noise', 8, 128, 16, 75, '444', 1))                      # 16 x 16 = 256: exactly one interval per thread
     return [('-'.join(str(v) for v in c), ) + c for c in out]

@@ -62,7 +62,8 @@ def batch(content, H, W, C, N):
 def encoder_cases():
     """(id, content, H, W, C, N, filters, rows_per_segment: an int, 'all' or None).  Every shape with every channel count under the
     adaptive filter and the default segments; every forced filter and every segment length on the shapes of more than one row; every
-    content; the row of the largest stride; the runs at the length-code boundaries; runs and match sources across segment ends."""
+    content; the row of the largest stride; the runs at the length-code boundaries; runs and match sources across segment ends;
+    batches of at least as many images as the 256 threads of the one-workgroup scan that places them (csrc/codec_stream.h)."""
     out = []
     for H, W in SHAPES:
         for C in (1, 2, 3, 4):
@@ -86,6 +87,8 @@ def encoder_cases():
     out.append(('zeros', 7, 300, 1, 1, 'none', 2))                        # ... by matches of 258 and by the end
     out.append(('same_rows', 6, 23, 3, 1, 'none', 1))                     # match sources in the previous segment only
     out.append(('same_rows', 6, 23, 3, 3, 'none', 2))
+    out.append(('noise', 1, 1, 1, 257, 'none', None))                     # a scan thread takes two images, the last threads none
+    out.append(('noise', 2, 3, 1, 256, 'none', 1))                        # one image per thread, two segments each
     out = list(dict.fromkeys(out))                                        # (a case two of the rules name is one case)
     return [('-'.join(str(v) for v in c), ) + c for c in out]
 

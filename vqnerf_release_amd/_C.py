@@ -994,16 +994,32 @@ JPEG_GEOM = ('n', 'h', 'w', 'quality', 'sub', 'ri', 'mcu', 'mcus_x', 'mcus_y', '
              'by_c', 'bx_c', 'off_cb', 'off_cr', 'off_slots', 'off_lens', 'off_dst', 'scratch_bytes', 'out_bytes', 'header_bytes')
 
 
+def _codec_plan(entry, fields, head_cap, *args):
+    """jpeg_plan / png_plan: the planner `entry` over *args -> ({name: int} over `fields`, its head_cap bytes of a file's front)"""
+    geom = np.zeros(len(fields), np.int64)
+    head = np.zeros(head_cap, np.uint8)
+    rc = getattr(lib(), entry)(*(int(a) for a in args), geom.ctypes.data, head.ctypes.data, head.size)
+    if rc != 0:
+        raise ValueError(lib().vqn_last_error().decode())
+    return {k: int(v) for k, v in zip(fields, geom)}, head
+
+
+def _codec_encode(name, fields, x, last, g, scratch, out, meta):
+    """jpeg_encode / png_encode: vqn_<name> on x with the planner's arguments (the first six of `fields`) out of the plan g"""
+    want = (g['n'], g['h'], g['w'], last)
+    if x.dtype != torch.uint8 or tuple(x.shape) != want or not x.is_contiguous():
+        raise VqnError(f'{name}: expected a contiguous uint8 {list(want)} tensor, got {x.dtype} '
+                       f'{tuple(x.shape)} contiguous={x.is_contiguous()}')
+    require_device(x, name)
+    only = out is None
+    _call('vqn_' + name, _ptr(x), *[g[k] for k in fields[:6]], _ptr(scratch), scratch.numel(), _ptr(out), 0 if only else out.numel(),
+          _ptr(meta), int(only))
+
+
 def jpeg_plan(n, h, w, quality, subsampling, restart_interval):
     """The planner's view of a batch (host only): ({name: int} over JPEG_GEOM, the header bytes SOI .. SOS).  subsampling 420 or 444.
     A batch it refuses raises ValueError with its reason."""
-    geom = np.zeros(len(JPEG_GEOM), np.int64)
-    header = np.zeros(JPEG_HEADER_CAP, np.uint8)
-    rc = lib().vqn_jpeg_plan(int(n), int(h), int(w), int(quality), int(subsampling), int(restart_interval), geom.ctypes.data,
-                             header.ctypes.data, header.size)
-    if rc != 0:
-        raise ValueError(lib().vqn_last_error().decode())
-    g = {k: int(v) for k, v in zip(JPEG_GEOM, geom)}
+    g, header = _codec_plan('vqn_jpeg_plan', JPEG_GEOM, JPEG_HEADER_CAP, n, h, w, quality, subsampling, restart_interval)
     return g, header[:g['header_bytes']].tobytes()
 
 
@@ -1011,13 +1027,7 @@ def jpeg_encode(frames, g, scratch, out=None, meta=None):
     """frames uint8 [n, h, w, 3] contiguous device tensor, g the plan of its batch, scratch a uint8 device buffer of g['scratch_bytes']
     (g['off_slots'] when out is None: the coefficients only).  Fills scratch (the coefficient planes first), out and meta int64 [n, 2];
     no host read."""
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or tuple(frames.shape) != (g['n'], g['h'], g['w'], 3) or not frames.is_contiguous():
-        raise VqnError(f"jpeg_encode: expected a contiguous uint8 [{g['n']}, {g['h']}, {g['w']}, 3] tensor, got {frames.dtype} "
-                       f'{tuple(frames.shape)} contiguous={frames.is_contiguous()}')
-    require_device(frames, 'jpeg_encode')
-    only = out is None
-    _call('vqn_jpeg_encode', _ptr(frames), g['n'], g['h'], g['w'], g['quality'], g['sub'], g['ri'], _ptr(scratch), scratch.numel(),
-          _ptr(out), 0 if only else out.numel(), _ptr(meta), int(only))
+    _codec_encode('jpeg_encode', JPEG_GEOM, frames, 3, g, scratch, out, meta)
 
 
 # PNG files of device images (csrc/png_encode.hip, csrc/png_plan.h, include/vqn_image_codec.h; decomp/nerfactor/util/png.py)
@@ -1032,26 +1042,15 @@ PNG_HEAD_BYTES = 33                # bytes of a file in front of IDAT (VQN_PNG_H
 def png_plan(n, h, w, c, filter_mode, rows_per_segment):
     """The planner's view of a batch (host only): ({name: int} over PNG_GEOM, the 33 bytes of a file in front of IDAT).  filter_mode:
     a value of PNG_FILTERS.  A batch it refuses raises ValueError with its reason."""
-    geom = np.zeros(len(PNG_GEOM), np.int64)
-    head = np.zeros(PNG_HEAD_BYTES, np.uint8)
-    rc = lib().vqn_png_plan(int(n), int(h), int(w), int(c), int(filter_mode), int(rows_per_segment), geom.ctypes.data, head.ctypes.data,
-                            head.size)
-    if rc != 0:
-        raise ValueError(lib().vqn_last_error().decode())
-    return {k: int(v) for k, v in zip(PNG_GEOM, geom)}, head.tobytes()
+    g, head = _codec_plan('vqn_png_plan', PNG_GEOM, PNG_HEAD_BYTES, n, h, w, c, filter_mode, rows_per_segment)
+    return g, head.tobytes()
 
 
 def png_encode(images, g, scratch, out=None, meta=None):
     """images uint8 [n, h, w, c] contiguous device tensor, g the plan of its batch, scratch a uint8 device buffer of g['scratch_bytes']
     (n h stride when out is None: the filtered stream only).  Fills scratch (the filtered stream first), out and meta int64 [n, 2];
     no host read."""
-    if images.dtype != torch.uint8 or tuple(images.shape) != (g['n'], g['h'], g['w'], g['c']) or not images.is_contiguous():
-        raise VqnError(f"png_encode: expected a contiguous uint8 [{g['n']}, {g['h']}, {g['w']}, {g['c']}] tensor, got {images.dtype} "
-                       f'{tuple(images.shape)} contiguous={images.is_contiguous()}')
-    require_device(images, 'png_encode')
-    only = out is None
-    _call('vqn_png_encode', _ptr(images), g['n'], g['h'], g['w'], g['c'], g['filter_mode'], g['rows_per_segment'], _ptr(scratch),
-          scratch.numel(), _ptr(out), 0 if only else out.numel(), _ptr(meta), int(only))
+    _codec_encode('png_encode', PNG_GEOM, images, g['c'], g, scratch, out, meta)
 
 
 def _f64_rows(t, name, D=None):

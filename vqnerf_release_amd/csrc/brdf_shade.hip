@@ -10,6 +10,7 @@
 // one pass over the geometry and the visibility row.
 // Bound: HBM for data_type == 'nerf' (2 KB of lvis per point) -- VALU otherwise; see DESIGN.md.
 #include "common.h"
+#include "wave.h"
 #include <stdlib.h>
 #include "vqnerf_hip.h"
 #include <math.h>
@@ -18,11 +19,6 @@ namespace {
 
 constexpr float PI_F = 3.14159265358979323846f;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 __device__ __forceinline__ float div_no_nan(float a, float b) { return b == 0.f ? 0.f : a / b; }
 // tf.linalg.l2_normalize: x * rsqrt(max(sum(x^2), eps))   (util/math.py:63-64, eps = 1e-6)

@@ -12,6 +12,7 @@
 // a naive chain rule: divide_no_nan and SqrtGrad give 0 (not NaN) at |v| = 0.
 // One wave per PAIR of points: lanes 0 / 1 do the per-point scalar arithmetic, all 64 lanes the D-long dot product of the pair.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -30,12 +31,6 @@ __device__ __forceinline__ void chroma(const float v[3], float c[3], float& norm
   norm = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
   const float inv = norm == 0.f ? 0.f : 1.f / norm;
   c[0] = v[0] * inv; c[1] = v[1] * inv; c[2] = v[2] * inv;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // the pair's smoothness weight w_s * exp(-alpha e) (sRGB targets) and dot product <z_a, z_b>; every lane returns both

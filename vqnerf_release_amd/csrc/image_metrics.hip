@@ -24,6 +24,7 @@
 // All LDS accesses of the two passes are lane-consecutive 8-byte words (ds_read_b64 / ds_write_b64: conflict-free within each
 // 32-lane half whatever the row stride).
 #include "common.h"
+#include "wave.h"
 #include "vqn_eval.h"
 
 // every product and sum below is rounded on its own (the statement's PSNR is matched bit for bit); fma() is written where wanted
@@ -73,18 +74,6 @@ __device__ __forceinline__ unsigned load_pixel(const void* img, const ImArgs& g,
 __device__ __forceinline__ double plane_value(const unsigned v, const int p) {
   if (p < 3) return (double)((v >> (8 * p)) & 255u);
   return 0.2126 * (double)(v & 255u) + 0.7152 * (double)((v >> 8) & 255u) + 0.0722 * (double)((v >> 16) & 255u);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 template <bool F32>
@@ -190,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void image_metrics_kernel(const ImArgs g,
   for (int p = 0; p < 4; ++p) vals[p] = wave_sum(ssim[p]);
   vals[4] = wave_sum(luma_se);
   unsigned long long isum[3];
-  for (int c = 0; c < 3; ++c) isum[c] = wave_sum_u64((unsigned long long)sse[c]);
+  for (int c = 0; c < 3; ++c) isum[c] = wave_sum((unsigned long long)sse[c]);
   const int wave = tid >> 6;
   if ((tid & 63) == 0) {
     for (int s = 0; s < 5; ++s) red[wave][s] = vals[s];
@@ -243,7 +232,7 @@ __global__ __launch_bounds__(64) void image_metrics_finalize_kernel(const double
     for (int c = 0; c < 3; ++c) is[c] += __double_as_longlong(src[5 + c]);
   }
   for (int s = 0; s < 5; ++s) fs[s] = wave_sum(fs[s]);
-  for (int c = 0; c < 3; ++c) is[c] = (long long)wave_sum_u64((unsigned long long)is[c]);
+  for (int c = 0; c < 3; ++c) is[c] = (long long)wave_sum((unsigned long long)is[c]);
   if (lane != 0) return;
   const long long npix = (long long)H * W, npos = (long long)(H - kHalo) * (W - kHalo);
   if (C == 1) {                                                              // luma of a one-channel image is the channel

@@ -26,8 +26,10 @@
 //      jpeg_meta_kernel turns into offsets and lengths.
 //   4. jpeg_compact_kernel: one workgroup per (interval, frame) copies the slot to its place and appends its RST marker.
 // Everything is integer work or f32 arithmetic in a fixed order: equal frames give equal bytes.
+#include "codec_stream.h"
 #include "common.h"
 #include "jpeg_plan.h"
+#include "wave.h"
 #include "vqn_image_codec.h"
 
 #pragma clang fp contract(off)
@@ -204,17 +206,6 @@ constexpr int kBitWords = 64;                // LDS words of a wave's bit buffer
 static_assert((7 + kJpegBlockBits + 31) / 32 + 2 <= kBitWords, "a block fits the bit buffer");
 constexpr int kHuffWords = sizeof(JpegHuff) / 4;
 
-__device__ __forceinline__ int wave_exclusive_sum(const int v, const int lane, int* total) {
-  int s = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(s, d, 64);
-    if (lane >= d) s += t;
-  }
-  *total = __shfl(s, 63, 64);
-  return s - v;
-}
-
 // byte i of the bit buffer (bits run from the top of word 0)
 __device__ __forceinline__ uint32_t bit_byte(const uint32_t* words, const int i) { return (words[i >> 2] >> (24 - 8 * (i & 3))) & 255u; }
 
@@ -332,27 +323,15 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const EntropyArgs a) {
 
 // ---- 3. places of the intervals -------------------------------------------------------------------------------------------------------
 // dst[f][i] = bytes in front of interval i of frame f in the output: every interval of a frame but its last is followed by two bytes of
-// RST.  meta[f] = {offset, length} of frame f.  One workgroup; thread t sums a contiguous run of the items, the runs are scanned in LDS.
+// RST.  meta[f] = {offset, length} of frame f.  One workgroup; the runs of the threads and their scan: csrc/codec_stream.h.
 __global__ __launch_bounds__(kThreads) void jpeg_scan_kernel(const uint32_t* lens, int64_t* dst, int64_t* meta, const int64_t n_frames,
                                                              const int64_t intervals) {
-  __shared__ int64_t sums[kThreads];
   const int tid = threadIdx.x;
-  const int64_t items = n_frames * intervals, per = (items + kThreads - 1) / kThreads;
-  const int64_t i0 = min(items, tid * per), i1 = min(items, i0 + per);
+  int64_t i0, i1;
+  codec_run<kThreads>(n_frames * intervals, tid, &i0, &i1);
   int64_t s = 0;
   for (int64_t i = i0; i < i1; ++i) s += (int64_t)lens[i] + ((i % intervals) + 1 < intervals ? 2 : 0);
-  sums[tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    int64_t run = 0;
-    for (int t = 0; t < kThreads; ++t) {
-      const int64_t v = sums[t];
-      sums[t] = run;
-      run += v;
-    }
-  }
-  __syncthreads();
-  s = sums[tid];
+  s = codec_scan_runs<kThreads>(s, tid);
   for (int64_t i = i0; i < i1; ++i) {
     dst[i] = s;
     s += (int64_t)lens[i] + ((i % intervals) + 1 < intervals ? 2 : 0);
@@ -374,7 +353,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_compact_kernel(const uint8_t* s
   const uint8_t* src = slots + item * slot_bytes;
   const int64_t n = lens[item], at = dst[item];
   if (at + n + 2 > out_bytes) return;                                    // (the planner sized `out` by the worst case: never taken)
-  for (int64_t i = threadIdx.x; i < n; i += kThreads) out[at + i] = src[i];
+  codec_copy_slot<kThreads>(src, out, at, n, threadIdx.x);
   if (threadIdx.x == 0 && blockIdx.x + 1 < intervals) {
     out[at + n] = 0xff;
     out[at + n + 1] = (uint8_t)(0xd0 + (blockIdx.x & 7));
@@ -382,12 +361,8 @@ __global__ __launch_bounds__(kThreads) void jpeg_compact_kernel(const uint8_t* s
 }
 
 int plan_or_refuse(const char* fn, int64_t n, int64_t h, int64_t w, int quality, int sub, int64_t ri, JpegGeom* g) {
-  char why[256];
-  const int rc = jpeg_plan(n, h, w, quality, sub, ri, g, why, sizeof(why));
-  if (rc != 0) {
-    vqn_set_error("%s: %s", fn, why);
-    return rc == -2 ? VQN_ESHAPE : VQN_EARG;
-  }
+  const int rc = codec_refuse(fn, [&](char* why, size_t len) { return jpeg_plan(n, h, w, quality, sub, ri, g, why, len); });
+  if (rc != VQN_OK) return rc;
   uint8_t header[kJpegHeaderCap];
   g->header_bytes = jpeg_header(*g, header, sizeof(header));
   return VQN_OK;
@@ -417,11 +392,8 @@ extern "C" int vqn_jpeg_encode(const uint8_t* rgb, int64_t n, int64_t h, int64_t
   if (rc != VQN_OK) return rc;
   VQN_CHECK_ARG(rgb && scratch, "null frames or scratch");
   VQN_CHECK_ARG(((uintptr_t)scratch & 15u) == 0u, "scratch is not 16-byte aligned");
-  char why[256];
-  if (jpeg_check_buffers(g, scratch_bytes, out_bytes, coefficients_only, why, sizeof(why)) != 0) {
-    vqn_set_error("%s: %s", __func__, why);
-    return VQN_EARG;
-  }
+  const auto fits = [&](char* why, size_t len) { return jpeg_check_buffers(g, scratch_bytes, out_bytes, coefficients_only, why, len); };
+  if (const int fit = codec_refuse(__func__, fits); fit != VQN_OK) return fit;
   VQN_CHECK_ARG(coefficients_only || (out && meta), "null out or meta");
   VQN_CHECK_SHAPE(n <= 65535 && g.intervals <= 0x7fffffff && g.mcus_x * g.mcus_y <= 0x7fffffff, "at most 65535 frames in a batch");
   uint8_t* base = (uint8_t*)scratch;

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/vqn_image_codec.h"  // (by path: the stand-alone build of this header names no include directory)
+#include "codec_plan.h"
 
 constexpr int kJpegMaxSide = 65535;
 constexpr int kJpegBlockBits = 64 * 26;                  // the most a block codes to: 64 coefficients of a 16-bit code + 10 bits
@@ -138,20 +139,9 @@ inline int jpeg_plan(int64_t n, int64_t h, int64_t w, int quality, int sub, int6
   return 0;
 }
 
-// The buffers a caller hands to the encoder against the plan -> 0, or -1 with the reason in msg.  coefficients_only: the first kernel
-// alone runs, which needs the coefficient planes of the scratch and no output.
+// codec_check_buffers for this plan.  coefficients_only: the first kernel alone runs, which needs the coefficient planes and no output.
 inline int jpeg_check_buffers(const JpegGeom& g, int64_t scratch_bytes, int64_t out_bytes, int coefficients_only, char* msg, size_t msg_len) {
-  const int64_t need = coefficients_only ? g.off_slots : g.scratch_bytes;
-  if (scratch_bytes < need) {
-    snprintf(msg, msg_len, "bad argument: the scratch holds %lld bytes, the batch needs %lld", (long long)scratch_bytes, (long long)need);
-    return -1;
-  }
-  if (!coefficients_only && out_bytes < g.out_bytes) {
-    snprintf(msg, msg_len, "bad argument: a byte total of up to %lld over the buffer of %lld bytes", (long long)g.out_bytes,
-             (long long)out_bytes);
-    return -1;
-  }
-  return 0;
+  return codec_check_buffers(g.off_slots, g.scratch_bytes, g.out_bytes, scratch_bytes, out_bytes, coefficients_only, msg, msg_len);
 }
 
 // The header of a file: SOI, APP0 (JFIF 1.01, no density), DQT x 2, SOF0, DHT x 4, DRI, SOS -> its length, or -1 when cap is too small.

@@ -22,6 +22,7 @@
 //      keeps its value; with opt_scale the products albedo' * opt_scale and spec' * opt_scale (one rounded multiply) are written too.
 //      The selection read the planes before this point, and outputs never alias inputs: it is the pre-edit selection.
 #include "common.h"
+#include "wave.h"
 #include "material_edit_plan.h"
 #include "vqn_material_edit.h"
 
@@ -161,23 +162,6 @@ __device__ __forceinline__ void edit_rows(const MatEditArgs& a, const MatEditCon
   }
 }
 
-// table[key] += 1 for every lane with `has`, equal keys of the wave merged first.  Called by all 64 lanes together.
-__device__ __forceinline__ void wave_count(unsigned* table, bool has, const int key, const int lane) {
-  unsigned long long pending = __ballot(has);
-  while (pending) {                                                          // wave-uniform
-    const int leader = __ffsll((long long)pending) - 1;
-    const int k = __builtin_amdgcn_readlane(key, leader);
-    const bool mine = has && key == k;
-    const unsigned long long same = __ballot(mine);
-    const int m = __popcll(same);
-    if (lane == leader) atomicAdd(&table[k], (unsigned)m);
-    has = has && !mine;
-    pending &= ~same;
-    if (m < kMinMerge) break;
-  }
-  if (has) atomicAdd(&table[key], 1u);
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void matedit_kernel(const MatEditArgs a) {
   __shared__ unsigned table[kWords];         // 0 selected, 1 unused, 2 invalid, 3 + c: selected rows of code c
@@ -282,7 +266,7 @@ __global__ __launch_bounds__(kThreads) void matedit_kernel(const MatEditArgs a) 
     }
     if (k.embed) {
 #pragma unroll
-      for (int r = 0; r < kRows; ++r) wave_count(table + kHead, sel[r] && code[r] >= 0, code[r], lane);
+      for (int r = 0; r < kRows; ++r) wave_add<kMinMerge>(table + kHead, sel[r] && code[r] >= 0, code[r], 1u, lane);
     }
 
     // ---- 3. edit ----

@@ -6,6 +6,7 @@
 //   geo/NeuS-ours2/models/renderer.py:229-282 (alpha, transmittance, colour/surf/depth/eikonal) -> vqn_neus_composite_fwd
 //   the reverse of the latter (autograd in the reference)                                     -> vqn_neus_composite_bwd
 #include "common.h"
+#include "wave.h"
 #include <math.h>
 
 namespace {
@@ -15,16 +16,6 @@ constexpr int IT = MAXN / 64;      // items per lane, blocked layout: element i 
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-  return v;
-}
 // exclusive scans over lanes
 __device__ __forceinline__ float wave_excl_prod(float v, int lane) {
   float inc = v;

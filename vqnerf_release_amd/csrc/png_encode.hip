@@ -21,8 +21,10 @@
 //   4. png_compact_kernel: one workgroup per (segment, image) copies the slot to its place; the first and the last of an image add
 //      the two bytes in front and the four behind.
 // Integer work throughout: equal images give equal bytes.
+#include "codec_stream.h"
 #include "common.h"
 #include "png_plan.h"
+#include "wave.h"
 #include "vqn_image_codec.h"
 
 namespace {
@@ -129,24 +131,6 @@ constexpr int kBitWords = 104;               // LDS words of the bit buffer: 7 b
 static_assert((7 + 64 * 48 + 31) / 32 + 3 <= kBitWords, "a window's tokens fit the bit buffer");
 static_assert(kPngHeaderWords + 2 <= kBitWords, "a block header fits the bit buffer");
 static_assert(64 + (kAhead - 1) * 64 - 63 >= kPngMaxMatch, "the carried ballots cover the longest match from the last lane");
-
-__device__ __forceinline__ int wave_exclusive_sum(const int v, const int lane, int* total) {
-  int s = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(s, d, 64);
-    if (lane >= d) s += t;
-  }
-  *total = __shfl(s, 63, 64);
-  return s - v;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // length 3 .. 258 -> its symbol less 257, with the number and the value of its extra bits
 __device__ __forceinline__ int len_symbol(const int len, int* extra_bits, int* extra) {
@@ -407,15 +391,15 @@ __global__ __launch_bounds__(64) void png_deflate_kernel(const DeflateArgs a) {
 }
 
 // ---- 3. places of the segments, the Adler-32 of the images ----------------------------------------------------------------------------
-// Thread t takes a contiguous run of the images: the length of each stream (2 + its segments + 4) and its Adler-32, then, after a
-// scan of the runs' totals in LDS, dst[image][segment] = where the segment's bytes go and meta[image] = {offset, length}.
+// Thread t takes a run of the images (codec_run): the length of each stream (2 + its segments + 4) and its Adler-32, then, after the
+// scan of the runs' totals (codec_scan_runs written out: as a call it costs this kernel two scalar registers), dst and meta.
 __global__ __launch_bounds__(kThreads) void png_scan_kernel(const uint32_t* lens, const uint32_t* adler, int64_t* dst, uint32_t* sums,
                                                             int64_t* meta, const int64_t n_images, const int64_t segments,
                                                             const int64_t segment_bytes, const int64_t image_bytes) {
   __shared__ int64_t totals[kThreads];
   const int tid = threadIdx.x;
-  const int64_t per = (n_images + kThreads - 1) / kThreads;
-  const int64_t i0 = min(n_images, tid * per), i1 = min(n_images, i0 + per);
+  int64_t i0, i1;
+  codec_run<kThreads>(n_images, tid, &i0, &i1);
   int64_t total = 0;
   for (int64_t i = i0; i < i1; ++i) {
     unsigned long long s1 = 1ull, s2 = 0ull;               // of the bytes so far
@@ -462,19 +446,13 @@ __global__ __launch_bounds__(kThreads) void png_compact_kernel(const uint8_t* sl
   const uint8_t* src = slots + item * slot_bytes;
   const int64_t n = min((int64_t)lens[item], slot_bytes), at = dst[item];
   if (at < 2 || at + n + 4 > out_bytes) return;            // (the planner sized `out` by the worst case: never taken)
-  for (int64_t i = threadIdx.x; i < n; i += kThreads) out[at + i] = src[i];
+  codec_copy_slot<kThreads>(src, out, at, n, threadIdx.x);
   if (threadIdx.x == 0 && blockIdx.x == 0) out[at - 2] = 0x78, out[at - 1] = 0x01;
   if (threadIdx.x < 4 && blockIdx.x + 1 == segments) out[at + n + threadIdx.x] = (uint8_t)(sums[image] >> (24 - 8 * threadIdx.x));
 }
 
 int plan_or_refuse(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, int filter_mode, int64_t rows_per_segment, PngGeom* g) {
-  char why[256];
-  const int rc = png_plan(n, h, w, c, filter_mode, rows_per_segment, g, why, sizeof(why));
-  if (rc != 0) {
-    vqn_set_error("%s: %s", fn, why);
-    return rc == -2 ? VQN_ESHAPE : VQN_EARG;
-  }
-  return VQN_OK;
+  return codec_refuse(fn, [&](char* why, size_t len) { return png_plan(n, h, w, c, filter_mode, rows_per_segment, g, why, len); });
 }
 
 }  // namespace
@@ -501,11 +479,8 @@ extern "C" int vqn_png_encode(const uint8_t* pix, int64_t n, int64_t h, int64_t 
   if (rc != VQN_OK) return rc;
   VQN_CHECK_ARG(pix && scratch, "null images or scratch");
   VQN_CHECK_ARG(((uintptr_t)scratch & 15u) == 0u, "scratch is not 16-byte aligned");
-  char why[256];
-  if (png_check_buffers(g, scratch_bytes, out_bytes, filtered_only, why, sizeof(why)) != 0) {
-    vqn_set_error("%s: %s", __func__, why);
-    return VQN_EARG;
-  }
+  const auto fits = [&](char* why, size_t len) { return png_check_buffers(g, scratch_bytes, out_bytes, filtered_only, why, len); };
+  if (const int fit = codec_refuse(__func__, fits); fit != VQN_OK) return fit;
   VQN_CHECK_ARG(filtered_only || (out && meta), "null out or meta");
   uint8_t* base = (uint8_t*)scratch;
   hipStream_t s = (hipStream_t)stream;

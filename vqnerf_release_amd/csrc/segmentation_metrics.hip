@@ -17,10 +17,7 @@
 //    LDS (<= 16.9 KB; the last one is `invalid`).  Label images are flat: all 64 lanes of a wave usually hold the same (g, p), and
 //    one ds_add per pixel would serialise on one counter.  So counts are combined BEFORE they touch LDS:
 //      1. a lane run-length merges its 16 pixels in registers: it presents (key, run length) only where a run ends;
-//      2. per pixel slot the wave merges equal keys: the first presenting lane's key is broadcast, the lanes that hold it are found
-//         with one ballot, their run lengths are added (popcount x length when they agree, a butterfly otherwise) and ONE lane adds
-//         the sum to LDS; this repeats while a round absorbed at least kMinMerge lanes, the rest add for themselves (many distinct
-//         keys: little contention, and leader rounds would only serialise the wave).
+//      2. per pixel slot the wave merges equal keys and ONE lane adds their sum to LDS (wave_add<kMinMerge>, csrc/wave.h).
 //    A flat wave costs one LDS add per 1024 pixels.  Nothing is accumulated across workgroups with atomics: each workgroup writes
 //    its table as plain words to its own slot of the scratch buffer.
 //  * seg_finalize_kernel: one workgroup.  Sums the slots in slot order into int64 cells, then (float64, fixed order of operations):
@@ -39,6 +36,7 @@
 //   9..41  int32    label_map[65] (entries >= C are -1) and one zero word of padding
 //   42..   int64    coo[R][C]
 #include "common.h"
+#include "wave.h"
 #include "vqn_eval.h"
 
 // every quotient and sum below is rounded on its own, as the statement's are
@@ -67,12 +65,6 @@ struct SegArgs {
   uint32_t pal_gt[kMaxSide - 1], pal_pd[kMaxSide - 1];      // R | G << 8 | B << 16, rows 0 .. R - 2 / C - 2 (colour form)
 };
 
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // pixel j of 48 bytes held as 12 words: its three bytes as R | G << 8 | B << 16
 __device__ __forceinline__ uint32_t pixel_of(const uint32_t (&w)[12], const int j) {
   const int o = 3 * j, d = o >> 2, s = (o & 3) * 8;
@@ -86,25 +78,6 @@ __device__ __forceinline__ int palette_label(const uint32_t v, const uint32_t* p
   for (int i = rows - 1; i >= 0; --i)        // descending: the first row that matches is the one left standing
     if (v == pal[i]) label = i + 1;
   return label;
-}
-
-// Adds `cnt` to table[key] for every lane with `has`, equal keys of the wave merged first.  Called by all 64 lanes together.
-__device__ __forceinline__ void wave_add(unsigned* table, bool has, const int key, const unsigned cnt, const int lane) {
-  unsigned long long pending = __ballot(has);
-  while (pending) {                                                          // wave-uniform
-    const int leader = __ffsll((long long)pending) - 1;
-    const int k = __builtin_amdgcn_readlane(key, leader);
-    const unsigned c0 = (unsigned)__builtin_amdgcn_readlane((int)cnt, leader);
-    const bool mine = has && key == k;
-    const unsigned long long same = __ballot(mine);
-    const int m = __popcll(same);
-    const unsigned total = __ballot(mine && cnt != c0) == 0 ? c0 * (unsigned)m : wave_sum_u32(mine ? cnt : 0u);
-    if (lane == leader) atomicAdd(&table[k], total);
-    has = has && !mine;
-    pending &= ~same;
-    if (m < kMinMerge) break;
-  }
-  if (has) atomicAdd(&table[key], cnt);
 }
 
 template <bool RGB, bool VEC>
@@ -201,7 +174,7 @@ __global__ __launch_bounds__(kThreads) void seg_count_kernel(const SegArgs a, un
     for (int j = 0; j < kPix; ++j) {
       run += 1u;
       const bool ends = j == kPix - 1 || key[j + 1] != key[j];
-      wave_add(table, ends && key[j] != kSkip, key[j], run, lane);
+      wave_add<kMinMerge>(table, ends && key[j] != kSkip, key[j], run, lane);
       if (ends) run = 0u;
     }
   }

@@ -5,6 +5,7 @@
 // In the reference these are ~10 framework ops per layer and step (norm, div, mul and their autograd), i.e. ~150 launches for
 // the 13 layers of the NeuS networks; here one wave per row, rows of all layers in one grid (layer table passed by value).
 #include "common.h"
+#include "wave.h"
 
 #define VQN_WN_MAX_LAYERS 24
 
@@ -19,12 +20,6 @@ struct WnTable {
   int rows[VQN_WN_MAX_LAYERS], cols[VQN_WN_MAX_LAYERS], row0[VQN_WN_MAX_LAYERS + 1];
   int n_layers;
 };
-
-__device__ __forceinline__ float wave_sum64(float x) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m);
-  return x;
-}
 
 template <bool BWD>
 __global__ __launch_bounds__(256) void weight_norm_kernel(const WnTable t) {
@@ -42,13 +37,13 @@ __global__ __launch_bounds__(256) void weight_norm_kernel(const WnTable t) {
     ss = fmaf(x, x, ss);
     if (BWD) dot = fmaf(dw[c], x, dot);
   }
-  ss = wave_sum64(ss);
+  ss = wave_sum(ss);
   const float nrm = sqrtf(ss), g = t.g[l][r];
   if (!BWD) {
     float* w = t.out0[l] + (size_t)r * C;
     for (int c = lane; c < C; c += 64) w[c] = (g * v[c]) / nrm;       // the reference's order of operations
   } else {
-    dot = wave_sum64(dot);
+    dot = wave_sum(dot);
     const float inv = 1.f / nrm, k = dot * inv * inv;
     float* dv = t.out0[l] + (size_t)r * C;
     for (int c = lane; c < C; c += 64) dv[c] = g * inv * (dw[c] - v[c] * k);

@@ -11,37 +11,36 @@ import struct
 import torch
 
 from vqnerf_release_amd import _C
+from vqnerf_release_amd.decomp.nerfactor.util.device_codec import DeviceCodec
 
 
-class JpegEncoder:
+class JpegEncoder(DeviceCodec):
     """quality 1 .. 100 (IJG scaling of the Annex K tables), subsampling '420' (what OpenCV's MJPG writes) or '444',
     restart_interval in MCUs (None: one MCU row).  The format and the shape of the device work: csrc/jpeg_encode.hip."""
 
     def __init__(self, quality=75, subsampling='420', restart_interval=None):
+        super().__init__('jpeg', _C.jpeg_encode)
         self.quality, self.subsampling, self.restart_interval = quality, subsampling, restart_interval
-        self._plans = {}
 
     def _plan(self, frames):
         if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise ValueError(f'JpegEncoder: expected a uint8 [N, H, W, 3] tensor, got {getattr(frames, "dtype", type(frames))} '
                              f'{tuple(getattr(frames, "shape", ()))}')
         key = tuple(int(s) for s in frames.shape[:3])
-        if key not in self._plans:
+
+        def make():
             sub = int(self.subsampling) if str(self.subsampling).isdigit() else 0
             ri = self.restart_interval
             if ri is None:                                           # one MCU row
                 mcu = 16 if sub == 420 else 8
                 ri = max((key[2] + mcu - 1) // mcu, 1)
-            self._plans[key] = _C.jpeg_plan(*key, self.quality, sub, ri)     # ValueError with the planner's reason
-        return self._plans[key]
+            return _C.jpeg_plan(*key, self.quality, sub, ri)
+        return self._cached_plan(key, make)
 
     def coefficients(self, frames):
         """-> {'y', 'cb', 'cr': int16 [N, by, bx, 64]}: the quantised coefficients in zigzag order (the first kernel alone)"""
         g, _ = self._plan(frames)
-        _C.require_device(frames, 'JpegEncoder.coefficients')
-        frames = frames.contiguous()
-        scratch = _C._scratch('jpeg', g['scratch_bytes'], frames.device)
-        _C.jpeg_encode(frames, g, scratch)
+        scratch, _ = self._run(frames, g, 'JpegEncoder.coefficients', first_only=True)
         return self._coefficient_views(scratch, g)
 
     @staticmethod
@@ -54,16 +53,8 @@ class JpegEncoder:
         """uint8 [N, H, W, 3] device tensor -> N complete files (header + scan + EOI) as bytes.  One read of the [N, 2] offsets and
         lengths, then one copy of exactly the bytes the batch came to."""
         g, header = self._plan(frames)
-        _C.require_device(frames, 'JpegEncoder.encode')
-        frames = frames.contiguous()
-        scratch = _C._scratch('jpeg', g['scratch_bytes'], frames.device)
-        out = _C._scratch('jpeg_out', g['out_bytes'], frames.device)
-        meta = torch.empty((g['n'], 2), dtype=torch.int64, device=frames.device)
-        _C.jpeg_encode(frames, g, scratch, out, meta)
-        meta_h = meta.cpu()
-        total = int(meta_h[-1, 0] + meta_h[-1, 1])
-        data = out[:total].cpu().numpy().tobytes()
-        files = [header + data[o:o + n] + b'\xff\xd9' for o, n in meta_h.tolist()]
+        scratch, scans = self._run(frames, g, 'JpegEncoder.encode')
+        files = [header + scan + b'\xff\xd9' for scan in scans]
         return (files, self._coefficient_views(scratch, g)) if want_coefficients else files
 
 
