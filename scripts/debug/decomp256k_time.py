@@ -23,7 +23,7 @@ for _ in range(5): tr.train_iter(batch, global_bs=n)
 torch.cuda.synchronize()
 print(f'n={n}: {(time.perf_counter()-t0)/5*1e3:.2f} ms/step')
 from vqnerf_release_amd import _C
-from vqnerf_release_amd.geo import train_programs as tp
+from vqnerf_release_amd import wgrad as tp
 for batched in (False, True):
     tp.BATCHED_WGRAD[0] = batched
     for _ in range(2): tr.train_iter(batch, global_bs=n)

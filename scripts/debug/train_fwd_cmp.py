@@ -17,7 +17,8 @@ col_l = [getattr(runner.color_network, 'lin%d' % l) for l in range(runner.color_
 with torch.no_grad():
     W, b = [m.effective_weight().float() for m in sdf_l], [m.bias.float() for m in sdf_l]
     Wc, bc = [m.effective_weight().float() for m in col_l], [m.bias.float() for m in col_l]
-    wbuf, descs, flat = eng.pack(W, b, Wc, bc, want_flat=True)
+    flat = eng.flat_weights(W, b, Wc, bc)
+    wbuf, descs = eng.program_pack(flat)
     Ta, Tb = eng.alloc_tensors(P, dev), eng.alloc_tensors(P, dev)
     for T in (Ta, Tb):
         T['X'].copy_(x); T['DIRS'].copy_(d)

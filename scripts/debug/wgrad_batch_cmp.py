@@ -3,7 +3,7 @@ sys.path.insert(0, '.')
 import numpy as np, torch
 from oracle import decomp as od
 from oracle import geo as og
-from vqnerf_release_amd.geo import train_programs as tp
+from vqnerf_release_amd import wgrad as tp
 from vqnerf_release_amd.decomp.nerfactor import train_nfr
 from vqnerf_release_amd.decomp.nerfactor.models import get_model_class
 from tests.decomp_util import make_config, load_oracle_params, make_batch

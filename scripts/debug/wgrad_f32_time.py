@@ -2,7 +2,7 @@ import sys, time, os
 sys.path.insert(0, '.')
 import torch, bench
 from vqnerf_release_amd import _C
-from vqnerf_release_amd.geo import train_programs as tp
+from vqnerf_release_amd import wgrad as tp
 dev = torch.device('cuda:0')
 runner, step = bench.geo_train_setup(dev, 0, 2560)
 for phase, mode in enumerate(['f32'] * 8 + ['bf16x3'] * 2 + ['f32'] * 3):

@@ -15,6 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import neus_train_cases as nc                                     # noqa: E402
+from vqnerf_release_amd import wgrad                                       # noqa: E402
 from vqnerf_release_amd.geo import train_programs as tp                     # noqa: E402
 
 SHAPE = 'shipped'
@@ -44,7 +45,7 @@ def main(out_path):
         r64, r32 = ref['f64']['grads']['rgb'], ref['f32']['grads']['rgb']
         for fwd, bwd, wg in SETTINGS:
             os.environ['VQN_TRAIN_FWD'], os.environ['VQN_TRAIN_BWD'] = fwd, bwd
-            tp.wgrad_mode(wg)
+            wgrad.wgrad_mode(wg)
             a, b = run(x, dirs, g), run(x, dirs, -g)
             row = dict(P=P, fwd=fwd, bwd=bwd, wgrad=wg, VQN_X3_BWD_NACC=nacc)
             for k in TENSORS:
@@ -61,7 +62,7 @@ def main(out_path):
     nL, nC = eng.nL, eng.nC
     outs = ['DC%d' % l for l in range(nC, -1, -1)] + ['GOUTF', 'ED'] + ['UD%d' % (l + 1) for l in range(nL)] + ['AB%d' % l for l in range(nL - 1, -1, -1)]
     with torch.no_grad():
-        wbuf, descs, flat = eng.pack(*params, want_flat=True)
+        flat = eng.flat_weights(*params)
         res = {}
         for sgn in (1.0, -1.0):
             T = eng.alloc_tensors(P, x.device)

@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from vqnerf_release_amd import _C
-from vqnerf_release_amd.geo import train_programs as tp
+from vqnerf_release_amd import wgrad as tp
 from vqnerf_release_amd.geo.models.fields import SDFNetwork, RenderingNetwork, SingleVarianceNetwork
 from vqnerf_release_amd.geo.models.renderer import NeuSRenderer
 from vqnerf_release_amd.geo.nerf_runner import SyntheticDataset

@@ -91,7 +91,7 @@ def test_bench_reads_the_profiler_counter_files(tmp_path):
 
 def test_fused_forward_pack_indices_reproduce_the_render_packs():
     """The training forward on the render kernel (vqn_neus_train_fwd) takes its two weight packs as ONE gather each from the
-    flat source vector of NeusTrainEngine.pack(); those gather indices must give exactly SdfPackPlan / ColPackPlan.pack() of the
+    flat source vector of NeusTrainEngine.flat_weights(); those gather indices must give exactly SdfPackPlan / ColPackPlan.pack() of the
     same effective weights (skip layer's 1/sqrt2 included) and the same descriptors."""
     import math
     from vqnerf_release_amd.geo import packing

@@ -149,8 +149,8 @@ def test_network_methods_hip_vs_autograd_path(case):
 @pytest.fixture(params=['f32', 'bf16x3'])
 def wgrad(request):
     """Both weight-gradient contractions against the reference's gradients: the f32 MFMA one (default) and the exact-split
-    bf16x3 one (opt-in, `train_programs.wgrad_mode('bf16x3')`) -- same bound (VERDICT r02 weak #3)."""
-    from vqnerf_release_amd.geo import train_programs as tp
+    bf16x3 one (opt-in, `wgrad.wgrad_mode('bf16x3')`) -- same bound (VERDICT r02 weak #3)."""
+    from vqnerf_release_amd import wgrad as tp
     old = tp.wgrad_mode()
     tp.wgrad_mode(request.param)
     yield request.param

@@ -1,6 +1,6 @@
 """The tile-program interpreter (csrc/tile_vm.hip, vqn_tile_program) op by op against the float64 model of tests/tile_vm_model.py.
 
-Every program is built by the translator of the model from the same case the model runs (geo/train_programs.Program calls, the
+Every program is built by the translator of the model from the same case the model runs (tile_program.Program calls, the
 packs by build_static_packs), runs once (the launch count is asserted), and writes into NaN-prefilled tensors between NaN guards:
   * written set -- the elements that are no longer NaN are exactly the ones the model says the ops write;
   * exact cases -- integer K inputs, weights and biases: every partial sum is exact in float32, so the output EQUALS the float64

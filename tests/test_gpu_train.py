@@ -195,7 +195,7 @@ def test_batched_weight_gradients_are_the_per_weight_sequence_bit_for_bit(monkey
     monkeypatch.setenv('VQN_REFL_TRAIN', 'prog')
     from oracle import decomp as od
     from oracle import geo as og
-    from vqnerf_release_amd.geo import train_programs as tp
+    from vqnerf_release_amd import wgrad as tp
     from vqnerf_release_amd.decomp.nerfactor import train_nfr
     from vqnerf_release_amd.decomp.nerfactor.models import get_model_class
     from tests.test_gpu_neus_render import _build
@@ -492,8 +492,9 @@ def test_training_forward_on_the_render_kernel_matches_the_interpreted_program(P
     sl = [getattr(sdf, 'lin%d' % l) for l in range(sdf.num_layers - 1)]
     cl = [getattr(col, 'lin%d' % l) for l in range(col.num_layers - 1)]
     with torch.no_grad():
-        wbuf, descs, flat = eng.pack([m.effective_weight().float() for m in sl], [m.bias.float() for m in sl],
-                                     [m.effective_weight().float() for m in cl], [m.bias.float() for m in cl], want_flat=True)
+        flat = eng.flat_weights([m.effective_weight().float() for m in sl], [m.bias.float() for m in sl],
+                                [m.effective_weight().float() for m in cl], [m.bias.float() for m in cl])
+        wbuf, descs = eng.program_pack(flat)
         Ta, Tb = eng.alloc_tensors(P, dev), eng.alloc_tensors(P, dev)
         for T in (Ta, Tb):
             T['X'].copy_(x)
@@ -565,8 +566,9 @@ def test_training_backward_on_the_two_image_engine_matches_the_interpreted_progr
     outs = ['DC%d' % l for l in range(eng.nC + 1)] + ['GOUTF', 'ED'] + ['UD%d' % (l + 1) for l in range(eng.nL)] + \
         ['AB%d' % l for l in range(eng.nL)]
     with torch.no_grad():
-        wbuf, descs, flat = eng.pack([m.effective_weight().float() for m in sl], [m.bias.float() for m in sl],
-                                     [m.effective_weight().float() for m in cl], [m.bias.float() for m in cl], want_flat=True)
+        flat = eng.flat_weights([m.effective_weight().float() for m in sl], [m.bias.float() for m in sl],
+                                [m.effective_weight().float() for m in cl], [m.bias.float() for m in cl])
+        wbuf, descs = eng.program_pack(flat)
         Ta, Tb = eng.alloc_tensors(P, dev), eng.alloc_tensors(P, dev)
         for T in (Ta, Tb):
             T['X'].copy_(x)
@@ -931,8 +933,8 @@ def test_training_backward_is_linear_in_the_adjoints_at_a_large_point_count(mode
         ['AB%d' % l for l in range(eng.nL)]
     run = eng.run_fused_backward_x3 if mode == 'x3' else eng.run_fused_backward
     with torch.no_grad():
-        wbuf, descs, flat = eng.pack([m.effective_weight().float() for m in sl], [m.bias.float() for m in sl],
-                                     [m.effective_weight().float() for m in cl], [m.bias.float() for m in cl], want_flat=True)
+        flat = eng.flat_weights([m.effective_weight().float() for m in sl], [m.bias.float() for m in sl],
+                                [m.effective_weight().float() for m in cl], [m.bias.float() for m in cl])
         T = eng.alloc_tensors(P, dev)
         T['X'].copy_(x)
         T['DIRS'].copy_(d)
@@ -975,7 +977,7 @@ def test_training_forward_outputs_are_the_render_kernels(mode):
         if mode == 'x3':
             eng.run_fused_forward_x3(W, b, Wc, bc, T, P)
         else:
-            eng.run_fused_forward(eng.pack(W, b, Wc, bc, want_flat=True)[2], T, P)
+            eng.run_fused_forward(eng.flat_weights(W, b, Wc, bc), T, P)
         m = 'x3' if mode == 'x3' else 'f32'
         wb_s, d_s = sdf.packs(max_tiles=col.max_tiles(), mode=m)
         wb_c, d_c = col.packs(feat_tiles=sdf.plan(mode=m).tiles[-1], mode=m)

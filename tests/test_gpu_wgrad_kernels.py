@@ -1,5 +1,6 @@
 """The weight-gradient kernels on their own, window by window: vqn_wgrad_partials / _x3 / _batched, vqn_wgrad_thin_batched,
-vqn_reduce_partials, vqn_wgrad_finalize and the planner geo/train_programs.WgradBatch that cuts a weight into their windows.
+vqn_reduce_partials, vqn_wgrad_finalize and the planners of vqnerf_release_amd/wgrad.py (WgradBatch, WgradPerWeight) that cut a
+weight into their windows.
 
 Three kinds of comparison (cases, operands and references: tests/wgrad_cases.py, checked on the CPU by tests/test_wgrad_cases.py):
   * exact -- integer operands in [-8, 8] (one bf16 piece each): every partial sum is an integer below 2^24, so any summation order
@@ -356,10 +357,13 @@ class _Dst:
         self.b = torch.full((rows + 13,), NAN, device='cuda')
         self.bias = self.b[3:]
 
-    def check(self, want, want_bias, col_first=0, tag=''):
-        """want [rows, cols] float64 integers; columns below col_first and everything around the window must still be NaN"""
+    def check(self, want, want_bias, col_first=0, tag='', scale=1.0):
+        """want [rows, cols] float64 integers (times the float32 `scale`, one rounding); columns below col_first and everything
+        around the window must still be NaN"""
         exp = torch.full_like(self.m, NAN)
         w = wc.exact32(want).cuda()
+        if scale != 1.0:
+            w = w * torch.tensor(scale, dtype=torch.float32, device='cuda')
         if self.transposed:
             exp[self.c0 + col_first:self.c0 + self.cols, self.r0:self.r0 + self.rows] = w[:, col_first:].T
         else:
@@ -373,7 +377,7 @@ class _Dst:
 
 def _plan_case(which, npt):
     from vqnerf_release_amd.decomp.train_programs import to_tfmt
-    from vqnerf_release_amd.geo.train_programs import WgradBatch
+    from vqnerf_release_amd.wgrad import WgradBatch
     N = 32 * npt - 5                                             # the last point tile is zero padded
     T = lambda rows, tiles=None: to_tfmt(rows.cuda(), tiles)
     P = lambda a, b: a.double().T @ b.double()                   # the product of the rows: integers, exact in float64
@@ -452,7 +456,7 @@ PLAN_CASES = ('transposed_257x295', 'two_terms_scaled_col_first', 'col_first_ski
 def test_wgradbatch_plan_is_the_matrix_product(which, mode):
     """WgradBatch's windows (8-tile blocking, col_first clipped per block, the thin path's negative pointer offsets) against the
     integer product of the rows the operands were packed from; 3 point tiles, n_split = 64."""
-    from vqnerf_release_amd.geo import train_programs as tp
+    from vqnerf_release_amd import wgrad as tp
     old = tp.wgrad_mode()
     try:
         tp.wgrad_mode(mode)
@@ -466,10 +470,60 @@ def test_wgradbatch_plan_is_the_matrix_product(which, mode):
 def test_wgradbatch_plan_at_1025_point_tiles():
     """The 257 x 295 weight again at 1025 point tiles under 'bf16x3': its 8 + 1 by 8 + 2 tile blocks run the full, the guarded and
     (the 1-tile row block) the narrow exact-split kernel."""
-    from vqnerf_release_amd.geo import train_programs as tp
+    from vqnerf_release_amd import wgrad as tp
     old = tp.wgrad_mode()
     try:
         tp.wgrad_mode('bf16x3')
         _plan_case('transposed_257x295', 1025)
     finally:
         tp.wgrad_mode(old)
+
+
+# ----------------------------------------------------------------------------------------------------------- the two executors
+def _run_executor(make, npt):
+    """One contraction list through the executor make() returns; every destination checked against the integer product of the rows
+    (and NaN around it) -> (launches record, destinations).  257 result rows = an 8-tile row window and one of a single valid row;
+    295 / 39 columns = two / one column windows."""
+    from vqnerf_release_amd.decomp.train_programs import to_tfmt
+    N = 32 * npt - 5                                             # the last point tile is zero padded
+    P = lambda a, b: a.double().T @ b.double()
+    a, a2 = _int_rows(N, 257, 21), _int_rows(N, 257, 22)
+    b295, b39, b39_2 = _int_rows(N, 295, 23), _int_rows(N, 39, 24), _int_rows(N, 39, 25)
+    wc.assert_headroom(a, a2, b295, b39, b39_2, n_points=2 * N, what='executors')
+    A, A2, B295, B39, B39_2 = [to_tfmt(t.cuda()) for t in (a, a2, b295, b39, b39_2)]
+    s2 = float(np.float32(1.0 / math.sqrt(2.0)))
+    dt = _Dst(257, 295, True, (2, 4))                            # transposed (the Keras layout), with its bias
+    ds = _Dst(257, 39, False, (1, 5))                            # two terms, scaled, into a column slice of a wider matrix
+    dc = _Dst(257, 39, False, (3, 2))                            # without its first column
+    with launches() as rec:
+        ex = make()
+        ex.contract(A, B295, 257, 295, dt.dst, dt.sr, dt.sc, bias_dst=dt.bias)
+        ex.contract(A, B39, 257, 39, ds.dst, ds.sr, ds.sc, A2=A2, B2=B39_2, scale=s2)
+        ex.contract(A2, B39, 257, 39, dc.dst, dc.sr, dc.sc, bias_dst=dc.bias, col_first=1)
+        ex.flush()
+    dt.check(P(a, b295), a.double().sum(0), tag='transposed')
+    ds.check(P(a, b39) + P(a2, b39_2), None, scale=s2, tag='two terms, scaled')
+    dc.check(P(a2, b39), a2.double().sum(0), col_first=1, tag='col_first')
+    return rec, (dt, ds, dc)
+
+
+@pytest.mark.parametrize('mode', ['f32', 'bf16x3'])
+def test_both_executors_write_the_same_bits_and_nothing_else(mode):
+    """WgradBatch and WgradPerWeight given the same contractions (3 point tiles in 2 uneven blocks): every destination and bias equal
+    bit for bit, NaN everywhere else; one vqn_wgrad_finalize for the batch, one vqn_wgrad_partials + vqn_reduce_partials per window and
+    operand pair (4 + 2 * 2 + 2) for the per-weight form."""
+    from vqnerf_release_amd import wgrad
+    old = wgrad.wgrad_mode()
+    try:
+        wgrad.wgrad_mode(mode)
+        rec_b, dst_b = _run_executor(lambda: wgrad.WgradBatch(2), 3)
+        rec_p, dst_p = _run_executor(lambda: wgrad.WgradPerWeight(2), 3)
+    finally:
+        wgrad.wgrad_mode(old)
+    entry = wgrad.WGRAD_ENTRY[mode]
+    partial_entries = lambda rec: set(n for n in rec.names if n.startswith('vqn_wgrad_partials'))
+    assert rec_b.counts.get('vqn_wgrad_finalize') == 1 and not rec_b.ran('vqn_reduce_partials') and partial_entries(rec_b) == {entry}, rec_b.counts
+    assert rec_p.counts.get('vqn_reduce_partials') == 10 and rec_p.counts.get(entry) == 10 and partial_entries(rec_p) == {entry} \
+        and not rec_p.ran('vqn_wgrad_finalize'), rec_p.counts
+    for x, y in zip(dst_b, dst_p):
+        assert torch.equal(_bits(x.m), _bits(y.m)) and torch.equal(_bits(x.b), _bits(y.b))

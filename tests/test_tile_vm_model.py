@@ -166,7 +166,7 @@ def test_the_model_refuses_what_the_entry_point_must_refuse():
 
 def test_every_case_translates_into_a_program_of_the_shipped_builder():
     """the translator emits Program calls; the descriptor it yields has the op kinds, the wave count and the row budget of the case"""
-    from vqnerf_release_amd.geo import train_programs as tp
+    from vqnerf_release_amd import tile_program as tp
     kinds = dict(posenc=tp.K_LD_POSENC, posenc_jvp=tp.K_LD_POSENC_JVP, ld_t=tp.K_LD_T, ld_vec=tp.K_LD_VEC, extras=tp.K_LD_EXTRAS,
                  gemm=tp.K_GEMM, st_vec=tp.K_ST_VEC, posenc_vjp=tp.K_POSENC_VJP)
     seen = set()

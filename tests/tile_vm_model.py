@@ -1,5 +1,5 @@
 """A plain numpy statement of every op of include/vqn_vm_desc.h (the tile-program interpreter, csrc/tile_vm.hip), the cases of
-tests/test_gpu_tile_vm_ops.py, and the translator that turns a case into geo/train_programs.Program calls.  Nothing here touches a
+tests/test_gpu_tile_vm_ops.py, and the translator that turns a case into tile_program.Program calls.  Nothing here touches a
 GPU; tests/test_tile_vm_model.py checks the model against torch float64 autograd, so that it is a reference of its own and not a
 transcription of the kernel.
 
@@ -277,7 +277,7 @@ def build_program(case, per_workgroup=()):
     """case -> dict(prog, desc [int32], gidx, flat [float32: the weight buffer is flat[gidx]], names, ld): the Program calls the
     shipped engines make (alloc, gemm, op, finalize, materialize, build_static_packs with a FlatLayout).  per_workgroup: tensors
     handed over with a negative ld."""
-    from vqnerf_release_amd.geo import train_programs as tp
+    from vqnerf_release_amd import tile_program as tp
     from vqnerf_release_amd.geo.packing import FlatLayout
     names = list(case['tensors'])
     Pg = tp.Program(names)

@@ -456,7 +456,7 @@ class BrdfModel(ShapeModel):
         return self.train_backend == 'hip' and x.is_cuda and getattr(self.embedder['xyz'], 'fused_ok', lambda: False)()
 
     # 'x3': the dedicated exact-split kernels of csrc/refl_train_x3.hip (decomp/refl_train.py) wherever the stack has their shape;
-    # 'prog': the interpreted tile programs of rounds 1-3 (decomp/train_programs.py).  VQN_REFL_TRAIN overrides.
+    # 'prog': the interpreted tile programs of rounds 1-3 (decomp/train_programs.py on tile_program.py, contractions: wgrad.py).  VQN_REFL_TRAIN overrides.
     REFL_TRAIN_DEFAULT = 'x3'
 
     def _stack_engine(self, names, x, with_encoder):

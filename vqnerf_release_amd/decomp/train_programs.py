@@ -10,8 +10,9 @@ import torch
 
 from vqnerf_release_amd import _C
 from vqnerf_release_amd.geo.packing import FlatLayout
-from vqnerf_release_amd.geo.train_programs import (Program, _f2i, DESC_INTS, K_LD_POSENC, K_LD_T, EPI_ACT, EPI_MUL_DACT, ACT_NONE, ACT_RELU,
-                                                   ACT_SIGMOID, build_static_packs, wgrad_mode, WgradBatch, BATCHED_WGRAD)
+from vqnerf_release_amd.tile_program import (Program, _f2i, K_LD_POSENC, K_LD_T, EPI_MUL_DACT, ACT_NONE, ACT_RELU, ACT_SIGMOID,
+                                             build_static_packs)
+from vqnerf_release_amd.wgrad import wgrad_executor
 
 ACTS = {None: ACT_NONE, 'relu': ACT_RELU, 'sigmoid': ACT_SIGMOID}
 
@@ -54,7 +55,7 @@ def from_tfmt(t, N, F):
 
 
 class _Engine:
-    """shared: program packing / launching / weight-gradient contraction"""
+    """shared: program packing / launching"""
     n_split = 256        # upper bound on the split-over-points workgroups of a weight-gradient call (one per CU); a call uses
                          # min(n_split, point tiles), so the reference batch (2048 points = 64 tiles) still runs 64 of them
 
@@ -85,20 +86,6 @@ class _Engine:
         d_host, d_dev = descs[which]
         names = list(prog.tn.keys())
         _C.tile_program(type(self).__name__ + '.' + which, d_dev, d_host, wbuf, [tensors.get(n) for n in names], [specs[n][1] for n in names], N)
-
-    def wgrad(self, A, B, a_rows, b_cols, ws, rowsum=False):
-        """sum_p A[o][p] B[i][p] -> [a_rows, b_cols]; rowsum=True: also sum_p A[o][p] (bias gradient) from the same pass."""
-        nt, at, bt = A.shape[0], A.shape[1], B.shape[1]
-        an, bn = (a_rows + 31) // 32, (b_cols + 31) // 32
-        assert an <= 8 and bn <= 8
-        if rowsum and (getattr(self, '_rs_ws', None) is None or self._rs_ws.device != A.device):
-            self._rs_ws = torch.empty(self.n_split * 256, dtype=torch.float32, device=A.device)
-        n = _C.wgrad_partials(A, at, 0, an, B, bt, 0, bn, nt, self.n_split, ws, self._rs_ws if rowsum else None, x3=wgrad_mode() == 'bf16x3')
-        out = torch.empty((an * 32, bn * 32), dtype=torch.float32, device=A.device)
-        rs = torch.empty((an * 32,), dtype=torch.float32, device=A.device) if rowsum else None
-        # ordered sum of the split-over-points partial blocks
-        _C.reduce_partials(ws, n, an * 32, bn * 32, out, bn * 32, rowsum=(self._rs_ws, rs, an * 32) if rowsum else None)
-        return (out[:a_rows, :b_cols], rs[:a_rows]) if rowsum else out[:a_rows, :b_cols]
 
     @staticmethod
     def alloc(specs, N, device, only=None):
@@ -200,30 +187,21 @@ class EncoderEngine(_Engine):
         pack_delta(g_z, T['Y%d' % top], self.layers[top]['act'], N, self.layers[top]['out'], T['GZ'])
         T['D%d' % top] = T['GZ']
         self.run('prog_bwd', descs, wbuf, T, self.specs, N)
-        if not BATCHED_WGRAD[0]:
-            ws = torch.empty(min(self.n_split, (N + 31) // 32) * 256 * 256, dtype=torch.float32, device=g_z.device)
         dW, db, dev = [], [], g_z.device
-        batch = WgradBatch(self.n_split)
+        ex = wgrad_executor(self.n_split)
         for k, L in enumerate(self.layers):
             D = T['D%d' % k]
             src = T['E'] if k == 0 else T['Y%d' % (k - 1)]
-            if BATCHED_WGRAD[0]:
-                # straight into the Keras layout [in, out] (element (o, i) at i * out + o), the skip input's rows after the y-part's
-                n_in, n_out = L['in_y'] + (self.E if L['skip'] else 0), L['out']
-                G = torch.empty((n_in, n_out), dtype=torch.float32, device=dev)
-                bsum = torch.empty((n_out,), dtype=torch.float32, device=dev)
-                batch.contract(D, src, n_out, L['in_y'], G, 1, n_out, bias_dst=bsum)
-                if L['skip']:
-                    batch.contract(D, T['E'], n_out, self.E, G[L['in_y']:], 1, n_out)
-                dW.append(G)
-                db.append(bsum)
-                continue
-            g, bsum = self.wgrad(D, src, L['out'], L['in_y'], ws, rowsum=True)
+            # straight into the Keras layout [in, out] (element (o, i) at i * out + o), the skip input's rows after the y-part's
+            n_in, n_out = L['in_y'] + (self.E if L['skip'] else 0), L['out']
+            G = torch.empty((n_in, n_out), dtype=torch.float32, device=dev)
+            bsum = torch.empty((n_out,), dtype=torch.float32, device=dev)
+            ex.contract(D, src, n_out, L['in_y'], G, 1, n_out, bias_dst=bsum)
             if L['skip']:
-                g = torch.cat([g, self.wgrad(D, T['E'], L['out'], self.E, ws)], 1)
-            dW.append(g.t().contiguous())                              # Keras layout [in, out]
+                ex.contract(D, T['E'], n_out, self.E, G[L['in_y']:], 1, n_out)
+            dW.append(G)
             db.append(bsum)
-        batch.flush()
+        ex.flush()
         return dW, db
 
 
@@ -336,31 +314,20 @@ class HeadsEngine(_Engine):
         for h, (net, g) in enumerate(zip(self.nets, g_outs)):
             pack_delta(g, T['Y%d_2' % h], ACT_SIGMOID, N, net.widths[2], T['D%d_2' % h])
         self.run('prog_bwd', descs, wbuf, T, self.specs, N)
-        if not BATCHED_WGRAD[0]:
-            ws = torch.empty(min(self.n_split, (N + 31) // 32) * 256 * 256, dtype=torch.float32, device=T['Z'].device)
         dW, db, dev = [], [], T['Z'].device
-        batch = WgradBatch(self.n_split)
-        for h, net in enumerate(self.nets):
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ex = wgrad_executor(self.n_split)
+        for h, net in enumerate(self.nets):           # Keras layout [in, out]; the last layer's input is [y1 ; z]
             w0, w1, c = net.widths
             D0, D1, D2 = T['D%d_0' % h], T['D%d_1' % h], T['D%d_2' % h]
-            if BATCHED_WGRAD[0]:
-                new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-                g0, g1, g2, b0, b1, b2 = new(self.Z, w0), new(w0, w1), new(w1 + self.Z, c), new(w0), new(w1), new(c)
-                batch.contract(D0, T['Z'], w0, self.Z, g0, 1, w0, bias_dst=b0)
-                batch.contract(D1, T['Y%d_0' % h], w1, w0, g1, 1, w1, bias_dst=b1)
-                batch.contract(D2, T['Y%d_1' % h], c, w1, g2, 1, c, bias_dst=b2)
-                batch.contract(D2, T['Z'], c, self.Z, g2[w1:], 1, c)
-                dW += [g0, g1, g2]
-                db += [b0, b1, b2]
-                continue
-            g0, b0 = self.wgrad(D0, T['Z'], w0, self.Z, ws, rowsum=True)
-            g1, b1 = self.wgrad(D1, T['Y%d_0' % h], w1, w0, ws, rowsum=True)
-            g2a, b2 = self.wgrad(D2, T['Y%d_1' % h], c, w1, ws, rowsum=True)
-            g0, g1 = g0.t().contiguous(), g1.t().contiguous()
-            g2 = torch.cat([g2a, self.wgrad(D2, T['Z'], c, self.Z, ws)], 1).t().contiguous()
+            g0, g1, g2, b0, b1, b2 = new(self.Z, w0), new(w0, w1), new(w1 + self.Z, c), new(w0), new(w1), new(c)
+            ex.contract(D0, T['Z'], w0, self.Z, g0, 1, w0, bias_dst=b0)
+            ex.contract(D1, T['Y%d_0' % h], w1, w0, g1, 1, w1, bias_dst=b1)
+            ex.contract(D2, T['Y%d_1' % h], c, w1, g2, 1, c, bias_dst=b2)
+            ex.contract(D2, T['Z'], c, self.Z, g2[w1:], 1, c)
             dW += [g0, g1, g2]
             db += [b0, b1, b2]
-        batch.flush()
+        ex.flush()
         return from_tfmt(T['GZ'], N, self.Z), dW, db
 
 

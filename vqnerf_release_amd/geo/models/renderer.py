@@ -7,7 +7,8 @@ Render / inference (no graph needed) is HIP end to end:
     vqn_neus_merge       -> cat_z_vals (:177-191)
     vqn_neus_section_mids, vqn_neus_fine_points, vqn_neus_composite_fwd -> render_core (:193-297)
 Training (a graph is needed, incl. the second-order eikonal term) keeps the no_grad up-sampling on those kernels and runs
-render_core as explicit forward / backward tile programs (`vqn_tile_program`, `vqn_wgrad_partials`, geo/train_programs.py)
+render_core as explicit forward / backward passes (`vqn_neus_train_fwd/_bwd`, `vqn_tile_program`, `vqn_wgrad_partials`: geo/train_programs.py,
+the program builder tile_program.py, the contractions wgrad.py)
 plus `vqn_neus_composite_fwd/_bwd` under two `torch.autograd.Function`s.  Networks whose shape the tile programs do not cover
 take the torch-autograd statement of render_core instead -- loudly: a RuntimeWarning names the reason and
 `renderer.last_train_backend` records which path the last graph-building render_core took ('hip' | 'torch').
