@@ -1,6 +1,7 @@
 """Dev probe: time of vqn_brdf_shade_fwd on a 640,000-point view (two material sets + split; one set + 16 probes; no visibility
-rows + gamma) -- HIP events around each launch."""
-import os, sys
+rows + gamma) -- HIP events around each launch.
+`probe_shade.py N --host`: wall time per call of the forward and the backward at N points (1: the host side dominates)."""
+import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from vqnerf_release_amd import _C
@@ -31,6 +32,20 @@ def t(fn, n=5):
     return e0.elapsed_time(e1) / n
 
 
+if '--host' in sys.argv:
+    def t_host(fn, n=300):
+        """wall time per call, microseconds: n calls back to back, one synchronisation at the end"""
+        for _ in range(10): fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n): fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e6
+    gs = [R(N, 3) for _ in range(2)]
+    print(f'host N={N} fwd 2 sets: %.2f us/call' % t_host(lambda: _C.brdf_shade_fwd(xyz, nrm, rayo, lvis, lxyz, lareas, light, mats, raw=True)))
+    print(f'host N={N} fwd 1 set + 16 probes: %.2f us/call' % t_host(lambda: _C.brdf_shade_fwd(xyz, nrm, rayo, lvis, lxyz, lareas, light, mats[:1], probes=probes)))
+    print(f'host N={N} bwd 2 sets: %.2f us/call' % t_host(lambda: _C.brdf_shade_bwd(xyz, nrm, rayo, lvis, lxyz, lareas, light, mats, gs)))
+    sys.exit(0)
 print(f'N={N}')
 print('2 sets + split, lvis      : %.3f ms' % t(lambda: _C.brdf_shade_fwd(xyz, nrm, rayo, lvis, lxyz, lareas, light, mats, want_split=True)))
 print('2 sets, lvis (train fwd)  : %.3f ms' % t(lambda: _C.brdf_shade_fwd(xyz, nrm, rayo, lvis, lxyz, lareas, light, mats, raw=True)))

@@ -22,11 +22,13 @@ def _data(N, D, K, seed):
 
 
 @pytest.mark.parametrize('N,D,K', [(1000, 256, 15), (4099, 256, 16), (777, 256, 8), (3000, 256, 64),
-                                   (513, 64, 16), (100, 20, 7), (1, 256, 15), (17, 256, 128)])
+                                   (513, 64, 16), (100, 20, 7), (1, 256, 15), (17, 256, 128), (17, 256, 64)])
 def test_assign_bit_exact_vs_strict_oracle(N, D, K):
+    """(17, 256, 64): 66320 B of LDS, the smallest shape whose launch raises the kernel's dynamic-LDS limit; (17, 256, 128): 8 code tiles"""
     from oracle import vq_strict as vs
     from vqnerf_release_amd import _C
     x, C = _data(N, D, K, seed=N + K)
+    assert _C.vq_assign_variant(D, K, has_dist=True) == 0            # a distance output: the f32 kernel
     idx, quant, dist = _C.vq_assign(torch.tensor(x).cuda(), torch.tensor(C).cuda(), want_quant=True, want_dist=True)
     ridx, rdist, rquant = vs.assign(x, C)
     np.testing.assert_array_equal(dist.cpu().numpy(), rdist)
@@ -66,7 +68,8 @@ def _adversarial(N, D, K, kind, seed):
 
 
 @pytest.mark.parametrize('kind', ['plain', 'duplicates', 'clusters', 'midpoints', 'scaled', 'tiny', 'huge', 'zeros', 'signed'])
-@pytest.mark.parametrize('N,D,K', [(3000, 256, 64), (1000, 256, 33), (1000, 256, 17), (2049, 64, 32), (500, 20, 40), (333, 252, 64)])
+@pytest.mark.parametrize('N,D,K', [(3000, 256, 64), (1000, 256, 33), (1000, 256, 17), (2049, 64, 32), (500, 20, 40), (333, 252, 64),
+                                   (17, 64, 17), (17, 256, 33)])            # (the last two: one workgroup, 2 and 4 code tiles)
 def test_prefiltered_assign_is_bit_exact_vs_strict_oracle(N, D, K, kind):
     """K in 17..64 without a distance output runs vq_assign_split_kernel (f16-pair prefilter + exact evaluation of the candidates):
     the indices and the gathered rows must be those of the defined arithmetic, including exact ties (lowest index)."""
@@ -128,11 +131,29 @@ def test_assign_ties_and_dropout_mask():
         np.testing.assert_array_equal(quant.cpu().numpy(), rquant)
 
 
-@pytest.mark.parametrize('N,D,K', [(5000, 256, 15), (2048, 256, 64), (33, 64, 5), (0, 256, 15), (4099, 128, 20), (1, 256, 15),
-                                   (777, 32, 5), (3000, 320, 9)])
+_EMA_FORMS = {
+    (5000, 256, 15): 'mfma', (2048, 256, 64): 'mfma', (33, 64, 5): 'mfma', (0, 256, 15): 'atomic', (4099, 128, 20): 'mfma',
+    (1, 256, 15): 'mfma', (777, 32, 5): 'two-pass', (3000, 320, 9): 'two-pass',
+    (1, 64, 5): 'mfma', (17, 64, 20): 'mfma', (4099, 64, 40): 'mfma',         # the matrix pipe at 1, 2 and 4 code tiles
+    (1, 20, 40): 'two-pass', (500, 20, 40): 'two-pass', (333, 252, 64): 'atomic'}
+
+
+@pytest.mark.parametrize('N,D,K', list(_EMA_FORMS))
 def test_ema_stats(N, D, K):
+    """every form the statistics take, chosen as _C.vq_ema_stats chooses it: by the workspace the query asks for"""
     from oracle import vq_strict as vs
     from vqnerf_release_amd import _C
+    need, form = _C.lib().vqn_vq_ema_stats_ws_bytes(N, D, K), _EMA_FORMS[(N, D, K)]
+    KP = 16 if K <= 16 else 32 if K <= 32 else 64
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if form == 'mfma':                                               # per-workgroup partials [KP, D] + [KP]; one 4-row step per wave
+        wgs = max(1, min(((N + 3) // 4 + 3) // 4, cus * (1 if KP == 64 else 2)))
+        assert D % 64 == 0 and D <= 256 and K <= 64 and need == wgs * 4 * (KP * D + KP)
+    elif form == 'two-pass':                                         # per-wave partials [K, D] + [K], four waves, 64 rows a workgroup
+        wgs = max(1, min((N + 63) // 64, cus * 2))
+        assert not (D % 64 == 0 and D <= 256) and need == wgs * 16 * (K * D + K)
+    else:
+        assert need == 0
     x, C = _data(max(N, 1), D, K, seed=3)
     x = x[:N]
     rng = np.random.default_rng(1)
@@ -250,7 +271,7 @@ def test_ste_and_commitment_pass(N, D):
 def test_counts_only_path():
     from vqnerf_release_amd import _C
     rng = np.random.default_rng(0)
-    for N, K in ((100003, 15), (5, 64), (0, 8)):
+    for N, K in ((100003, 15), (5, 64), (0, 8), (1, 8)):
         idx = rng.integers(-1, K + 2, N)                              # includes out-of-range codes: ignored
         got = _C.vq_counts(torch.tensor(idx, dtype=torch.int64).cuda(), K).cpu().numpy()
         want = np.array([(idx == k).sum() for k in range(K)], np.float32)

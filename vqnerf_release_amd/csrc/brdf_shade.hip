@@ -11,6 +11,7 @@
 // Bound: HBM for data_type == 'nerf' (2 KB of lvis per point) -- VALU otherwise; see DESIGN.md.
 #include "common.h"
 #include "wave.h"
+#include "launch.h"
 #include <stdlib.h>
 #include "vqnerf_hip.h"
 #include <math.h>
@@ -534,48 +535,26 @@ extern "C" int vqn_brdf_shade_fwd_rows(const int64_t* lvis_rows, const float* xy
   VQN_CHECK_ARG(probes == nullptr || (n_probes >= 1 && rgb0_probes != nullptr), "probes need n_probes >= 1 and rgb0_probes");
   VQN_CHECK_SHAPE(probes == nullptr || ((uintptr_t)probes & 15) == 0, "probes must be 16-byte aligned");
   a.probes = probes; a.n_probes = probes ? n_probes : 0; a.rgb_probes = rgb0_probes;
-  long blocks = (N + 3) / 4;
-  const long cap = (long)vqn_num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  hipStream_t s = (hipStream_t)stream;
   const bool pr = a.probes != nullptr;
   // relighting with the probe table in LDS: one 768-thread workgroup per CU (three waves per SIMD at 168 registers)
   const size_t plds = pr ? (size_t)n_probes * (L / 256) * 3 * 1024 : 0;
   static const int no_plds = [] { const char* e = getenv("VQN_SHADE_NO_PLDS"); return (e != nullptr && atoi(e) != 0) ? 1 : 0; }();
   const bool use_plds = pr && plds <= 144 * 1024 && !no_plds && !(L == 1024 && n_sets == 2);      // (that one form would spill)
   const int plds_waves = L == 1024 ? 8 : 12;
-  long blocks8 = (N + plds_waves - 1) / plds_waves;
-  if (blocks8 > (long)vqn_num_cus()) blocks8 = vqn_num_cus();
-#define VQN_SHADE_PLDS(LQ, NS_)                                                                                                    \
-  do {                                                                                                                             \
-    VQN_HIP(hipFuncSetAttribute((const void*)brdf_shade_kernel<LQ, true, NS_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds)); \
-    hipLaunchKernelGGL((brdf_shade_kernel<LQ, true, NS_, true>), dim3((unsigned)blocks8), dim3(64 * plds_waves), plds, s, a);                    \
-  } while (0)
-#define VQN_SHADE_LAUNCH(LQ)                                                                                   \
-  do {                                                                                                         \
-    if (use_plds && n_sets == 1) VQN_SHADE_PLDS(LQ, 1);                                                        \
-    else if (use_plds) VQN_SHADE_PLDS(LQ, 2);                                                                  \
-    else if (pr && n_sets == 1) hipLaunchKernelGGL((brdf_shade_kernel<LQ, true, 1>), dim3((unsigned)blocks), dim3(256), 0, s, a);   \
-    else if (pr) hipLaunchKernelGGL((brdf_shade_kernel<LQ, true, 2>), dim3((unsigned)blocks), dim3(256), 0, s, a);                  \
-    else if (n_sets == 1) hipLaunchKernelGGL((brdf_shade_kernel<LQ, false, 1>), dim3((unsigned)blocks), dim3(256), 0, s, a);        \
-    else hipLaunchKernelGGL((brdf_shade_kernel<LQ, false, 2>), dim3((unsigned)blocks), dim3(256), 0, s, a);                         \
-  } while (0)
-  if (L == 256) VQN_SHADE_LAUNCH(1);
-  else if (L == 512) VQN_SHADE_LAUNCH(2);
-  else VQN_SHADE_LAUNCH(4);
-#undef VQN_SHADE_LAUNCH
-#undef VQN_SHADE_PLDS
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  const dim3 grid((unsigned)vqn_grid((N + 3) / 4, 8)), grid_plds((unsigned)vqn_grid((N + plds_waves - 1) / plds_waves, 1));
+  const char* fn = __func__;
+  return vqn_pick<1, 2, 4>(fn, L / 256, [&](auto lq) {
+    constexpr int LQ = decltype(lq)::value;
+    if (use_plds)
+      return vqn_pick<1, 2>(fn, n_sets, [&](auto ns) {
+        return vqn_launch(fn, brdf_shade_kernel<LQ, true, decltype(ns)::value, true>, grid_plds, 64 * plds_waves, plds, stream, a);
+      });
+    if (pr) return vqn_pick<1, 2>(fn, n_sets, [&](auto ns) { return vqn_launch(fn, brdf_shade_kernel<LQ, true, decltype(ns)::value>, grid, 256, 0, stream, a); });
+    return vqn_pick<1, 2>(fn, n_sets, [&](auto ns) { return vqn_launch(fn, brdf_shade_kernel<LQ, false, decltype(ns)::value>, grid, 256, 0, stream, a); });
+  });
 }
 
-extern "C" int64_t vqn_brdf_shade_bwd_partials(int64_t N) {
-  long blocks = (N + 3) / 4;
-  const long cap = (long)vqn_num_cus() * 4;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return blocks * 4;
-}
+extern "C" int64_t vqn_brdf_shade_bwd_partials(int64_t N) { return vqn_grid1((N + 3) / 4, 4) * 4; }
 
 extern "C" int vqn_brdf_shade_bwd(const float* xyz, const float* normal, const float* rayo, const float* lvis,
                                   const float* lxyz, const float* lareas, const float* light, int64_t N, int L,
@@ -606,13 +585,9 @@ extern "C" int vqn_brdf_shade_bwd(const float* xyz, const float* normal, const f
   a.g_albedo[0] = g_albedo0; a.g_spec[0] = g_spec0; a.g_rough[0] = g_rough0;
   a.g_albedo[1] = g_albedo1; a.g_spec[1] = g_spec1; a.g_rough[1] = g_rough1;
   a.g_light_part = g_light_partials; a.N = N; a.n_sets = n_sets;
-  const long blocks = vqn_brdf_shade_bwd_partials(N) / 4;
-  hipStream_t s = (hipStream_t)stream;
-  if (L == 256) hipLaunchKernelGGL(brdf_shade_bwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  else if (L == 512) hipLaunchKernelGGL(brdf_shade_bwd_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(brdf_shade_bwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  const dim3 grid((unsigned)(vqn_brdf_shade_bwd_partials(N) / 4));
+  const char* fn = __func__;
+  return vqn_pick<1, 2, 4>(fn, L / 256, [&](auto lq) { return vqn_launch(fn, brdf_shade_bwd_kernel<decltype(lq)::value>, grid, 256, 0, stream, a); });
 }
 
 // ---- display transfer of the rendered colours (nerfactor/util/img.py:142-186: clip to [0, 1], then the piecewise sRGB curve) as one
@@ -632,10 +607,5 @@ extern "C" int vqn_linear2srgb(const float* x, int64_t n, float* y, void* stream
   VQN_CHECK_ARG(n >= 0, "n >= 0");
   if (n == 0) return VQN_OK;
   VQN_CHECK_ARG(x && y, "x and y must be non-null");
-  long blocks = (n + 255) / 256;
-  const long cap = (long)vqn_num_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(linear2srgb_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)n, y);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, linear2srgb_kernel, dim3((unsigned)vqn_grid((n + 255) / 256, 16)), 256, 0, stream, x, (long)n, y);
 }

@@ -70,8 +70,9 @@ static inline int chain_check_desc(const ChainDesc& d, const ChainEngineRules& r
 
 #ifdef __HIPCC__
 #include "common.h"
+#include "launch.h"
 
-// The checks report under the entry point's own name (`fn`); a HIP error names this header as its location, as with neus_launch.h.
+// The checks report under the entry point's own name (`fn`); a HIP error names launch.h as its location.
 
 // every output a program writes: a pointer (`null_msg` if not: the entry points word it differently), room for the layer's width,
 // 16-byte alignment where the kernel stores float4s.  `allow_null_slot0` (program A of the fused front): z may stay on the chip
@@ -110,21 +111,9 @@ static int chain_fwd_args(const char* fn, const ChainEngineRules& rules, const i
   return VQN_OK;
 }
 
-// workgroups of a persistent launch over `n_tiles` point tiles: two 4-wave workgroups per CU where the LDS holds two, else one
-static long chain_grid(const int n_waves, const size_t lds, const long n_tiles) {
-  const int per_cu = (n_waves == 4 && 2 * lds <= 160 * 1024) ? 2 : 1;
-  const long grid = (long)vqn_num_cus() * per_cu;
-  return grid > n_tiles ? n_tiles : grid;
-}
-
-// launch an NW-wave kernel over the N points with `lds` bytes of dynamic LDS (beyond the 64 KiB a kernel gets unasked: raise its limit first)
+// launch an NW-wave kernel over the N points with `lds` bytes of dynamic LDS
 template <int NW, class Kernel, class... Args>
 static int chain_launch(const char* fn, const Kernel kernel, const size_t lds, const int64_t N, void* stream, const Args... args) {
-  if (lds > 64 * 1024)
-    VQN_HIP_IN(fn, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long grid = chain_grid(NW, lds, (N + 31) / 32);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NW * 64), lds, (hipStream_t)stream, args...);
-  VQN_HIP_IN(fn, hipGetLastError());
-  return VQN_OK;
+  return vqn_launch(fn, kernel, vqn_tile_grid(NW, lds, (N + 31) / 32), NW * 64, lds, stream, args...);
 }
 #endif

@@ -13,6 +13,7 @@
 // One wave per PAIR of points: lanes 0 / 1 do the per-point scalar arithmetic, all 64 lanes the D-long dot product of the pair.
 #include "common.h"
 #include "wave.h"
+#include "launch.h"
 
 namespace {
 
@@ -162,10 +163,7 @@ int check(const LossArgs& a) {
 }
 
 unsigned grid_for(long N) {
-  long blocks = ((N + 1) / 2 + 3) / 4;
-  const long cap = (long)vqn_num_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  return (unsigned)(blocks < 1 ? 1 : blocks);
+  return (unsigned)vqn_grid1(((N + 1) / 2 + 3) / 4, 16);
 }
 
 }  // namespace
@@ -176,9 +174,7 @@ extern "C" int vqn_decomp_loss_fwd(const float* rgb_pred, const float* vq_rgb, c
   const LossArgs a{rgb_pred, vq_rgb, rgb_gt, z, spec, rough, (long)N, D, nerf, w_rgb, w_chr, w_smooth, chr_alpha, chr_thres, w_lambert};
   VQN_CHECK_ARG(check(a) == 0 && (N == 0 || terms != nullptr), "null pointer or negative size");
   if (N == 0) return VQN_OK;
-  hipLaunchKernelGGL(decomp_loss_fwd_kernel, dim3(grid_for(N)), dim3(256), 0, (hipStream_t)stream, a, terms);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, decomp_loss_fwd_kernel, dim3(grid_for(N)), 256, 0, stream, a, terms);
 }
 
 extern "C" int vqn_decomp_loss_bwd(const float* rgb_pred, const float* vq_rgb, const float* rgb_gt, const float* z, const float* spec,
@@ -190,10 +186,8 @@ extern "C" int vqn_decomp_loss_bwd(const float* rgb_pred, const float* vq_rgb, c
   VQN_CHECK_ARG(g_z == nullptr || z != nullptr, "g_z without z");
   VQN_CHECK_ARG(g_spec == nullptr || spec != nullptr, "g_spec without spec");
   if (N == 0) return VQN_OK;
-  hipLaunchKernelGGL(decomp_loss_bwd_kernel, dim3(grid_for(N)), dim3(256), 0, (hipStream_t)stream, a, g_terms, g_rgb_pred, g_vq_rgb, g_z,
-                     g_spec);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, decomp_loss_bwd_kernel, dim3(grid_for(N)), 256, 0, stream, a, g_terms, g_rgb_pred, g_vq_rgb, g_z,
+                    g_spec);
 }
 
 // ---- the EMA codebook move of VectorQuantizerEMA in training (vq_layers.py:304-325 + Sonnet's ExponentialMovingAverage, twice) as ONE
@@ -255,10 +249,8 @@ extern "C" int vqn_vq_ema_update(const float* counts, const float* dw, const flo
   VQN_CHECK_ARG(counts && dw && codebook && hidden_cs && average_cs && counter_cs && hidden_dw && average_dw && counter_dw && update,
                 "null pointer");
   VQN_CHECK_SHAPE(D >= 1 && K >= 1 && K <= 1024, "1 <= K <= 1024");
-  hipLaunchKernelGGL(vq_ema_update_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, counts, dw, codebook, D, K, decay, eps, hidden_cs,
-                     average_cs, (long long*)counter_cs, hidden_dw, average_dw, (long long*)counter_dw, update);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, vq_ema_update_kernel, dim3(1), 256, 0, stream, counts, dw, codebook, D, K, decay, eps, hidden_cs,
+                    average_cs, (long long*)counter_cs, hidden_dw, average_dw, (long long*)counter_dw, update);
 }
 
 // ---- backward of the two row-wise steps around the quantiser (networks/vq_layers.py of the reference: the l2-normalised encoder output,
@@ -379,10 +371,8 @@ extern "C" int vqn_vq_train_bwd(const float* z, const float* xnorm, const float*
   if (N == 0) return VQN_OK;
   VQN_CHECK_ARG(z && xnorm && quant && g_loss && g_z, "null pointer");
   VQN_CHECK_SHAPE(D % 4 == 0 && D <= 1024, "D a multiple of 4, at most 1024");
-  hipLaunchKernelGGL(vq_train_bwd_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, z, xnorm, quant, g_ste, g_loss,
-                     (float)(2.0 / ((double)N * D)), loss_post, (long)N, D, eps, g_z);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, vq_train_bwd_kernel, dim3((unsigned)((N + 3) / 4)), 256, 0, stream, z, xnorm, quant, g_ste, g_loss,
+                    (float)(2.0 / ((double)N * D)), loss_post, (long)N, D, eps, g_z);
 }
 
 extern "C" int vqn_l2_normalize_rows_bwd(const float* x, const float* g, int64_t N, int D, float eps, float* gx, void* stream) {
@@ -390,9 +380,7 @@ extern "C" int vqn_l2_normalize_rows_bwd(const float* x, const float* g, int64_t
   if (N == 0) return VQN_OK;
   VQN_CHECK_ARG(x && g && gx, "null pointer");
   VQN_CHECK_SHAPE(D % 4 == 0 && D <= 1024, "D a multiple of 4, at most 1024");
-  hipLaunchKernelGGL(l2_normalize_rows_bwd_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, g, (long)N, D, eps, gx);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, l2_normalize_rows_bwd_kernel, dim3((unsigned)((N + 3) / 4)), 256, 0, stream, x, g, (long)N, D, eps, gx);
 }
 
 extern "C" int vqn_vq_ste_loss_bwd(const float* x, const float* quant, const float* g_ste, const float* g_loss, int64_t numel, float* gx,
@@ -404,11 +392,9 @@ extern "C" int vqn_vq_ste_loss_bwd(const float* x, const float* quant, const flo
   const long n4 = numel / 4;
   long blocks = (n4 + 255) / 256;
   if (blocks > 256L * 16) blocks = 256L * 16;
-  hipLaunchKernelGGL(ste_commit_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(x),
-                     reinterpret_cast<const f32x4*>(quant), reinterpret_cast<const f32x4*>(g_ste), g_loss, (float)(2.0 / (double)numel), n4,
-                     reinterpret_cast<f32x4*>(gx));
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, ste_commit_bwd_kernel, dim3((unsigned)blocks), 256, 0, stream, reinterpret_cast<const f32x4*>(x),
+                    reinterpret_cast<const f32x4*>(quant), reinterpret_cast<const f32x4*>(g_ste), g_loss, (float)(2.0 / (double)numel), n4,
+                    reinterpret_cast<f32x4*>(gx));
 }
 
 // ---- the codebook as the model uses it (vq_nfr.py: clip with identity gradient to [0, 1], l2-normalise every code) and the
@@ -550,9 +536,7 @@ extern "C" int vqn_codebook_prep(const float* raw, const float* g, int D, int K,
 extern "C" int vqn_sim_smooth_fwd(const float* codebook, int D, int K, float weight, float* out4, void* stream) {
   VQN_CHECK_ARG(codebook && out4, "null pointer");
   VQN_CHECK_SHAPE(D >= 1 && K >= 2 && K <= 256, "D >= 1, 2 <= K <= 256");
-  hipLaunchKernelGGL(sim_smooth_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, codebook, D, K, weight, out4);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, sim_smooth_fwd_kernel, dim3(1), 256, 0, stream, codebook, D, K, weight, out4);
 }
 
 extern "C" int vqn_sim_smooth_bwd(const float* codebook, const float* fwd4, const float* g_loss, int D, int K, float weight, float* g_codebook,
@@ -561,7 +545,5 @@ extern "C" int vqn_sim_smooth_bwd(const float* codebook, const float* fwd4, cons
   VQN_CHECK_SHAPE(D >= 1 && K >= 2 && K <= 256, "D >= 1, 2 <= K <= 256");
   long blocks = ((long)D * K + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(sim_smooth_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, codebook, fwd4, g_loss, D, K, weight, g_codebook);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, sim_smooth_bwd_kernel, dim3((unsigned)blocks), 256, 0, stream, codebook, fwd4, g_loss, D, K, weight, g_codebook);
 }

@@ -5,6 +5,7 @@
 //    the identity: no backward kernel.
 //  * vqn_ks_split_fwd / _bwd: spec = ks * basecolor, albedo = (1 - ks) * basecolor (vq_nfr.py:590-592) and their adjoints.
 #include "common.h"
+#include "launch.h"
 #include "vqnerf_hip.h"
 
 namespace {
@@ -64,11 +65,7 @@ __global__ __launch_bounds__(256) void loss_total_kernel(const float* __restrict
   }
 }
 
-long grid_for(long n) {
-  long blocks = (n + 255) / 256;
-  const long cap = (long)vqn_num_cus() * 16;
-  return blocks > cap ? cap : (blocks < 1 ? 1 : blocks);
-}
+long grid_for(long n) { return vqn_grid1((n + 255) / 256, 16); }
 
 }  // namespace
 
@@ -76,19 +73,15 @@ extern "C" int vqn_clip_preserve(const float* x, int64_t n, float lo, float hi, 
   VQN_CHECK_ARG(n >= 0, "n >= 0");
   if (n == 0) return VQN_OK;
   VQN_CHECK_ARG(x && y, "null pointer");
-  hipLaunchKernelGGL(clip_preserve_kernel, dim3((unsigned)grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, (long)n, lo, hi, y);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, clip_preserve_kernel, dim3((unsigned)grid_for(n)), 256, 0, stream, x, (long)n, lo, hi, y);
 }
 
 extern "C" int vqn_ks_split_fwd(const float* basecolor, const float* ks, int ks_channels, int64_t n, float* albedo, float* spec, void* stream) {
   VQN_CHECK_ARG(n >= 0 && (ks_channels == 1 || ks_channels == 3), "n >= 0, ks_channels 1 | 3");
   if (n == 0) return VQN_OK;
   VQN_CHECK_ARG(basecolor && ks && albedo && spec, "null pointer");
-  hipLaunchKernelGGL(ks_split_fwd_kernel, dim3((unsigned)grid_for(3 * n)), dim3(256), 0, (hipStream_t)stream, basecolor, ks, ks_channels, (long)n,
-                     albedo, spec);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, ks_split_fwd_kernel, dim3((unsigned)grid_for(3 * n)), 256, 0, stream, basecolor, ks, ks_channels, (long)n,
+                    albedo, spec);
 }
 
 extern "C" int vqn_ks_split_bwd(const float* basecolor, const float* ks, int ks_channels, int64_t n, const float* g_albedo, const float* g_spec,
@@ -96,10 +89,8 @@ extern "C" int vqn_ks_split_bwd(const float* basecolor, const float* ks, int ks_
   VQN_CHECK_ARG(n >= 0 && (ks_channels == 1 || ks_channels == 3), "n >= 0, ks_channels 1 | 3");
   if (n == 0) return VQN_OK;
   VQN_CHECK_ARG(basecolor && ks && g_basecolor && g_ks, "null pointer");
-  hipLaunchKernelGGL(ks_split_bwd_kernel, dim3((unsigned)grid_for(n)), dim3(256), 0, (hipStream_t)stream, basecolor, ks, ks_channels, (long)n,
-                     g_albedo, g_spec, g_basecolor, g_ks);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, ks_split_bwd_kernel, dim3((unsigned)grid_for(n)), 256, 0, stream, basecolor, ks, ks_channels, (long)n,
+                    g_albedo, g_spec, g_basecolor, g_ks);
 }
 
 extern "C" int vqn_loss_total(const float* terms, int64_t n, const float* vqloss, const float* sim, int use_chr, int use_smooth, int use_lambert,
@@ -107,8 +98,6 @@ extern "C" int vqn_loss_total(const float* terms, int64_t n, const float* vqloss
   VQN_CHECK_ARG(n >= 0, "n >= 0");
   if (n == 0) return VQN_OK;
   VQN_CHECK_ARG(terms && vqloss && out, "null pointer");
-  hipLaunchKernelGGL(loss_total_kernel, dim3((unsigned)grid_for(n)), dim3(256), 0, (hipStream_t)stream, terms, (long)n, vqloss, sim, use_chr,
-                     use_smooth, use_lambert, out);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, loss_total_kernel, dim3((unsigned)grid_for(n)), 256, 0, stream, terms, (long)n, vqloss, sim, use_chr,
+                    use_smooth, use_lambert, out);
 }

@@ -441,9 +441,7 @@ extern "C" int vqn_mlp_chain_vq_fwd(const int32_t* desc_a, const float* wbuf_a, 
   const int rows = da.total_rows > db.total_rows ? da.total_rows : db.total_rows;
   const size_t lds = (size_t)rows * 1024 + sizeof(ChainSmalls) + (size_t)(da.small_w4 > db.small_w4 ? da.small_w4 : db.small_w4) * 16 + (size_t)KT * 16 * 4 + 4 * 4;
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "the two programs do not fit in 160 KB of LDS");
-  const void* kern = KT == 1 ? (const void*)mlp_chain_vq_kernel<1> : (KT == 2 ? (const void*)mlp_chain_vq_kernel<2> : (const void*)mlp_chain_vq_kernel<4>);
-  if (lds > 64 * 1024) VQN_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long grid = chain_grid(4, lds, (N + 31) / 32);
+  const long grid = vqn_tile_grid(4, lds, (N + 31) / 32);
   VQN_CHECK_SHAPE(grid + 1 <= VQN_QUANT_WS_FLOATS, "workspace too small for this device");
   VqTail vq;
   vq.frags = reinterpret_cast<const f32x4*>(cb_frags);
@@ -453,14 +451,11 @@ extern "C" int vqn_mlp_chain_vq_fwd(const int32_t* desc_a, const float* wbuf_a, 
   vq.loss_part = ws + 1;
   vq.counts = counts;
   vq.ste_out = ste;
-#define VQN_FRONT(KT_)                                                                                                              \
-  hipLaunchKernelGGL(mlp_chain_vq_kernel<KT_>, dim3((unsigned)grid), dim3(256), lds, s, da, reinterpret_cast<const f32x4*>(wbuf_a), db, \
-                     reinterpret_cast<const f32x4*>(wbuf_b), in, (long)N, oa, ob, z_row0, vq)
-  if (KT == 1) VQN_FRONT(1);
-  else if (KT == 2) VQN_FRONT(2);
-  else VQN_FRONT(4);
-#undef VQN_FRONT
-  VQN_LAUNCH_CHECK();
+  const int rc = vqn_pick<1, 2, 4>(__func__, KT, [&](auto kt) {
+    return vqn_launch("vqn_mlp_chain_vq_fwd", mlp_chain_vq_kernel<decltype(kt)::value>, grid, 256, lds, s, da, reinterpret_cast<const f32x4*>(wbuf_a), db,
+                      reinterpret_cast<const f32x4*>(wbuf_b), in, (long)N, oa, ob, z_row0, vq);
+  });
+  if (rc != VQN_OK) return rc;
   return vqn_internal_finish_loss(ws + 1, (int)grid, loss_scale, loss, s);
 }
 

@@ -2,10 +2,11 @@
 // the backward (neus_train_bwd.hip, neus_train_bwd_x3.hip): descriptors, argument checks, grid sizing, launch.  Not a public header.
 #pragma once
 #include "neus_phases.h"
+#include "launch.h"
 #include <stdio.h>
 
 // The checks report under the entry point's own name (`fn`), so that an argument or shape message reads as it would from the entry
-// point itself; a HIP error names this header as its location.
+// point itself; a HIP error names launch.h as its location.
 
 // the sdf form (vqn_neus_sdf_points*): on VQN_OK with P > 0, *sd holds the checked descriptor; P == 0 is VQN_OK with nothing to do
 static int neus_sdf_args(const char* fn, const int32_t* sdf_desc, const float* wbuf_sdf, const float* rays_o, const float* rays_d,
@@ -65,23 +66,7 @@ static int64_t neus_stash_bytes(const SdfDesc& sd) { return (int64_t)(sd.n_lin -
 // two 256-thread one-image ones), no more than there are groups, and no more than `scratch_bytes` holds stashes of `per_img` bytes per
 // image (per_img == 0: the kernel keeps no stash).  0 = the scratch holds not even one workgroup's.
 static long pair_grid(const long n_tiles, const int images, const int64_t per_img, const int64_t scratch_bytes) {
-  long grid = (long)vqn_num_cus() * (images == 1 ? 2 : 1);
-  const long groups = (n_tiles + images - 1) / images;
-  if (grid > groups) grid = groups;
-  // (per_img == 0 makes the comparison false, so the division below never sees a zero divisor)
-  if ((int64_t)grid * images * per_img > scratch_bytes) grid = (long)(scratch_bytes / (images * per_img));
-  return grid;
-}
-
-// launch the kernel with `lds` bytes of dynamic LDS; `opt_in`: raise its limit first (the two-image forms always, the one-image forms
-// beyond the 64 KiB a kernel gets unasked)
-template <class Kernel, class... Args>
-static int neus_launch(const char* fn, const Kernel kernel, const bool opt_in, const long grid, const int threads, const size_t lds, void* stream,
-                       const Args... args) {
-  if (opt_in) VQN_HIP_IN(fn, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, (hipStream_t)stream, args...);
-  VQN_HIP_IN(fn, hipGetLastError());
-  return VQN_OK;
+  return vqn_grid_in_scratch(vqn_grid((n_tiles + images - 1) / images, images == 1 ? 2 : 1), images * per_img, scratch_bytes);
 }
 
 // ---- the backward (vqn_neus_train_bwd, vqn_neus_train_bwd_x3): one pass, two engines.  What differs between them stays in their files:

@@ -761,8 +761,8 @@ int sdf_images(const SdfDesc& sd) {
 template <int NIMG>
 int launch_sdf_images(const char* fn, const SdfDesc& sd, const f32x4* ws, const float* rays_o, const float* rays_d, const float* z,
                       const float* pts, const int64_t P, const int S, float* out_sdf, void* stream) {
-  return neus_launch(fn, neus_pointsN_kernel<NIMG>, true, pair_grid((P + 31) / 32, NIMG, 0, 0), 512, lds_bytes_sdf<NIMG>(sd), stream, sd, ws,
-                     rays_o, rays_d, z, pts, (long)P, S, out_sdf);
+  return vqn_launch(fn, neus_pointsN_kernel<NIMG>, pair_grid((P + 31) / 32, NIMG, 0, 0), 512, lds_bytes_sdf<NIMG>(sd), stream, sd, ws,
+                    rays_o, rays_d, z, pts, (long)P, S, out_sdf);
 }
 
 bool extras_rows_ok(const ColDesc& cd) { return cd.extra_rows >= 1 && cd.extra_rows <= 8; }
@@ -784,12 +784,12 @@ extern "C" int vqn_neus_sdf_points(const int32_t* sdf_desc, const float* wbuf_sd
   if (images == 4) return launch_sdf_images<4>(__func__, sd, ws, rays_o, rays_d, z, pts, P, S, out_sdf, stream);
   if (images == 3) return launch_sdf_images<3>(__func__, sd, ws, rays_o, rays_d, z, pts, P, S, out_sdf, stream);
   if (images == 2)
-    return neus_launch(__func__, neus_points2_kernel<false>, true, pair_grid(n_tiles, 2, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws,
-                       nullptr, rays_o, rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
+    return vqn_launch(__func__, neus_points2_kernel<false>, pair_grid(n_tiles, 2, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws,
+                      nullptr, rays_o, rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
   const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  return neus_launch(__func__, neus_points_kernel<false>, lds > 64 * 1024, pair_grid(n_tiles, 1, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o, rays_d,
-                     z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr);
+  return vqn_launch(__func__, neus_points_kernel<false>, pair_grid(n_tiles, 1, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o, rays_d,
+                    z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr);
 }
 
 // Training forward: vqn_neus_fine_points at explicit (pts, dirs) that ALSO writes the saved tensors of the training engine (see
@@ -817,10 +817,10 @@ extern "C" int vqn_neus_train_fwd(const int32_t* sdf_desc, const float* wbuf_sdf
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
   const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  return neus_launch(__func__, neus_points2_kernel<true, true>, true, grid, 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd,
-                     reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr, nullptr, pts, dirs,
-                     (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb,
-                     neus_train_out(tensors, nL, nC, e_tiles, outf_tiles, extr_tiles));
+  return vqn_launch(__func__, neus_points2_kernel<true, true>, grid, 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd,
+                    reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr, nullptr, pts, dirs,
+                    (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb,
+                    neus_train_out(tensors, nL, nC, e_tiles, outf_tiles, extr_tiles));
 }
 
 extern "C" int64_t vqn_neus_fine_scratch_bytes(const int32_t* sdf_desc) {
@@ -864,14 +864,14 @@ extern "C" int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_s
     const long grid = pair_grid(n_tiles, 2, per_img, scratch_bytes);
 #endif
     VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-    return neus_launch(__func__, fold ? neus_points2_kernel<true, false, true> : neus_points2_kernel<true>, true, grid, 512, lds_bytes<2>(sd.max_tiles),
-                       stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad,
-                       out_rgb, TrainOut{});
+    return vqn_launch(__func__, fold ? neus_points2_kernel<true, false, true> : neus_points2_kernel<true>, grid, 512, lds_bytes<2>(sd.max_tiles),
+                      stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad,
+                      out_rgb, TrainOut{});
   }
   const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
   const long grid = pair_grid(n_tiles, 1, per_img, scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  return neus_launch(__func__, neus_points_kernel<true>, lds > 64 * 1024, grid, 256, lds, stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S,
-                     reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);
+  return vqn_launch(__func__, neus_points_kernel<true>, grid, 256, lds, stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S,
+                    reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);
 }

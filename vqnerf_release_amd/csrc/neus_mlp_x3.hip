@@ -448,9 +448,9 @@ extern "C" int vqn_neus_sdf_points_x3(const int32_t* sdf_desc, const float* wbuf
   memset(&cd, 0, sizeof(cd));
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
-  return neus_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<false, 2> : neus_points_x3_kernel<false, 1>, true,
-                     pair_grid((P + 31) / 32, 2, 0, 0), 512, lds2, stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), nullptr, rays_o,
-                     rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
+  return vqn_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<false, 2> : neus_points_x3_kernel<false, 1>,
+                    pair_grid((P + 31) / 32, 2, 0, 0), 512, lds2, stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), nullptr, rays_o,
+                    rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
 }
 
 extern "C" int vqn_neus_fine_points_x3(const int32_t* sdf_desc, const float* wbuf_sdf, const int32_t* col_desc,
@@ -467,9 +467,9 @@ extern "C" int vqn_neus_fine_points_x3(const int32_t* sdf_desc, const float* wbu
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
   const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  return neus_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2> : neus_points_x3_kernel<true, 1>, true, grid, 512, lds2, stream, sd,
-                     cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d, z, pts, dirs,
-                     (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb, TrainOut{});
+  return vqn_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2> : neus_points_x3_kernel<true, 1>, grid, 512, lds2, stream, sd,
+                    cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d, z, pts, dirs,
+                    (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb, TrainOut{});
 }
 
 // Training forward on the exact-split engine: vqn_neus_train_fwd with x3 packs and descriptors (vqn_neus_pack_create(..., f16s = 2)).
@@ -498,8 +498,8 @@ extern "C" int vqn_neus_train_fwd_x3(const int32_t* sdf_desc, const float* wbuf_
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
   const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
-  return neus_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2, true> : neus_points_x3_kernel<true, 1, true>, true, grid, 512, lds2,
-                     stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr,
-                     nullptr, pts, dirs, (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb,
-                     neus_train_out(tensors, nL, nC, e_tiles, outf_tiles, extr_tiles));
+  return vqn_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2, true> : neus_points_x3_kernel<true, 1, true>, grid, 512, lds2,
+                    stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr,
+                    nullptr, pts, dirs, (long)P, 1, reinterpret_cast<f32x4*>(scratch), out_sdf, out_n, out_rgb,
+                    neus_train_out(tensors, nL, nC, e_tiles, outf_tiles, extr_tiles));
 }

@@ -7,6 +7,7 @@
 //   the reverse of the latter (autograd in the reference)                                     -> vqn_neus_composite_bwd
 #include "common.h"
 #include "wave.h"
+#include "launch.h"
 #include <math.h>
 
 namespace {
@@ -394,13 +395,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs a)
   }
 }
 
-int ray_grid(long B) {
-  long g = (B + 3) / 4;
-  const long cap = (long)vqn_num_cus() * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+int ray_grid(long B) { return (int)vqn_grid1((B + 3) / 4, 8); }
 
 }  // namespace
 
@@ -412,10 +407,8 @@ extern "C" int vqn_neus_upsample(const float* rays_o, const float* rays_d, const
   VQN_CHECK_ARG(rays_o && rays_d && z && sdf && u && z_new, "null pointer");
   VQN_CHECK_SHAPE(n >= 2 && n <= MAXN, "2 <= n <= 256 samples per ray");
   VQN_CHECK_SHAPE(n_new >= 1 && n_new <= 64, "1 <= n_new <= 64");
-  hipLaunchKernelGGL(upsample_kernel, dim3(ray_grid(B)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z, sdf,
-                     (long)B, n, r_limit, inv_s, u, n_new, z_new);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, upsample_kernel, dim3(ray_grid(B)), 256, 0, stream, rays_o, rays_d, z, sdf,
+                    (long)B, n, r_limit, inv_s, u, n_new, z_new);
 }
 
 extern "C" int vqn_neus_merge(const float* z, const float* sdf, const float* z_new, const float* sdf_new, int64_t B,
@@ -425,10 +418,8 @@ extern "C" int vqn_neus_merge(const float* z, const float* sdf, const float* z_n
   VQN_CHECK_ARG(z && z_new && z_out, "null pointer");
   VQN_CHECK_ARG(sdf_out == nullptr || (sdf && sdf_new), "sdf_out needs sdf and sdf_new");
   VQN_CHECK_SHAPE(n >= 1 && n <= MAXN && n_new >= 1 && n_new <= 64, "n <= 256, n_new <= 64");
-  hipLaunchKernelGGL(merge_kernel, dim3(ray_grid(B)), dim3(256), 0, (hipStream_t)stream, z, sdf, z_new, sdf_new,
-                     (long)B, n, n_new, z_out, sdf_out);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, merge_kernel, dim3(ray_grid(B)), 256, 0, stream, z, sdf, z_new, sdf_new,
+                    (long)B, n, n_new, z_out, sdf_out);
 }
 
 extern "C" int vqn_neus_section_mids(const float* z, int64_t B, int n, float sample_dist,
@@ -437,10 +428,8 @@ extern "C" int vqn_neus_section_mids(const float* z, int64_t B, int n, float sam
   if (B == 0) return VQN_OK;
   VQN_CHECK_ARG(z && mid_z, "null pointer");
   const long tot = (long)B * n;
-  hipLaunchKernelGGL(section_mids_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z,
-                     (long)B, n, sample_dist, sample_dist_per_ray, mid_z, dists);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, section_mids_kernel, dim3((unsigned)((tot + 255) / 256)), 256, 0, stream, z,
+                    (long)B, n, sample_dist, sample_dist_per_ray, mid_z, dists);
 }
 
 extern "C" int vqn_neus_composite_fwd(const float* rays_o, const float* rays_d, const float* mid_z, const float* dists,
@@ -456,9 +445,7 @@ extern "C" int vqn_neus_composite_fwd(const float* rays_o, const float* rays_d, 
   VQN_CHECK_SHAPE(n >= 1 && n <= MAXN, "1 <= n <= 256 samples per ray");
   CompArgs a{rays_o, rays_d, mid_z, dists, sdf, grad, rgb, inv_s, background_rgb, (long)B, n, radius, cos_anneal_ratio,
              color, weights, cdf, inside, surf, depth, weight_sum, weight_max, gerr, alpha};
-  hipLaunchKernelGGL(composite_fwd_kernel, dim3(ray_grid(B)), dim3(256), 0, (hipStream_t)stream, a);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, composite_fwd_kernel, dim3(ray_grid(B)), 256, 0, stream, a);
 }
 
 extern "C" int vqn_neus_composite_bwd(const float* rays_o, const float* rays_d, const float* mid_z, const float* dists,
@@ -478,7 +465,5 @@ extern "C" int vqn_neus_composite_bwd(const float* rays_o, const float* rays_d, 
   a.bg = background_rgb; a.g_color = g_color; a.g_wsum = g_weight_sum; a.g_weights = g_weights;
   a.g_gerr = g_gradient_error; a.gerr_den = gerr_den; a.rays_o = rays_o; a.B = B; a.n = n; a.radius = radius;
   a.car = cos_anneal_ratio; a.g_sdf = g_sdf; a.g_grad = g_grad; a.g_rgb = g_rgb; a.g_inv_s = g_inv_s;
-  hipLaunchKernelGGL(composite_bwd_kernel, dim3(ray_grid(B)), dim3(256), 0, (hipStream_t)stream, a);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, composite_bwd_kernel, dim3(ray_grid(B)), 256, 0, stream, a);
 }

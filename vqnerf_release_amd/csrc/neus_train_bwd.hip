@@ -298,6 +298,6 @@ extern "C" int vqn_neus_train_bwd(const int32_t* desc, const float* wbuf, const 
   const int rc = train_bwd_args(__func__, desc, wbuf, wbuf, pts, g_rgb, rgb, g_n, g_sdf, P, scratch, scratch_bytes, saved, n_saved, outs,
                                 n_outs, engine_rules, "invalid backward descriptor", &bd, &tp, &grid);
   if (rc != VQN_OK) return rc;
-  return neus_launch(__func__, neus_train_bwd2_kernel, true, grid, 512, lds_bytes_b(bd.max_tiles), stream, bd,
-                     reinterpret_cast<const f32x4*>(wbuf), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
+  return vqn_launch(__func__, neus_train_bwd2_kernel, grid, 512, lds_bytes_b(bd.max_tiles), stream, bd,
+                    reinterpret_cast<const f32x4*>(wbuf), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
 }

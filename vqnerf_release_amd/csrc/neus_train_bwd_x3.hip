@@ -373,7 +373,7 @@ extern "C" int vqn_neus_train_bwd_x3(const int32_t* desc, const void* wbuf_piece
                                 outs, n_outs, engine_rules, "invalid backward descriptor for the x3 engine (layers of at most 256 outputs)",
                                 &bd, &tp, &grid);
   if (rc != VQN_OK) return rc;
-  return neus_launch(__func__, bwd_nacc() == 2 ? neus_train_bwd_x3_kernel<2> : neus_train_bwd_x3_kernel<1>, true, grid, 512,
-                     lds_bytes_b(bd.max_tiles), stream, bd, reinterpret_cast<const f32x4*>(wbuf_pieces),
-                     reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
+  return vqn_launch(__func__, bwd_nacc() == 2 ? neus_train_bwd_x3_kernel<2> : neus_train_bwd_x3_kernel<1>, grid, 512,
+                    lds_bytes_b(bd.max_tiles), stream, bd, reinterpret_cast<const f32x4*>(wbuf_pieces),
+                    reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
 }

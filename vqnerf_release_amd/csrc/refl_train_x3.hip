@@ -19,6 +19,7 @@
 // Saved tensors and adjoints are f32 in the tile format [point tile][feature tile][32 features][32 points] the contraction reads.
 #include "x3_calls.h"
 #include "tfmt.h"
+#include "launch.h"
 #include "vqnerf_hip.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -686,7 +687,20 @@ int images_per_wg(long n_tiles, const ReflDesc& rd) {
   if (rd.zx_tiles > 0) return 1;                                 // (two image regions per point tile: one image per workgroup)
   const char* e = getenv("VQN_REFL_NIMG");                       // (read per call: the tests switch it)
   if (e && (e[0] == '1' || e[0] == '2')) return e[0] - '0';
-  return (n_tiles + 1) / 2 * 2 <= (long)vqn_num_cus() ? 1 : 2;
+  return vqn_fits_cus((n_tiles + 1) / 2 * 2, 1) ? 1 : 2;         // (no more tiles, rounded up to pairs, than CUs)
+}
+
+// what the forward and the backward launch over P points: images per workgroup, its LDS bytes, the workgroups (x dimension)
+struct ReflLaunch {
+  int nimg;
+  size_t lds;
+  long grid;
+};
+ReflLaunch refl_launch(const int64_t P, const ReflDesc& rd) {
+  const long n_tiles = (P + 31) / 32;
+  const int nimg = images_per_wg(n_tiles, rd);
+  const long units = nimg == 1 ? n_tiles : (n_tiles + 1) / 2;
+  return {nimg, lds_bytes_r(rd.max_tiles, nimg, rd.zx_tiles), vqn_grid(units, RT_WGS_PER_CU(nimg))};
 }
 
 }  // namespace
@@ -732,19 +746,12 @@ extern "C" int vqn_refl_train_fwd_x3_zx(const int32_t* desc, const void* wbuf_pi
     VQN_CHECK_ARG(head_out[k] != nullptr, "null head output");
     tp.OUT[k] = head_out[k];
   }
-  const long n_tiles = (P + 31) / 32;
-  const int nimg = images_per_wg(n_tiles, rd);
-  const size_t lds = lds_bytes_r(rd.max_tiles, nimg, rd.zx_tiles);
-  auto kern = nimg == 1 ? refl_train_fwd_x3_kernel<1> : refl_train_fwd_x3_kernel<2>;
-  VQN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long units = nimg == 1 ? n_tiles : (n_tiles + 1) / 2;
-  long grid = (long)vqn_num_cus() * RT_WGS_PER_CU(nimg);
-  if (grid > units) grid = units;
+  const ReflLaunch L = refl_launch(P, rd);
   const unsigned gy = (split_heads && nH > 1) ? (unsigned)nH : 1u;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid, gy), dim3(512), lds, (hipStream_t)stream, rd, reinterpret_cast<const f32x4*>(wbuf_pieces),
-                     reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_pick<1, 2>(__func__, L.nimg, [&](auto nimg) {
+    return vqn_launch("vqn_refl_train_fwd_x3_zx", refl_train_fwd_x3_kernel<decltype(nimg)::value>, dim3((unsigned)L.grid, gy), 512, L.lds, stream, rd,
+                      reinterpret_cast<const f32x4*>(wbuf_pieces), reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P);
+  });
 }
 
 extern "C" int64_t vqn_refl_train_bwd_x3_scratch_bytes(const int32_t* desc) {
@@ -792,22 +799,15 @@ extern "C" int vqn_refl_train_bwd_x3(const int32_t* desc, const void* wbuf_piece
     tp.H0[k] = saved[nE + 2 * k]; tp.H1[k] = saved[nE + 2 * k + 1];
     tp.D0[k] = outs[nE + 3 * k]; tp.D1[k] = outs[nE + 3 * k + 1]; tp.D2[k] = outs[nE + 3 * k + 2];
   }
-  const long n_tiles = (P + 31) / 32;
-  const int nimg = images_per_wg(n_tiles, rd);
+  const ReflLaunch L = refl_launch(P, rd);
   const unsigned gy = split ? (unsigned)nH : 1u;
-  const int64_t per_wg = (int64_t)nimg * 4 * rd.z_tiles * 1024;
-  const size_t lds = lds_bytes_r(rd.max_tiles, nimg, rd.zx_tiles);
-  auto kern = nimg == 1 ? refl_train_bwd_x3_kernel<1> : refl_train_bwd_x3_kernel<2>;
-  VQN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long units = nimg == 1 ? n_tiles : (n_tiles + 1) / 2;
-  long grid = (long)vqn_num_cus() * RT_WGS_PER_CU(nimg);
-  if (grid > units) grid = units;
-  if ((int64_t)grid * gy * per_wg > scratch_bytes) grid = (long)(scratch_bytes / (per_wg * gy));
+  const long grid = vqn_grid_in_scratch(L.grid, (int64_t)gy * L.nimg * 4 * rd.z_tiles * 1024, scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_refl_train_bwd_x3_scratch_bytes)");
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid, gy), dim3(512), lds, (hipStream_t)stream, rd, reinterpret_cast<const f32x4*>(wbuf_pieces),
-                     reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P, reinterpret_cast<f32x4*>(scratch));
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_pick<1, 2>(__func__, L.nimg, [&](auto nimg) {
+    return vqn_launch("vqn_refl_train_bwd_x3", refl_train_bwd_x3_kernel<decltype(nimg)::value>, dim3((unsigned)grid, gy), 512, L.lds, stream, rd,
+                      reinterpret_cast<const f32x4*>(wbuf_pieces), reinterpret_cast<const f32x4*>(wbuf_f32), tp, (long)P,
+                      reinterpret_cast<f32x4*>(scratch));
+  });
 }
 
 #ifdef VQN_RT_STAMPS

@@ -9,6 +9,7 @@
 // built by vqnerf_release_amd/geo/train_programs.py.  Weight gradients (contractions over points) are taken from the
 // saved TFMT tensors by csrc/wgrad.hip.  Formats: include/vqn_vm_desc.h.
 #include "mlp_prims.h"
+#include "launch.h"
 #include <type_traits>
 #include <vector>
 #include "vqn_vm_desc.h"
@@ -450,13 +451,14 @@ extern "C" int vqn_tfmt_unpack(const float* t, int tiles_f, int64_t N, int F, fl
   return VQN_OK;
 }
 
+// LDS bytes and workgroups of a program over N points: what vqn_tile_program launches and what vqn_tile_program_grid tells the caller
+// who allocates per-workgroup tensors
+static size_t vm_lds(const VmDesc* d) { return (size_t)d->total_rows * 1024; }
+static long vm_grid(const VmDesc* d, const int64_t N) { return vqn_tile_grid(d->n_waves, vm_lds(d), (N + 31) / 32); }
+
 extern "C" int64_t vqn_tile_program_grid(const int32_t* desc_host, int64_t N) {
   if (desc_host == nullptr || N <= 0) return 0;
-  const VmDesc* d = reinterpret_cast<const VmDesc*>(desc_host);
-  const size_t lds = (size_t)d->total_rows * 1024;
-  const long n_tiles = (N + 31) / 32;
-  long grid = (long)vqn_num_cus() * ((d->n_waves == 4 && 2 * lds <= 160 * 1024) ? 2 : 1);
-  return grid > n_tiles ? n_tiles : grid;
+  return vm_grid(reinterpret_cast<const VmDesc*>(desc_host), N);
 }
 
 extern "C" int vqn_tile_program(const void* desc_dev, const int32_t* desc_host, const float* wbuf,
@@ -468,7 +470,7 @@ extern "C" int vqn_tile_program(const void* desc_dev, const int32_t* desc_host, 
   const VmDesc* d = reinterpret_cast<const VmDesc*>(desc_host);
   VQN_CHECK_SHAPE(d->n_ops >= 1 && d->n_ops <= VQN_VM_MAX_OPS, "1 <= n_ops <= 96");
   VQN_CHECK_SHAPE(d->n_waves == 4 || d->n_waves == 8, "n_waves must be 4 or 8");
-  const size_t lds = (size_t)d->total_rows * 1024;
+  const size_t lds = vm_lds(d);
   VQN_CHECK_SHAPE(d->total_rows >= 1 && lds <= 160 * 1024, "program does not fit in 160 KB of LDS");
   // validate every op against the row budget and the tensor table before anything is launched
   const int32_t* const tensor_ld_arg = tensor_ld;         // negative entries flag per-workgroup tensors (vqn_tile_program_grid)
@@ -547,23 +549,10 @@ extern "C" int vqn_tile_program(const void* desc_dev, const int32_t* desc_host, 
   VmTable tab;
   memset(&tab, 0, sizeof(tab));
   for (int i = 0; i < n_tensors; ++i) { tab.t[i].ptr = tensors[i]; tab.t[i].ld = tensor_ld[i] < 0 ? -tensor_ld[i] : tensor_ld[i]; tab.t[i].pad = tensor_ld[i] < 0; }
-  const long n_tiles = (N + 31) / 32;
-  hipStream_t s = (hipStream_t)stream;
   const VmDesc* dd = reinterpret_cast<const VmDesc*>(desc_dev);
-  if (d->n_waves == 4) {
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)tile_vm_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per_cu = (2 * lds <= 160 * 1024) ? 2 : 1;
-    long grid = (long)vqn_num_cus() * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(tile_vm_kernel<4>, dim3((unsigned)grid), dim3(256), lds, s, dd, reinterpret_cast<const f32x4*>(wbuf), tab, (long)N);
-  } else {
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)tile_vm_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    long grid = (long)vqn_num_cus();
-    if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(tile_vm_kernel<8>, dim3((unsigned)grid), dim3(512), lds, s, dd, reinterpret_cast<const f32x4*>(wbuf), tab, (long)N);
-  }
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_pick<4, 8>(__func__, d->n_waves, [&](auto nw) {
+    constexpr int NW = decltype(nw)::value;
+    return vqn_launch("vqn_tile_program", tile_vm_kernel<NW>, dim3((unsigned)vm_grid(d, N)), NW * 64, lds, stream, dd,
+                      reinterpret_cast<const f32x4*>(wbuf), tab, (long)N);
+  });
 }

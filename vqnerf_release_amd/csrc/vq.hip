@@ -13,7 +13,7 @@
 //     dist      : (x2 - 2 dot) + c2 ; argmin, lowest index wins ties.
 // The codebook lives in LDS already laid out as MFMA B-fragments (one ds_read_b128 per 4 MFMAs).
 #include "vq_step.h"
-#include "vqnerf_hip.h"
+#include "vq_plan.h"
 #include <math.h>
 
 namespace {
@@ -954,82 +954,6 @@ __global__ __launch_bounds__(256) void vq_counts_kernel(const long long* __restr
     if (hist[k]) atomicAdd(&counts[k], (float)hist[k]);
 }
 
-static bool ema_mfma_ok(int D, int K) { return D > 0 && (D & 63) == 0 && D <= 256 && K > 0 && K <= 64; }
-static int ema_mfma_kt(int K) { return K <= 16 ? 1 : K <= 32 ? 2 : 4; }
-static long ema_mfma_grid(long N, int K) {
-  const long per_cu = ema_mfma_kt(K) == 4 ? 1 : 2;          // KT = 4 keeps 256 accumulator registers: one wave per SIMD
-  long blocks = ((N + 3) / 4 + 3) / 4;                      // >= one 4-row step per wave
-  const long cap = (long)vqn_num_cus() * per_cu;
-  if (blocks > cap) blocks = cap;
-  return blocks < 1 ? 1 : blocks;
-}
-
-static long ema_grid(long N, int D, int K) {
-  const size_t lds = (size_t)4 * (K * D + K) * sizeof(float);
-  const long per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-  long blocks = (N + 63) / 64;
-  const long cap = (long)vqn_num_cus() * per_cu;
-  if (blocks > cap) blocks = cap;
-  return blocks < 1 ? 1 : blocks;
-}
-
-static long assign_grid(long N) {
-  const long n_groups = (N + 15) >> 4;
-  long blocks = (n_groups + 3) / 4;
-  const long cap = (long)vqn_num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  return blocks < 1 ? 1 : blocks;
-}
-
-template <int KT, bool FUSE>
-int launch_assign(const float* x, long N, int D, const float* C, int K, const float* sel, float* ws, long long* idx,
-                  float* quant, float* dist, const VqFuse fuse, hipStream_t s) {
-  const int D16 = (D + 15) >> 4;
-  const size_t lds = ((size_t)KT * D16 * 256 + 3 * KT * 16 + 4) * sizeof(float);
-  const long blocks = assign_grid(N);
-  if (lds > 64 * 1024) {
-    VQN_HIP(hipFuncSetAttribute((const void*)vq_assign_kernel<KT, true, FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    VQN_HIP(hipFuncSetAttribute((const void*)vq_assign_kernel<KT, false, FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  if (sel != nullptr) {
-    // distances.max() is taken over the UNMASKED distances (vq_layers.py:285) -> extra pass
-    VQN_HIP(hipMemsetD32Async((hipDeviceptr_t)ws, (int)0x807fffff /* key(-inf) */, 1, s));
-    hipLaunchKernelGGL((vq_assign_kernel<KT, true, FUSE>), dim3((unsigned)blocks), dim3(256), lds, s, x, N, D, C, K, sel,
-                       reinterpret_cast<int*>(ws), idx, quant, dist, fuse);
-    VQN_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL((vq_assign_kernel<KT, false, FUSE>), dim3((unsigned)blocks), dim3(256), lds, s, x, N, D, C, K, sel,
-                     reinterpret_cast<int*>(ws), idx, quant, dist, fuse);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
-}
-
-// The prefiltered kernel (vq_assign_split_kernel) serves K in 17..64 without a code-dropout mask or a distance output; VQN_VQ_SPLIT=0
-// keeps the f32 kernel (A/B measurements, bisecting).
-static bool split_ok(int K, int D, const float* sel, const float* dist) {
-  static const int on = [] { const char* e = getenv("VQN_VQ_SPLIT"); return (e == nullptr || atoi(e) != 0) ? 1 : 0; }();
-  return on && K > 16 && K <= 64 && D <= 256 && sel == nullptr && dist == nullptr;
-}
-
-static long split_grid(long N) {
-  const long n_groups = (N + 15) >> 4;
-  long blocks = (n_groups + 7) / 8;
-  const long cap = (long)vqn_num_cus();
-  if (blocks > cap) blocks = cap;
-  return blocks < 1 ? 1 : blocks;
-}
-
-template <int KT, bool FUSE>
-int launch_split(const float* x, long N, int D, const float* C, int K, long long* idx, float* quant, const VqFuse fuse, hipStream_t s) {
-  const int D16 = (D + 15) >> 4;
-  const size_t lds = (size_t)KT * D16 * 1024 + (size_t)2 * KT * 8 * 1024 + ((size_t)2 * KT * 16 + 4 + 8) * sizeof(float);
-  VQN_CHECK_SHAPE(lds <= 160 * 1024, "codebook does not fit in 160 KB of LDS");
-  VQN_HIP(hipFuncSetAttribute((const void*)vq_assign_split_kernel<KT, FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((vq_assign_split_kernel<KT, FUSE>), dim3((unsigned)split_grid(N)), dim3(512), lds, s, x, N, D, C, K, idx, quant, fuse);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
-}
-
 // B fragments + |c|^2 of a codebook of <= 64 codes (1, 2 or 4 tiles of 16), D = 256, as the fused reflectance kernel (csrc/mlp_chain.hip) reads them:
 // exactly what vq_assign_kernel<1, ...> stages into LDS (same element order, the same fmaf chain over d for |c|^2).
 __global__ __launch_bounds__(256) void vq_codebook_frags_kernel(const float* __restrict__ C, int D, int K, int KT, float* __restrict__ out) {
@@ -1056,23 +980,60 @@ __global__ __launch_bounds__(256) void vq_codebook_frags_kernel(const float* __r
 
 }  // namespace
 
+// ---- host side: argument checks, one call into the plan (vq_plan.h), vqn_pick and vqn_launch (launch.h) ----
+
+static long here(const VqGrid& g) { return vqn_grid1(g.units, g.per_cu); }      // the workgroups of a planned grid on this device
+static bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
+// VQN_VQ_SPLIT=0 keeps the f32 kernel where the prefiltered one would run (A/B measurements, bisecting)
+static bool split_on() {
+  static const int on = [] { const char* e = getenv("VQN_VQ_SPLIT"); return (e == nullptr || atoi(e) != 0) ? 1 : 0; }();
+  return on != 0;
+}
+
+// What vqn_vq_assign and the fused forms share: the plan's refusals, the choice of kernel, the launch.  *blocks: the workgroups (FUSE:
+// each leaves a loss sum in fuse.loss_part).
+template <bool FUSE>
+static int assign_rows(const char* fn, const float* x, const long N, const int D, const float* C, const int K, const float* sel, float* ws,
+                       long long* idx, float* quant, float* dist, const VqFuse fuse, void* s, long* blocks) {
+  VqAssign p;
+  const char* why = vq_assign_plan(N, D, K, sel != nullptr, dist != nullptr, split_on(), &p);
+  VQN_CHECK_SHAPE_IN(fn, why == nullptr, why);
+  *blocks = here(p.grid);
+  if (FUSE) {
+    VQN_CHECK_SHAPE_IN(fn, *blocks + 1 <= VQN_QUANT_WS_FLOATS, "workspace too small for this device");
+    VQN_CHECK_SHAPE_IN(fn, aligned16(fuse.xnorm), "xnorm must be 16-byte aligned");
+  }
+  const dim3 grid((unsigned)*blocks);
+  if (p.split)
+    return vqn_pick<2, 4>(fn, p.KTp, [&](auto kt) {
+      return vqn_launch(fn, vq_assign_split_kernel<decltype(kt)::value, FUSE>, grid, p.threads, p.lds, s, x, N, D, C, K, idx, quant, fuse);
+    });
+  int* gmax_key = reinterpret_cast<int*>(ws);
+  return vqn_pick<1, 2, 4, 8>(fn, p.KTp, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (sel != nullptr) {
+      // distances.max() is taken over the UNMASKED distances (vq_layers.py:285) -> extra pass
+      VQN_HIP_IN(fn, hipMemsetD32Async((hipDeviceptr_t)ws, (int)0x807fffff /* key(-inf) */, 1, (hipStream_t)s));
+      const int rc = vqn_launch(fn, vq_assign_kernel<KT, true, FUSE>, grid, p.threads, p.lds, s, x, N, D, C, K, sel, gmax_key, idx, quant, dist, fuse);
+      if (rc != VQN_OK) return rc;
+    }
+    return vqn_launch(fn, vq_assign_kernel<KT, false, FUSE>, grid, p.threads, p.lds, s, x, N, D, C, K, sel, gmax_key, idx, quant, dist, fuse);
+  });
+}
+
 int vqn_internal_finish_loss(const float* part, int n, float scale, float* loss, hipStream_t s) {
-  hipLaunchKernelGGL(vq_ste_loss_final_kernel, dim3(1), dim3(64), 0, s, part, n, scale, loss, 1.0f);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, vq_ste_loss_final_kernel, dim3(1), 64, 0, s, part, n, scale, loss, 1.0f);
 }
 
 extern "C" int vqn_vq_codebook_frags(const float* codebook, int D, int K, float* frags, void* stream) {
   VQN_CHECK_ARG(codebook && frags, "codebook and frags must be non-null");
   VQN_CHECK_SHAPE(D == 256 && K >= 1 && K <= 64, "D = 256, K <= 64");
-  hipLaunchKernelGGL(vq_codebook_frags_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, codebook, D, K, K <= 16 ? 1 : (K <= 32 ? 2 : 4), frags);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, vq_codebook_frags_kernel, dim3(1), 256, 0, stream, codebook, D, K, K <= 16 ? 1 : (K <= 32 ? 2 : 4), frags);
 }
 
 extern "C" int vqn_vq_assign_variant(int D, int K, int has_sel_mask, int has_dist) {
-  static const float one = 1.f;
-  return split_ok(K, D, has_sel_mask ? &one : nullptr, has_dist ? &one : nullptr) ? 1 : 0;
+  return vq_split_ok(D, K, has_sel_mask != 0, has_dist != 0, split_on()) ? 1 : 0;
 }
 
 extern "C" int vqn_vq_assign(const float* x, int64_t N, int D, const float* codebook, int K, const float* sel_mask,
@@ -1082,34 +1043,18 @@ extern "C" int vqn_vq_assign(const float* x, int64_t N, int D, const float* code
   VQN_CHECK_ARG(x && codebook && idx, "x, codebook and idx must be non-null");
   VQN_CHECK_ARG(sel_mask == nullptr || ws != nullptr, "sel_mask needs a 4-byte device workspace `ws`");
   VQN_CHECK_SHAPE(D % 4 == 0, "D must be a multiple of 4 (16-byte rows)");
-  VQN_CHECK_SHAPE(((uintptr_t)x % 16) == 0 && (quant == nullptr || ((uintptr_t)quant % 16) == 0), "x/quant must be 16-byte aligned");
-  const int KT = (K + 15) / 16;
-  const int D16 = (D + 15) / 16;
-  VQN_CHECK_SHAPE(KT <= 8, "K <= 128");
-  int KTp = KT <= 1 ? 1 : KT <= 2 ? 2 : KT <= 4 ? 4 : 8;
-  VQN_CHECK_SHAPE(((size_t)KTp * D16 * 256 + 3 * KTp * 16 + 4) * 4 <= 160 * 1024, "codebook does not fit in 160 KB of LDS");
-  hipStream_t s = (hipStream_t)stream;
-  long long* idx_ll = reinterpret_cast<long long*>(idx);
-  const VqFuse nf = {0.f, nullptr, nullptr, nullptr};
-  if (split_ok(K, D, sel_mask, dist))
-    return KTp == 2 ? launch_split<2, false>(x, N, D, codebook, K, idx_ll, quant, nf, s)
-                    : launch_split<4, false>(x, N, D, codebook, K, idx_ll, quant, nf, s);
-  switch (KTp) {
-    case 1: return launch_assign<1, false>(x, N, D, codebook, K, sel_mask, ws, idx_ll, quant, dist, nf, s);
-    case 2: return launch_assign<2, false>(x, N, D, codebook, K, sel_mask, ws, idx_ll, quant, dist, nf, s);
-    case 4: return launch_assign<4, false>(x, N, D, codebook, K, sel_mask, ws, idx_ll, quant, dist, nf, s);
-    default: return launch_assign<8, false>(x, N, D, codebook, K, sel_mask, ws, idx_ll, quant, dist, nf, s);
-  }
+  VQN_CHECK_SHAPE(aligned16(x) && aligned16(quant), "x/quant must be 16-byte aligned");
+  long blocks;
+  return assign_rows<false>(__func__, x, N, D, codebook, K, sel_mask, ws, reinterpret_cast<long long*>(idx), quant, dist,
+                            VqFuse{0.f, nullptr, nullptr, nullptr}, stream, &blocks);
 }
 
 extern "C" int vqn_l2_normalize_rows(const float* x, int64_t N, int D, float eps, float* y, void* stream) {
   VQN_CHECK_ARG(N >= 0 && D > 0, "N >= 0, D > 0 required");
   if (N == 0) return VQN_OK;
   VQN_CHECK_ARG(x && y, "x and y must be non-null");
-  VQN_CHECK_SHAPE(D % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0, "D multiple of 4, x / y 16-byte aligned");
-  hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3((unsigned)assign_grid(N)), dim3(256), 0, (hipStream_t)stream, x, (long)N, D, eps, y);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  VQN_CHECK_SHAPE(D % 4 == 0 && aligned16(x) && aligned16(y), "D multiple of 4, x / y 16-byte aligned");
+  return vqn_launch(__func__, l2_normalize_rows_kernel, dim3((unsigned)here(vq_normalize_grid(N))), 256, 0, stream, x, (long)N, D, eps, y);
 }
 
 static int quantize_rows_impl(const float* z, int64_t N, int D, const float* codebook, int K, const float* sel_mask, float eps,
@@ -1125,31 +1070,12 @@ static int quantize_rows_impl(const float* z, int64_t N, int D, const float* cod
   }
   VQN_CHECK_ARG(z && codebook && idx, "z, codebook and idx must be non-null");
   VQN_CHECK_SHAPE(D % 4 == 0 && D <= 256, "D must be a multiple of 4 and <= 256 (the row stays in registers)");
-  VQN_CHECK_SHAPE(((uintptr_t)z % 16) == 0 && (ste == nullptr || ((uintptr_t)ste % 16) == 0), "z / ste must be 16-byte aligned");
-  const int KT = (K + 15) / 16;
-  const int D16 = (D + 15) / 16;
-  VQN_CHECK_SHAPE(KT <= 8, "K <= 128");
-  int KTp = KT <= 1 ? 1 : KT <= 2 ? 2 : KT <= 4 ? 4 : 8;
-  VQN_CHECK_SHAPE(((size_t)KTp * D16 * 256 + 3 * KTp * 16 + 4) * 4 <= 160 * 1024, "codebook does not fit in 160 KB of LDS");
-  long long* idx_ll = reinterpret_cast<long long*>(idx);
-  const bool split = split_ok(K, D, sel_mask, nullptr);
-  const long blocks = split ? split_grid(N) : assign_grid(N);
-  VQN_CHECK_SHAPE(blocks + 1 <= VQN_QUANT_WS_FLOATS, "workspace too small for this device");
-  VQN_CHECK_SHAPE(xnorm == nullptr || ((uintptr_t)xnorm % 16) == 0, "xnorm must be 16-byte aligned");
+  VQN_CHECK_SHAPE(aligned16(z) && aligned16(ste), "z / ste must be 16-byte aligned");
+  long blocks;
   const VqFuse fz = {eps, ws + 1, counts, xnorm};      // ws[0]: the code-dropout maximum; ws[1 ..]: per-workgroup loss sums
-  int rc;
-  if (split)
-    rc = KTp == 2 ? launch_split<2, true>(z, N, D, codebook, K, idx_ll, ste, fz, s) : launch_split<4, true>(z, N, D, codebook, K, idx_ll, ste, fz, s);
-  else switch (KTp) {
-    case 1: rc = launch_assign<1, true>(z, N, D, codebook, K, sel_mask, ws, idx_ll, ste, nullptr, fz, s); break;
-    case 2: rc = launch_assign<2, true>(z, N, D, codebook, K, sel_mask, ws, idx_ll, ste, nullptr, fz, s); break;
-    case 4: rc = launch_assign<4, true>(z, N, D, codebook, K, sel_mask, ws, idx_ll, ste, nullptr, fz, s); break;
-    default: rc = launch_assign<8, true>(z, N, D, codebook, K, sel_mask, ws, idx_ll, ste, nullptr, fz, s); break;
-  }
+  const int rc = assign_rows<true>(__func__, z, N, D, codebook, K, sel_mask, ws, reinterpret_cast<long long*>(idx), ste, nullptr, fz, stream, &blocks);
   if (rc != VQN_OK) return rc;
-  hipLaunchKernelGGL(vq_ste_loss_final_kernel, dim3(1), dim3(64), 0, s, ws + 1, (int)blocks, loss_scale, loss, loss_post);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  return vqn_launch(__func__, vq_ste_loss_final_kernel, dim3(1), 64, 0, stream, ws + 1, (int)blocks, loss_scale, loss, loss_post);
 }
 
 extern "C" int vqn_vq_quantize_rows(const float* z, int64_t N, int D, const float* codebook, int K, const float* sel_mask, float eps,
@@ -1166,13 +1092,10 @@ extern "C" int vqn_vq_quantize_rows_train(const float* z, int64_t N, int D, cons
   return quantize_rows_impl(z, N, D, codebook, K, sel_mask, eps, loss_scale, ws, idx, ste, loss, counts, xnorm, stream, loss_post);
 }
 
+// 0: the single-pass (LDS-atomic) form is used
 extern "C" int64_t vqn_vq_ema_stats_ws_bytes(int64_t N, int D, int K) {
-  if (N > 0 && ema_mfma_ok(D, K)) {
-    const int KP = 16 * ema_mfma_kt(K);
-    return ema_mfma_grid(N, K) * ((int64_t)KP * D + KP) * (int64_t)sizeof(float);
-  }
-  if (N <= 0 || D <= 0 || K <= 0 || (long)K * D > 4096 || (D & 3)) return 0;       // 0: the single-pass (LDS-atomic) form is used
-  return ema_grid(N, D, K) * 4 * (int64_t)(K * D + K) * (int64_t)sizeof(float);
+  const VqEma e = vq_ema_plan(N, D, K, true);
+  return here(e.grid) * e.ws_per_wg;
 }
 
 extern "C" int vqn_vq_ema_stats(const float* x, const int64_t* idx, int64_t N, int D, int K, float* counts, float* dw,
@@ -1180,94 +1103,54 @@ extern "C" int vqn_vq_ema_stats(const float* x, const int64_t* idx, int64_t N, i
   VQN_CHECK_ARG(N >= 0 && D > 0 && K > 0, "N >= 0, D > 0, K > 0 required");
   VQN_CHECK_ARG(counts, "counts must be non-null");
   hipStream_t s = (hipStream_t)stream;
-  if (dw == nullptr) {                                  /* counts only */
+  VqEma e = vq_ema_plan(N, D, K, dw != nullptr);
+  if (e.ws_per_wg > 0 && !(ws != nullptr && ws_bytes >= here(e.grid) * e.ws_per_wg)) e = vq_ema_atomic(N, D, K);
+  if (e.ws_per_wg == 0) {                               /* counts only and the single pass accumulate into their outputs */
     VQN_HIP(hipMemsetAsync(counts, 0, sizeof(float) * K, s));
+    if (dw != nullptr) VQN_HIP(hipMemsetAsync(dw, 0, sizeof(float) * (size_t)D * K, s));
     if (N == 0) return VQN_OK;
+  }
+  const long long* il = reinterpret_cast<const long long*>(idx);
+  const long blocks = here(e.grid);
+  const dim3 grid((unsigned)blocks);
+  if (e.form == VQ_EMA_COUNTS) {
     VQN_CHECK_ARG(idx, "idx must be non-null");
-    long blocks = (N + 4095) / 4096;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(vq_counts_kernel, dim3((unsigned)blocks), dim3(256), sizeof(int) * K, s,
-                       reinterpret_cast<const long long*>(idx), (long)N, K, counts);
-    VQN_LAUNCH_CHECK();
-    return VQN_OK;
+    return vqn_launch(__func__, vq_counts_kernel, grid, 256, e.lds, stream, il, (long)N, K, counts);
   }
-  const int64_t need = vqn_vq_ema_stats_ws_bytes(N, D, K);
-  if (N > 0 && need > 0 && ws != nullptr && ws_bytes >= need && ema_mfma_ok(D, K)) {
-    VQN_CHECK_ARG(x && idx, "x and idx must be non-null");
-    VQN_CHECK_SHAPE(((uintptr_t)x % 16) == 0, "x must be 16-byte aligned");
-    const int KT = ema_mfma_kt(K), KP = 16 * KT, DJ = D / 64;
-    const long blocks = ema_mfma_grid(N, K);
-    const size_t lds = ((size_t)KP * (D + 1) + KP) * sizeof(float);
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-    const long long* il = reinterpret_cast<const long long*>(idx);
-#define VQN_EMA_LAUNCH(KT_, RU_)                                                                                              \
-    do {                                                                                                                      \
-      if (lds > 64 * 1024)                                                                                                    \
-        VQN_HIP(hipFuncSetAttribute((const void*)vq_ema_mfma_kernel<KT_, RU_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      hipLaunchKernelGGL((vq_ema_mfma_kernel<KT_, RU_>), dim3((unsigned)blocks), dim3(256), lds, s, x4, il, (long)N, DJ, ws);  \
-    } while (0)
-    if (KT == 1) VQN_EMA_LAUNCH(1, 8);
-    else if (KT == 2) VQN_EMA_LAUNCH(2, 4);
-    else VQN_EMA_LAUNCH(4, 4);
-#undef VQN_EMA_LAUNCH
-    VQN_LAUNCH_CHECK();
-    const int tot = K * D + K;
-    hipLaunchKernelGGL(vq_ema_reduce2_kernel, dim3((tot + 15) / 16), dim3(256), 0, s, ws, (int)blocks, D, K, KP, counts, dw);
-    VQN_LAUNCH_CHECK();
-    return VQN_OK;
-  }
-  if (N > 0 && need > 0 && ws != nullptr && ws_bytes >= need) {
-    VQN_CHECK_ARG(x && idx, "x and idx must be non-null");
-    VQN_CHECK_SHAPE(((uintptr_t)x % 16) == 0, "x must be 16-byte aligned");
-    const long blocks = ema_grid(N, D, K);
-    const size_t lds = (size_t)4 * (K * D + K) * sizeof(float);
-    if (lds > 64 * 1024)
-      VQN_HIP(hipFuncSetAttribute((const void*)vq_ema_partial_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(vq_ema_partial_kernel<8>, dim3((unsigned)blocks), dim3(256), lds, s, x,
-                       reinterpret_cast<const long long*>(idx), (long)N, D, K, ws);
-    VQN_LAUNCH_CHECK();
-    const int tot = K * D + K;
-    hipLaunchKernelGGL(vq_ema_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, ws, blocks * 4, D, K, counts, dw);
-    VQN_LAUNCH_CHECK();
-    return VQN_OK;
-  }
-  VQN_HIP(hipMemsetAsync(counts, 0, sizeof(float) * K, s));
-  VQN_HIP(hipMemsetAsync(dw, 0, sizeof(float) * (size_t)D * K, s));
-  if (N == 0) return VQN_OK;
   VQN_CHECK_ARG(x && idx, "x and idx must be non-null");
-  VQN_CHECK_SHAPE(D % 4 == 0 && ((uintptr_t)x % 16) == 0, "D multiple of 4 and x 16-byte aligned");
-  const size_t lds = ((size_t)K * D + K) * sizeof(float);
-  VQN_CHECK_SHAPE(lds <= 160 * 1024, "K*D accumulators do not fit in 160 KB of LDS");
-  if (lds > 64 * 1024)
-    VQN_HIP(hipFuncSetAttribute((const void*)vq_ema_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  long blocks = (N + 63) / 64;                        // >= 16 rows per wave
-  const long cap = (long)vqn_num_cus() * 4;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(vq_ema_stats_kernel, dim3((unsigned)blocks), dim3(256), lds, s, x,
-                     reinterpret_cast<const long long*>(idx), (long)N, D, K, counts, dw);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  if (e.form == VQ_EMA_ATOMIC) {
+    VQN_CHECK_SHAPE(D % 4 == 0 && aligned16(x), "D multiple of 4 and x 16-byte aligned");
+    VQN_CHECK_SHAPE(e.lds <= VQ_LDS_MAX, "K*D accumulators do not fit in 160 KB of LDS");
+    return vqn_launch(__func__, vq_ema_stats_kernel, grid, 256, e.lds, stream, x, il, (long)N, D, K, counts, dw);
+  }
+  VQN_CHECK_SHAPE(aligned16(x), "x must be 16-byte aligned");
+  const int tot = K * D + K;
+  if (e.form == VQ_EMA_MFMA) {
+    const int rc = vqn_pick<1, 2, 4>(__func__, e.KT, [&](auto kt) {
+      constexpr int KT = decltype(kt)::value;
+      return vqn_launch("vqn_vq_ema_stats", vq_ema_mfma_kernel<KT, KT == 1 ? 8 : 4>, grid, 256, e.lds, stream, reinterpret_cast<const f32x4*>(x), il,
+                        (long)N, D / 64, ws);
+    });
+    if (rc != VQN_OK) return rc;
+    return vqn_launch(__func__, vq_ema_reduce2_kernel, dim3((tot + 15) / 16), 256, 0, stream, ws, (int)blocks, D, K, 16 * e.KT, counts, dw);
+  }
+  const int rc = vqn_launch(__func__, vq_ema_partial_kernel<8>, grid, 256, e.lds, stream, x, il, (long)N, D, K, ws);
+  if (rc != VQN_OK) return rc;
+  return vqn_launch(__func__, vq_ema_reduce_kernel, dim3((tot + 255) / 256), 256, 0, stream, ws, blocks * 4, D, K, counts, dw);
 }
 
 extern "C" int vqn_vq_ste_loss(const float* x, const float* quant, int64_t numel, float scale, float* ste, float* loss,
                                float* ws, void* stream) {
   VQN_CHECK_ARG(numel >= 0 && loss && ws, "numel >= 0, loss and ws (VQN_STE_WS_FLOATS floats) must be non-null");
-  hipStream_t s = (hipStream_t)stream;
   if (numel == 0) {                                     /* mean over nothing: the reference yields NaN (0 / 0) */
-    VQN_HIP(hipMemsetD32Async((hipDeviceptr_t)loss, 0x7fc00000, 1, s));     // quiet NaN, written on the device (capturable)
+    VQN_HIP(hipMemsetD32Async((hipDeviceptr_t)loss, 0x7fc00000, 1, (hipStream_t)stream));     // quiet NaN, written on the device (capturable)
     return VQN_OK;
   }
   VQN_CHECK_ARG(x && quant, "x and quant must be non-null");
-  VQN_CHECK_SHAPE((numel & 3) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)quant % 16) == 0 && (ste == nullptr || ((uintptr_t)ste % 16) == 0),
-                  "numel multiple of 4 and 16-byte aligned tensors");
-  const long n4 = numel / 4;
-  long blocks = (n4 + 1023) / 1024;
-  if (blocks > 1024) blocks = 1024;                     /* = VQN_STE_WS_FLOATS */
-  hipLaunchKernelGGL(vq_ste_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const f32x4*>(x),
-                     reinterpret_cast<const f32x4*>(quant), n4, reinterpret_cast<f32x4*>(ste), ws);
-  VQN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(vq_ste_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, (int)blocks, scale, loss, 1.0f);
-  VQN_LAUNCH_CHECK();
-  return VQN_OK;
+  VQN_CHECK_SHAPE((numel & 3) == 0 && aligned16(x) && aligned16(quant) && aligned16(ste), "numel multiple of 4 and 16-byte aligned tensors");
+  const long n4 = numel / 4, blocks = vq_ste_grid(n4);
+  const int rc = vqn_launch(__func__, vq_ste_loss_kernel, dim3((unsigned)blocks), 256, 0, stream, reinterpret_cast<const f32x4*>(x),
+                            reinterpret_cast<const f32x4*>(quant), n4, reinterpret_cast<f32x4*>(ste), ws);
+  if (rc != VQN_OK) return rc;
+  return vqn_launch(__func__, vq_ste_loss_final_kernel, dim3(1), 64, 0, stream, ws, (int)blocks, scale, loss, 1.0f);
 }
