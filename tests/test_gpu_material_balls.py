@@ -1,0 +1,376 @@
+"""GPU: the material-ball kernel (csrc/material_balls.hip, vqn_material_balls) against the float64 model of
+tests/material_balls_model.py, its 8-bit and sheet outputs against the project's device conversion, its refusals, and the layers above
+it: Model.material_rows / material_balls of vq_nfr and ref_nfr, the scene driver decomp/materials.py and decomp/edit.run(preview=True).
+
+The float bound.  The yardstick is the existing shading kernel: the foreground samples of the case YARDSTICK are materialised (xyz,
+normal, camera as ray origin, no visibility row) and shaded by vqn_brdf_shade_fwd with the same materials and probes; its largest
+absolute error against the float64 model, and the new kernel's on the same samples, are recorded in
+profiles/observed_errors_material_balls.json.  The new kernel may err at most twice the shading kernel's recorded figure (the project's
+convention for observed-error bounds; it allows for another summation order).  The yardstick case uses materials of roughness >= 0.2:
+under a mirror-like lobe (roughness 1e-3: alpha^2 = 1e-12) the lobe's argument 1 - (h.n)^2 (1 - alpha^2) is a difference of nearly
+equal f32 numbers wherever a half vector comes within ~0.03 rad of the normal, and what any f32 kernel returns there is decided by the
+last bit of (h.n)^2, not by its arithmetic.  For such materials the float comparison is made on the pixels none of whose samples has
+a front-lit light with 1 - (h.n)^2 < T_FLOOR = 1e-3: there the cancellation costs at most 2^-23 / 1e-3 ~ 1e-4 relative on a lobe
+value D <= alpha^2 / (pi T_FLOOR^2) = 3e-7, far below the bound; on the other pixels the output is only required to lie in [0, 1].
+Every other assertion (mask, background, bytes, sheet) holds on all pixels of all cases."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import material_balls_model as mb
+from tests.gpu_util import launches, record_observed
+from vqnerf_release_amd import _C
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PROFILE = os.path.join(ROOT, 'profiles', 'observed_errors_material_balls.json')
+ENTRY = 'vqn_material_balls'
+T_FLOOR = 1e-3
+ROT = [[0.0, 0.6, 0.8], [1.0, 0.0, 0.0], [0.0, 0.8, -0.6]]       # a rotation other than the default camera's
+
+
+def _bound():
+    with open(PROFILE) as f:
+        return 2.0 * json.load(f)['shade_kernel_max_abs_err']
+
+
+def _materials(kind, M, seed=0):
+    rng = np.random.default_rng(seed)
+    if kind == 'grid':                                           # rough x f0, a fixed albedo
+        rows = [[0.6, 0.4, 0.2, f, f, f, r] for r in (1e-3, 0.3, 1.0) for f in (0.0, 0.04, 1.0)]
+        return np.array(rows[:M], np.float32)
+    mats = rng.uniform(0.0, 1.0, (M, 7))
+    mats[:, 6] = 0.2 + 0.8 * mats[:, 6]                          # roughness in [0.2, 1]: see the module text
+    return mats.astype(np.float32)
+
+
+def _probes(names, hw, seed=1):
+    rng = np.random.default_rng(seed)
+    out = []
+    for n in names:
+        if n == 'hdr':                                           # HDR-like: most of the sky dim, a few pixels up to 50
+            out.append(50.0 * rng.uniform(0.0, 1.0, hw + (3,)) ** 6)
+        else:
+            out.append(np.ones(hw + (3,)) if n == 'white' else mb.load_light(n, hw[0]))
+    return np.stack(out).reshape(len(names), -1, 3).astype(np.float32)
+
+
+# name: ims, spp, M, materials, probes, light grid (8 x 16 = 128, 16 x 32 = 512, 16 x 64 = 1024 lights), white_bg, cam_rot, gamma
+CASES = {
+    'one_pixel': (1, 1, 1, 'random', ['white'], (8, 16), True, None, None),
+    'rim_black': (8, 4, 3, 'grid', ['white', 'point'], (8, 16), False, None, None),
+    'grid_33': (33, 9, 9, 'grid', ['white', 'hdr'], (8, 16), True, None, None),
+    'yardstick': (33, 1, 64, 'random', ['white', 'point', 'hdr'], (16, 32), True, ROT, None),
+    'gamma_65_24': (8, 9, 65, 'random', ['hdr'] * 22 + ['white', 'point'], (8, 16), False, ROT, (1.7, 0.8)),
+    'seventeen_1024': (8, 4, 3, 'random', ['hdr'] * 16 + ['white'], (16, 64), True, None, (0.5, 1.0 / 2.2)),
+}
+YARDSTICK = 'yardstick'
+_cache = {}
+
+
+def _case(name):
+    """inputs, the kernel's three outputs and the model's image of a case, computed once"""
+    if name in _cache:
+        return _cache[name]
+    ims, spp, M, kind, probe_names, hw, white_bg, rot, gamma = CASES[name]
+    lxyz, areas = mb.gen_light_xyz(*hw)
+    lxyz, areas = lxyz.reshape(-1, 3).astype(np.float32), areas.reshape(-1).astype(np.float32)
+    mats = _materials(kind, M, seed=len(name))
+    probes = _probes(probe_names, hw)
+    dev = lambda a: torch.tensor(a, device='cuda')
+    order = list(np.random.default_rng(2).permutation(M)[:max(1, M - 1)])
+    rows, cols = (len(order) + 3) // 4 + 1, 4                    # at least one empty row of cells
+    with launches() as rec:
+        got = _C.material_balls(dev(mats), dev(probes), dev(lxyz), dev(areas), ims, spp, cam_rot=rot, white_bg=white_bg, gamma=gamma,
+                                want_f32=True, want_u8=True, sheet=(order, rows, cols))
+    assert rec.counts[ENTRY] == 1
+    want, t_min = mb.render(mats, probes, lxyz, areas, ims, spp, cam_rot=rot, white_bg=white_bg, gamma=gamma, details=True)
+    _cache[name] = dict(mats=mats, probes=probes, lxyz=lxyz, areas=areas, got=got, want=want, t_min=t_min, order=order, rows=rows, cols=cols)
+    return _cache[name]
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_float_output_against_the_model(name):
+    c = _case(name)
+    ims, spp, M = CASES[name][:3]
+    got = c['got']['f32'].cpu().numpy().astype(np.float64)
+    assert got.shape == c['want'].shape == (M, c['probes'].shape[0], ims, ims, 3)
+    assert np.all(got >= 0.0) and np.all(got <= 1.0)
+    bound = _bound()
+    worst = 0.0
+    for m in range(M):
+        ok = np.ones((ims, ims), bool) if c['mats'][m, 6] >= 0.2 else c['t_min'] >= T_FLOOR
+        err = np.abs(got[m] - c['want'][m])[:, ok]
+        worst = max(worst, float(err.max()) if err.size else 0.0)
+    record_observed('material_balls', name, worst, bound)
+    assert worst <= bound
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_background_pixels_are_exact(name):
+    c = _case(name)
+    ims, spp = CASES[name][:2]
+    bg = 1.0 if CASES[name][6] else 0.0
+    empty = mb.pixel_fg_count(ims, spp) == 0
+    got = c['got']['f32'].cpu().numpy()
+    assert np.all(got[:, :, empty] == np.float32(bg))
+    if ims >= 8:
+        assert empty.any() and not empty.all()
+
+
+@pytest.mark.parametrize('ims,spp', [(1, 1), (8, 4), (33, 1), (33, 9), (8, 16)])
+def test_foreground_mask_is_the_models(ims, spp):
+    # a light so strong that every foreground sample clips to exactly 1, on a black background: a pixel's value is then the number of
+    # its foreground samples times the f32 1 / spp, whatever the shading arithmetic does
+    lxyz, areas = mb.gen_light_xyz(8, 16)
+    dev = lambda a: torch.tensor(np.asarray(a, np.float32), device='cuda')
+    mats = dev([[1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 1.0]])
+    got = _C.material_balls(mats, dev(np.full((1, 128, 3), 1e6)), dev(lxyz.reshape(-1, 3)), dev(areas.reshape(-1)), ims, spp,
+                            white_bg=False)['f32'].cpu().numpy()
+    count = mb.pixel_fg_count(ims, spp).astype(np.float32)
+    want = count * (np.float32(1) / np.float32(spp))
+    assert np.array_equal(got[0, 0], np.repeat(want[..., None], 3, -1))
+    if ims >= 8 and spp > 1:
+        assert ((count > 0) & (count < spp)).any()               # a pixel straddles the rim
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_bytes_and_sheet(name):
+    c = _case(name)
+    f32, u8, sheet = c['got']['f32'], c['got']['u8'], c['got']['sheet']
+    want_u8 = (torch.clamp(_C.linear2srgb(f32), 0.0, 1.0) * 255.0).to(torch.uint8)       # the conversion of vis._device_images
+    assert torch.equal(u8, want_u8)
+    want_sheet = mb.sheet(u8.cpu().numpy(), c['order'], c['rows'], c['cols'], white_bg=CASES[name][6])
+    assert np.array_equal(sheet.cpu().numpy(), want_sheet)
+    # the bytes are also the model's transfer of the kernel's floats, up to the last place of the device's powf
+    model_u8 = (np.clip(mb.linear2srgb(f32.cpu().numpy()), 0, 1) * np.float32(255)).astype(np.uint8)
+    assert np.abs(model_u8.astype(int) - u8.cpu().numpy().astype(int)).max() <= 1
+
+
+def test_outputs_do_not_depend_on_which_are_asked_for():
+    c = _case('rim_black')
+    ims, spp = CASES['rim_black'][:2]
+    dev = lambda a: torch.tensor(a, device='cuda')
+    args = (dev(c['mats']), dev(c['probes']), dev(c['lxyz']), dev(c['areas']), ims, spp)
+    only_u8 = _C.material_balls(*args, white_bg=False, want_f32=False, want_u8=True)
+    assert only_u8['f32'] is None and only_u8['sheet'] is None and torch.equal(only_u8['u8'], c['got']['u8'])
+    only_sheet = _C.material_balls(*args, white_bg=False, want_f32=False, sheet=(c['order'], c['rows'], c['cols']))
+    assert only_sheet['u8'] is None and torch.equal(only_sheet['sheet'], c['got']['sheet'])
+
+
+def test_yardstick_the_shading_kernel_on_the_same_samples():
+    """Both kernels' largest absolute error against the float64 model on the foreground samples of the case YARDSTICK (spp = 1: a
+    pixel is one sample, so the images ARE the per-sample values)."""
+    c = _case(YARDSTICK)
+    ims, spp, M = CASES[YARDSTICK][:3]
+    assert spp == 1
+    P = c['probes'].shape[0]
+    fg, xyz, normal, cam = mb.geometry(ims, spp, cam_rot=CASES[YARDSTICK][7])
+    S = xyz.shape[0]
+    assert S > 400
+    want = c['want'][:, :, fg]                                                                            # [M, P, S, 3]
+    dev = lambda a: torch.tensor(np.ascontiguousarray(a, np.float32), device='cuda')
+    rep = lambda a: dev(np.repeat(a[None], M, 0).reshape(M * S, -1))                                      # material-major rows
+    mat_rows = np.repeat(c['mats'][:, None], S, 1).reshape(M * S, 7)
+    with launches() as rec:
+        out = _C.brdf_shade_fwd(rep(xyz), rep(normal), rep(np.broadcast_to(cam, xyz.shape)), None, dev(c['lxyz']), dev(c['areas']),
+                                dev(c['probes'][0]), [(dev(mat_rows[:, :3]), dev(mat_rows[:, 3:6]), dev(mat_rows[:, 6:7]))],
+                                want_normal=False, probes=dev(c['probes']))
+    assert rec.counts['vqn_brdf_shade_fwd'] == 1
+    shade = out['rgb_probes'].cpu().numpy().astype(np.float64).reshape(M, S, P, 3).transpose(0, 2, 1, 3)
+    shade_err = float(np.abs(shade - want).max())
+    balls_err = float(np.abs(c['got']['f32'].cpu().numpy().astype(np.float64)[:, :, fg] - want).max())
+    with open(PROFILE) as f:
+        prof = json.load(f)
+    record_observed('material_balls_yardstick', 'shade_kernel', shade_err, prof['shade_kernel_max_abs_err'])
+    record_observed('material_balls_yardstick', 'material_balls', balls_err, 2.0 * prof['shade_kernel_max_abs_err'])
+    assert balls_err <= 2.0 * prof['shade_kernel_max_abs_err']
+    assert shade_err <= 2.0 * prof['shade_kernel_max_abs_err']   # the recorded figure still describes the yardstick
+
+
+def _canaries(M, P, ims, rows, cols):
+    return (torch.full((max(M, 1), P, max(ims, 1), max(ims, 1), 3), 7.5, device='cuda'),
+            torch.full((max(M, 1), P, max(ims, 1), max(ims, 1), 3), 77, dtype=torch.uint8, device='cuda'),
+            torch.full((P, max(rows, 1) * max(ims, 1), max(cols, 1) * max(ims, 1), 3), 77, dtype=torch.uint8, device='cuda'))
+
+
+@pytest.mark.parametrize('what,code,word', [
+    ('M0', -2, 'materials'), ('M66', -2, 'materials'), ('P25', -2, 'probes'), ('L96', -2, 'multiple of 64'), ('spp2', -2, 'square'),
+    ('ims0', -2, 'ims'), ('no_output', -1, 'no output'), ('few_cells', -1, 'does not hold')])
+def test_refusals_leave_the_outputs_alone(what, code, word):
+    M, P, L, ims, spp, rows, cols = 4, 2, 128, 8, 4, 2, 2
+    if what == 'M0':
+        M = 0
+    if what == 'M66':
+        M, rows, cols = 66, 9, 9
+    if what == 'P25':
+        P = 25
+    if what == 'L96':
+        L = 96
+    if what == 'spp2':
+        spp = 2
+    if what == 'ims0':
+        ims = 0
+    if what == 'few_cells':
+        rows, cols = 1, 3
+    out = _canaries(M, min(P, 24), ims, rows, cols)
+    before = [t.clone() for t in out]
+    if what == 'no_output':
+        out = (None, None, None)
+    rng = np.random.default_rng(0)
+    dev = lambda *s: torch.tensor(rng.uniform(0.1, 1, s).astype(np.float32), device='cuda')
+    with pytest.raises(_C.VqnError) as e:
+        _C.material_balls(dev(M, 7), dev(P, L, 3), dev(L, 3), dev(L), ims, spp, sheet=(None, rows, cols), out=out)
+    assert f'rc={code}' in str(e.value) and word in str(e.value) and ENTRY in str(e.value)
+    torch.cuda.synchronize()
+    for t, b in zip(_canaries(M, min(P, 24), ims, rows, cols) if what == 'no_output' else out, before):
+        assert torch.equal(t, b)
+
+
+# ---- the models and the drivers ----------------------------------------------------------------------------------------------------
+H, W, BG = 6, 5, 6                                               # the 6 x 5 views of tests/test_gpu_material_edit.py: every 6th row is background
+K = 8
+
+
+@pytest.fixture(scope='module')
+def vq():
+    from tests.test_gpu_material_edit import _probes as set_probes, _with_hw
+    from tests.test_gpu_vq_entrypoints import _build, _points
+    od, pt, specs, model, gamma, lxyz, lareas = _build('nerf', K)
+    set_probes(model)
+    views = [_with_hw(_points(od, 'nerf', H * W, seed)[1]) for seed in (6, 7)]
+    return model, views
+
+
+@pytest.fixture(scope='module')
+def ref(vq):
+    from tests.test_gpu_decomp import _ref_setup
+    from tests.test_gpu_material_edit import _probes as set_probes
+    model = _ref_setup('hw')[4]                                  # a data type with a gamma pair
+    set_probes(model, 1)
+    model.__dict__['_stage2'] = vq[0]                            # what load_stage2 attaches
+    return model
+
+
+def test_material_rows_equal_the_vq_branch_bit_for_bit(vq):
+    """The VQ branch of this repository's vq_nfr lives in `call` (its fast_render renders the continuous branch only): the points'
+    encoder output is forced onto the codes, and pred['vq_albedo' | 'vq_spec' | 'vq_rough'] of a point on code k must be row k."""
+    model, views = vq
+    rows = model.material_rows()
+    assert rows.shape == (K, 7) and rows.dtype == torch.float32 and rows.is_cuda
+    batch = views[0]
+    fg = batch[5][:, 0] > 0
+    pick = torch.arange(int(fg.sum()), device='cuda') % K
+    Z = model.get_codebook().detach().t().contiguous()[pick].contiguous()
+    front = model.fuse_front
+    model.fuse_front = False
+    model.enc_and_heads = lambda pts, suffix: (Z,) + tuple(model._all_heads(Z, suffix))
+    try:
+        with torch.no_grad():
+            pred = model.call(batch, mode='test')[0]
+    finally:
+        del model.enc_and_heads
+        model.fuse_front = front
+    assert torch.equal(pred['embed'][fg][:, 0].to(torch.int64) - 1, pick)
+    got = torch.cat([pred['vq_albedo'][fg], pred['vq_spec'][fg].expand(-1, 3), pred['vq_rough'][fg]], -1)
+    assert torch.equal(got, rows[pick])
+    assert len(torch.unique(rows, dim=0)) == K                   # the codes do differ
+
+
+def test_material_balls_light_first_then_the_probes(vq, ref):
+    model, _ = vq
+    with launches() as rec:
+        out = model.material_balls(probes=True, ims=8, spp=4)
+    assert rec.counts[ENTRY] == 1
+    assert out['names'] == ['light', 'probe0', 'probe1']
+    assert out['f32'].shape == (K, 3, 8, 8, 3) and out['u8'].shape == (K, 3, 8, 8, 3) and out['sheet'] is None
+    rows = model.material_rows()
+    geom = (model.lxyz.reshape(-1, 3).contiguous(), model.lareas.reshape(-1).contiguous())
+    for i, light in enumerate([model.light.detach()] + list(model.novel_probes.values())):
+        one = _C.material_balls(rows, light.reshape(1, -1, 3).float().contiguous(), *geom, 8, 4, white_bg=bool(model.white_bg))['f32']
+        assert torch.equal(out['f32'][:, i], one[:, 0]), i
+    alone = model.material_balls(probes=False, ims=8, spp=4)
+    assert alone['names'] == ['light'] and torch.equal(alone['f32'][:, 0], out['f32'][:, 0])
+    # the stage-3 model: the stage-2 rows under ITS light, probes and gamma pair
+    got = ref.material_balls(probes=True, ims=8, spp=1, cols=3)
+    assert got['names'] == ['light', 'probe0'] and torch.equal(ref.material_rows(), rows)
+    assert got['f32'].shape == (K, 2, 8, 8, 3) and got['sheet'].shape == (2, 3 * 8, 3 * 8, 3)
+    g = [float(x) for x in ref.gamma.detach().tolist()]
+    lights = torch.stack([ref.light.detach().reshape(-1, 3), list(ref.novel_probes.values())[0].reshape(-1, 3)]).float().contiguous()
+    want = _C.material_balls(rows, lights, ref.lxyz.reshape(-1, 3).contiguous(), ref.lareas.reshape(-1).contiguous(), 8, 1,
+                             white_bg=bool(ref.white_bg), gamma=g)['f32']
+    assert torch.equal(got['f32'], want) and g != [1.0, 1.0]
+
+
+def _png(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert('RGB'))
+
+
+def test_materials_run(vq, tmp_path):
+    from vqnerf_release_amd.decomp import materials
+    model, views = vq
+    out = str(tmp_path / 'host')
+    rec = materials.run(model, out, views=views, ims=8, spp=4, cols=3)
+    assert rec == json.load(open(os.path.join(out, 'materials.json')))
+    names = ['light', 'probe0', 'probe1']
+    assert rec['probes'] == names and len(rec['codes']) == K
+    # usage: counted from vis_mat's embed, shares sum to 1, ranks are a permutation ordered by the counts
+    with torch.no_grad():
+        emb = torch.cat([model.vis_mat(b, mode='test')[0]['embed'].reshape(-1) for b in views]).cpu().numpy().astype(np.int64)
+    counts = np.bincount(emb, minlength=K + 1)[1:]
+    assert [c['points'] for c in rec['codes']] == counts.tolist() and counts.sum() == (emb > 0).sum() > 0
+    assert abs(sum(c['share'] for c in rec['codes']) - 1.0) < 1e-12
+    assert sorted(c['rank'] for c in rec['codes']) == list(range(K))
+    order = rec['order']
+    assert [rec['codes'][k]['rank'] for k in order] == list(range(K)) and all(counts[a] >= counts[b] for a, b in zip(order, order[1:]))
+    balls = model.material_balls(probes=True, ims=8, spp=4, order=order, cols=3, want_f32=False)
+    rows = model.material_rows().cpu().numpy()
+    for k in range(K):
+        assert np.allclose(rec['codes'][k]['albedo'] + rec['codes'][k]['f0'] + [rec['codes'][k]['rough']], rows[k], rtol=0, atol=0)
+        for p, name in enumerate(names):
+            assert np.array_equal(_png(os.path.join(out, 'materials', f'ball_{k:02d}_{name}.png')), balls['u8'][k, p].cpu().numpy())
+    for p, name in enumerate(names):
+        sheet = _png(os.path.join(out, 'materials', f'palette_{name}.png'))
+        assert sheet.shape == (3 * 8, 3 * 8, 3) and np.array_equal(sheet, balls['sheet'][p].cpu().numpy())
+        assert np.array_equal(sheet[:8, :8], balls['u8'][order[0], p].cpu().numpy())         # the most used code comes first
+    assert sorted(os.listdir(os.path.join(out, 'materials'))) == sorted(
+        [f'ball_{k:02d}_{n}.png' for k in range(K) for n in names] + [f'palette_{n}.png' for n in names])
+    # encoded on the device: the same pixels
+    dev_out = str(tmp_path / 'device')
+    with launches() as l:
+        materials.run(model, dev_out, views=views, ims=8, spp=4, cols=3, png='device')
+    assert l.ran('vqn_png_encode')
+    for f in os.listdir(os.path.join(out, 'materials')):
+        assert np.array_equal(_png(os.path.join(out, 'materials', f)), _png(os.path.join(dev_out, 'materials', f))), f
+    # without views: the index order, no shares
+    rec0 = materials.run(model, str(tmp_path / 'plain'), ims=8, spp=1, probes=False)
+    assert rec0['order'] == list(range(K)) and all('share' not in c and c['rank'] == c['code'] for c in rec0['codes']) and rec0['probes'] == ['light']
+
+
+def _listing(root):
+    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)
+
+
+def test_edit_run_preview(vq, tmp_path):
+    from tests.test_gpu_material_edit import _Views, _selection_for
+    from vqnerf_release_amd.decomp import edit
+    model, views = vq
+    with torch.no_grad():
+        base = model.fast_render(views[0], mode='test', gen_embed=True)[0]
+    sel = _selection_for(base)
+    dst = {'diff': [0.7, 0.2, 0.1], 'spec': [-1, -1, -1], 'rough': [0.35]}
+    plain, shown = str(tmp_path / 'plain'), str(tmp_path / 'shown')
+    edit.run(model, _Views(views), plain, sel, dst)[0].flush()
+    edit.run(model, _Views(views), shown, sel, dst, preview=True)[0].flush()
+    previews = [f'dst_preview_{n}.png' for n in ('light', 'probe0', 'probe1')]
+    assert not any(f.startswith('dst_preview') for f in _listing(plain))
+    assert sorted(set(_listing(shown)) - set(_listing(plain))) == sorted(previews) and set(_listing(plain)) <= set(_listing(shown))
+    row = torch.tensor([[0.7, 0.2, 0.1, 0.0, 0.0, 0.0, 0.35]], device='cuda')
+    want = model.material_balls(probes=True, rows=row, want_f32=False)['u8'][0].cpu().numpy()
+    for p, f in enumerate(previews):
+        assert np.array_equal(_png(os.path.join(shown, f)), want[p])

@@ -62,6 +62,7 @@ l vqn_seg_scratch_bytes(lii)  i vqn_seg_contingency_rgb(pppflpipiplpp)  i vqn_se
 i vqn_meanshift_seek(plplidipppp)  l vqn_meanshift_merge_scratch_bytes(li)  i vqn_meanshift_merge(pplidplppp)
 i vqn_meanshift_assign(plpiidppp)""",
     'vqn_material_edit.h': 'i vqn_material_select_edit(pppiplppipipfppppppppppppp)',
+    'vqn_material_balls.h': 'i vqn_material_balls(pipippiiifpipppppiiiplp)',
     'vqn_image_codec.h': """
 i vqn_jpeg_plan(llliilppi)  i vqn_jpeg_encode(pllliilplplpip)  i vqn_png_plan(llllilppi)  i vqn_png_encode(pllllilplplpip)""",
     'vqn_geometry_eval.h': """
@@ -975,6 +976,55 @@ def material_select_edit(n, planes=(), embed=None, mask_in=None, terms=(), ops=(
           nul(codes_h), float(eps), _ptr(e[0]), _ptr(e[1]), _ptr(e[2]), nul(dst_h), nul(scale_h), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]),
           _ptr(o[4]), _ptr(mask_out), _ptr(counts))
     return mask_out, counts, (tuple(outs) if edit is not None else None)
+
+
+# --------------------------------------------------------------------------------------
+# material balls (csrc/material_balls.hip, include/vqn_material_balls.h; decomp/nerfactor/util/material_balls.py)
+MATBALLS_MAX_MATERIALS = 65        # materials at most (VQN_MATBALLS_MAX_MATERIALS)
+MATBALLS_MAX_PROBES = 24           # probes at most (VQN_MATBALLS_MAX_PROBES)
+MATBALLS_SCRATCH_PER_LIGHT = 288   # bytes of scratch per light that always suffice (VQN_MATBALLS_SCRATCH_PER_LIGHT)
+MATBALLS_MAX_OUT_BYTES = 2 ** 31 - 1   # bytes of an output buffer at most (VQN_MATBALLS_MAX_OUT_BYTES)
+
+
+def material_balls(materials, lights, lxyz, areas, ims, spp, sphere_radius=0.4, cam_rot=None, white_bg=True, gamma=None,
+                   want_f32=True, want_u8=False, sheet=None, out=None):
+    """materials float32 [M, 7] = albedo[3], f0[3], rough[1]; lights [P, L, 3]; lxyz [L, 3]; areas [L]: contiguous device tensors.
+    cam_rot: 9 host floats or None (the default camera); gamma: 2 host floats or None.  sheet: None or (order, rows, cols), order a
+    host list of distinct material indices or None (0 .. M - 1).  out: None or (f32, u8, sheet) tensors to write into (None entries are
+    not written), which replaces want_f32 / want_u8 / sheet's allocation -- the refusal tests hand in canary-filled buffers.
+    -> dict(f32 [M, P, ims, ims, 3] | None, u8 uint8 [M, P, ims, ims, 3] | None, sheet uint8 [P, rows ims, cols ims, 3] | None)."""
+    for n_, t in (('materials', materials), ('lights', lights), ('lxyz', lxyz), ('areas', areas)):
+        _f32c(t, n_)
+    M, dev = materials.shape[0], materials.device
+    P, L = (lights.shape[0], lights.shape[1]) if lights.dim() == 3 else (0, 0)
+    if materials.dim() != 2 or materials.shape[1] != 7 or lights.dim() != 3 or lights.shape[2] != 3 or lxyz.numel() != 3 * L or areas.numel() != L:
+        raise VqnError(f'material_balls: expected materials [M, 7], lights [P, L, 3], lxyz [L, 3], areas [L], got {tuple(materials.shape)}, '
+                       f'{tuple(lights.shape)}, {tuple(lxyz.shape)}, {tuple(areas.shape)}')
+    ims, spp = int(ims), int(spp)
+    order, rows, cols = sheet if sheet is not None else (None, 0, 0)
+    order_h = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    rot_h = None if cam_rot is None else np.ascontiguousarray(cam_rot, dtype=np.float32).reshape(-1)
+    gam_h = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.float32).reshape(-1)
+    if (rot_h is not None and rot_h.size != 9) or (gam_h is not None and gam_h.size != 2):
+        raise VqnError('material_balls: cam_rot is 9 floats and gamma 2')
+    if out is not None:
+        f32, u8, sh = out
+    else:
+        shapes = [(M, P, ims, ims, 3) if want_f32 else None, (M, P, ims, ims, 3) if want_u8 else None,
+                  (P, int(rows) * ims, int(cols) * ims, 3) if sheet is not None else None]
+        if any(s is not None and (min(s) < 0 or int(np.prod(s, dtype=np.float64)) * (4 if i == 0 else 1) > MATBALLS_MAX_OUT_BYTES)
+               for i, s in enumerate(shapes)):
+            raise VqnError(f'material_balls: an output of {M} x {P} images of {ims} x {ims} pixels (sheet {rows} x {cols}) exceeds '
+                           f'{MATBALLS_MAX_OUT_BYTES} bytes')
+        f32, u8, sh = [None if s is None else torch.empty(s, dtype=torch.float32 if i == 0 else torch.uint8, device=dev)
+                       for i, s in enumerate(shapes)]
+    need = MATBALLS_SCRATCH_PER_LIGHT * max(L, 1)
+    scratch = _scratch('material_balls', need, dev)
+    nul = lambda a: None if a is None else a.ctypes.data
+    _call('vqn_material_balls', _ptr(materials), M, _ptr(lights), P, _ptr(lxyz), _ptr(areas), L, ims, spp, float(sphere_radius), nul(rot_h),
+          int(bool(white_bg)), nul(gam_h), _ptr(f32), _ptr(u8), _ptr(sh), nul(order_h), 0 if order_h is None else int(order_h.size),
+          int(rows), int(cols), _ptr(scratch), need)
+    return dict(f32=f32, u8=u8, sheet=sh)
 
 
 # --------------------------------------------------------------------------------------

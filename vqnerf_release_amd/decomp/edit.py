@@ -50,16 +50,33 @@ def _hw(to_vis):
     return tuple(int(x) for x in (hw[0] if hw.ndim == 2 else hw).tolist())
 
 
+def write_preview(model, dst, outroot, relight_probes=True, ims=128, spp=4):
+    """outroot/dst_preview_{probe}.png: the replacement material `dst` as a lit sphere under the model's light (`light`) and, with
+    relight_probes, its novel probes (decomp/nerfactor/util/material_balls.py).  A part of dst the edit leaves alone (first component
+    negative) has no value of its own: it is shown as 0 (diff, spec) or 1 (rough).  -> the paths written."""
+    from vqnerf_release_amd.decomp.nerfactor.util import material_balls
+    row = material_balls.material_row({k: (dst[k] if not np.asarray(dst[k], np.float64).reshape(-1)[0] < 0 else
+                                           ([1.0] if k == 'rough' else [0.0, 0.0, 0.0])) for k in ('diff', 'spec', 'rough')})
+    out = model.material_balls(probes=relight_probes, ims=ims, spp=spp, rows=torch.as_tensor(row, device=model.lxyz.device)[None],
+                               want_f32=False, want_u8=True)
+    os.makedirs(outroot, exist_ok=True)
+    paths = [os.path.join(outroot, f'dst_preview_{name}.png') for name in out['names']]
+    for path, image in zip(paths, out['u8'][0].cpu().numpy()):
+        vis.write_png(path, image)
+    return paths
+
+
 @torch.no_grad()
 def run(vq_model, dataset, outroot, selection, dst, ref_model=None, ref_dataset=None, opt_scale=None, relight_probes=True, dst_env=None,
-        name_fmt='batch{i:09d}', writer=None, num_p=None, p_i=None, png='host'):
+        name_fmt='batch{i:09d}', writer=None, num_p=None, p_i=None, png='host', preview=False):
     """Every view of `dataset` (sharded as in train_nfr.render_views: process p_i of num_p takes views p_i, p_i + num_p, ...):
     vq_model.fast_render(edit_select=selection, edit_material=dst, opt_scale, relight_probes | dst_env) -> the mask and the edited
     stage-2 render; with ref_model (and ref_dataset, the same views with the stage-3 inputs; not under dst_env, as in edit.py:225-230)
     ref_model.fast_render(edit_rows=that mask, opt_scale).  Files: outroot/<name>/ by vis_batch (pred_edit_mask.png and embed_map.png
     among them; the two models write the files both know with the same content), outroot/auto_sel/<name>.npy and auto_sel/dst.json.  If a condition
     names rgb, a plain render of the view comes first (the stage-3 model's if given, else the stage-2 model's `call`) and feeds it.
-    png is handed to vis_batch ('device': the PNGs are encoded on the device).
+    png is handed to vis_batch ('device': the PNGs are encoded on the device).  preview=True also writes outroot/dst_preview_{probe}.png,
+    the ball of the replacement row (write_preview), before the first view is relit.
     -> (writer, {name: selected pixels}), the counts read from the device once, at the end."""
     if not isinstance(selection, material_edit.Selection):
         raise ValueError(f'selection is a material_edit.Selection, got {type(selection).__name__}')
@@ -75,6 +92,8 @@ def run(vq_model, dataset, outroot, selection, dst, ref_model=None, ref_dataset=
     sel_dir = os.path.join(outroot, 'auto_sel')
     if p_i == 0:
         _write_dst(sel_dir, dst)
+        if preview:
+            write_preview(vq_model, dst, outroot, relight_probes=relight_probes)
     os.makedirs(sel_dir, exist_ok=True)
     needs_rgb = 'rgb' in selection.needs()
     names, counts = [], []

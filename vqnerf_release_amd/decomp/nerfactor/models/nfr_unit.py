@@ -645,6 +645,33 @@ class BrdfModel(ShapeModel):
         self._numerics(out.get('rgb_probes'), 'Light Probe Renders')
         return out
 
+    # ------------------------------------------------------------------ materials on their own (vq_nfr / ref_nfr: material_rows)
+    def ball_lights(self, probes=True):
+        """(names, float32 [P, L, 3]): the model's own light first, then `novel_probes` in their order"""
+        names, maps = ['light'], [self.light.detach()]
+        if probes:
+            names += list(self.novel_probes)
+            maps += list(self.novel_probes.values())
+        dev = self.lxyz.device
+        return names, torch.stack([torch.as_tensor(m, dtype=torch.float32, device=dev).reshape(-1, 3) for m in maps], 0).contiguous()
+
+    @torch.no_grad()
+    def material_balls(self, probes=True, ims=128, spp=4, rows=None, order=None, cols=None, want_f32=True, want_u8=True):
+        """Every material of material_rows() (vq_nfr: one per code; or `rows` [M, 7]) as a lit sphere under the model's light and then
+        `novel_probes` (util/material_balls.py, csrc/material_balls.hip), with the model's background and, for the data types that
+        have one, its gamma pair.  -> dict(names, f32 [M, P, ims, ims, 3] | None, u8 | None, sheet | None: given `order` or `cols`)."""
+        from vqnerf_release_amd.decomp.nerfactor.util import material_balls as balls
+        names, lights = self.ball_lights(probes)
+        rows = self.material_rows() if rows is None else rows
+        gamma = None if self.data_type == 'nerf' else [float(g) for g in self.gamma.detach().tolist()]
+        sheet = None
+        if order is not None or cols is not None:
+            sheet = (order,) + balls.sheet_shape(rows.shape[0] if order is None else len(order), cols)
+        out = _C.material_balls(*balls._device_inputs(rows, lights, self.lxyz, self.lareas), ims, spp, white_bg=bool(self.white_bg),
+                                gamma=gamma, want_f32=want_f32, want_u8=want_u8, sheet=sheet)
+        out['names'] = names
+        return out
+
     def _shade_train(self, xyz, normal, rayo, lvis, materials, light=None):
         """Shading with gradients (albedo / spec / rough / light) through the fused forward + backward kernels."""
         light = self.light if light is None else light

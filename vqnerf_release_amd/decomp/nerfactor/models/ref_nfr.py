@@ -47,6 +47,18 @@ class Model(BrdfModel):
                 p.requires_grad_(False)
         if vq_model._light is not None:
             self.set_light(vq_model.light.detach().clone())       # what stage 2 saved to np_light.npy: the clipped light
+        # for material_rows (this model has no codebook of its own); past nn.Module's registration: stage 2 is no submodule of stage 3,
+        # its parameters are not this model's
+        self.__dict__['_stage2'] = vq_model
+
+    _stage2 = None
+
+    def material_rows(self):
+        """float32 [K, 7]: the code materials of the stage-2 model whose frozen encoder this one carries (vq_nfr.Model.material_rows).
+        Stage 3 itself has no per-code material: its albedo and roughness also read the per-pixel reference colour."""
+        if self._stage2 is None:
+            raise ValueError('material_rows: no stage-2 model attached (load_stage2 attaches it)')
+        return self._stage2.material_rows()
 
     def set_light(self, arr):
         """The stage-3 light is a CONSTANT: the reference loads the light stage 2 wrote (`np_light.npy`) into a plain tensor

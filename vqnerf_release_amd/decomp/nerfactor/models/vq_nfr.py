@@ -436,6 +436,16 @@ class Model(BrdfModel):
             to_vis['gt_' + k] = v
         return pred, gt, {'mode': mode, 'gtc': rgb_m}, to_vis
 
+    # ------------------------------------------------------------------ the codebook's materials on their own
+    @torch.no_grad()
+    def material_rows(self):
+        """float32 [K, 7] = albedo[3], spec (f0)[3], rough[1] of every code: the VQ heads evaluated on the K prepared codes (the
+        columns of get_codebook(), which are the rows `quantize` holds for a point that sits on its code) through the same
+        `_all_heads(z_vq, 'vq')` that `call` runs, so row k is what the VQ branch gives a point quantised to code k."""
+        codes = self.get_codebook().detach().t().contiguous()
+        albedo, spec, rough = self._all_heads(codes, 'vq')
+        return torch.cat([albedo, spec.expand(-1, 3), rough], -1).contiguous()
+
     def vis_mat(self, batch, mode='train', opt_scale=None, ref_batch=False, thres=None):
         self._validate_mode(mode)
         id_, hw, rayo, rayd, rgb, alpha, pred_alpha, xyz = batch[:8]
