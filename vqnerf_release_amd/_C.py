@@ -63,6 +63,9 @@ i vqn_meanshift_seek(plplidipppp)  l vqn_meanshift_merge_scratch_bytes(li)  i vq
 i vqn_meanshift_assign(plpiidppp)""",
     'vqn_material_edit.h': 'i vqn_material_select_edit(pppiplppipipfppppppppppppp)',
     'vqn_material_balls.h': 'i vqn_material_balls(pipippiiifpipppppiiiplp)',
+    'vqn_mesh_materials.h': """
+l vqn_mesh_label_scratch_bytes(ll)  i vqn_mesh_label_mode(plpliiippplp)  i vqn_mesh_split_count(plplippppp)
+i vqn_mesh_split_emit(pllippppllpppp)""",
     'vqn_image_codec.h': """
 i vqn_jpeg_plan(llliilppi)  i vqn_jpeg_encode(pllliilplplpip)  i vqn_png_plan(llllilppi)  i vqn_png_encode(pllllilplplpip)""",
     'vqn_geometry_eval.h': """
@@ -794,6 +797,76 @@ def mc_brick_emit(ub, brick_ijk, slot, dims, threshold, vert_offset, tri_offset,
           None if origin is None else _host(origin, np.float32), None if step is None else _host(step, np.float32),
           _ptr(verts) if n_verts else None, _ptr(tris) if n_tris else None)
     return verts, tris
+
+
+# --------------------------------------------------------------------------------------
+# material codes on a mesh (csrc/mesh_materials.hip, include/vqn_mesh_materials.h; geo/mesh.py, decomp/material_mesh.py)
+MESHMAT_MAX_CODES = 128            # codes at most (VQN_MESHMAT_MAX_CODES)
+MESHMAT_FACES_PER_BLOCK = 512      # faces per row entry of block_count (VQN_MESHMAT_FACES_PER_BLOCK)
+MESHMAT_WORD_BITS = 32             # vertices per word of the usage bitmap (VQN_MESHMAT_WORD_BITS)
+
+
+def _mesh_codes(triangles, codes, what):
+    """checks of (triangles [T,3], codes [V]) -> (T, V)"""
+    T = _mesh_tris(triangles, what)
+    if codes.dtype != torch.int32 or not codes.is_contiguous() or codes.device != triangles.device or codes.dim() != 1:
+        raise VqnError(f'{what}: expected contiguous int32 codes [V] on the device of the triangles, got {codes.dtype} {tuple(codes.shape)} '
+                       f'on {codes.device}')
+    return T, codes.shape[0]
+
+
+def mesh_label_mode(triangles, codes, n_codes, iters, self_weight):
+    """`iters` >= 1 rounds of majority vote over the mesh (vqn_mesh_label_mode) -> (codes int32 [V], changed int32 [iters]), new tensors."""
+    T, V = _mesh_codes(triangles, codes, 'mesh_label_mode')
+    out = torch.empty_like(codes)
+    changed = torch.empty((max(int(iters), 0),), dtype=torch.int32, device=codes.device)
+    need = lib().vqn_mesh_label_scratch_bytes(T, V)
+    buf = _scratch('mesh_label_mode', max(need, 64), codes.device)        # (need < 0: sizes the call itself refuses, with the reason)
+    _call('vqn_mesh_label_mode', _ptr(triangles) if T else None, T, _ptr(codes) if V else None, V, int(n_codes), int(self_weight), int(iters),
+          _ptr(out) if V else None, _ptr(changed) if changed.numel() else None, _ptr(buf), buf.numel())
+    return out, changed
+
+
+def mesh_split_shape(T, V):
+    """-> (B, W): the face blocks and the bitmap words per code of a mesh of T triangles and V vertices"""
+    return max(1, -(-T // MESHMAT_FACES_PER_BLOCK)), -(-V // MESHMAT_WORD_BITS)
+
+
+def mesh_split_count(triangles, codes, n_codes):
+    """-> (face_code int32 [T], block_count int32 [K, B], bitmap int32 [K, W] (the bits of a uint32), word_count int32 [K, W])."""
+    T, V = _mesh_codes(triangles, codes, 'mesh_split_count')
+    K = int(n_codes)
+    B, W = mesh_split_shape(T, V)
+    dev = triangles.device
+    rows = min(max(K, 0), MESHMAT_MAX_CODES)                             # (a refused K: nothing is written, nothing large is allocated)
+    face_code = torch.empty((T,), dtype=torch.int32, device=dev)
+    block_count = torch.empty((rows, B), dtype=torch.int32, device=dev)
+    bitmap = torch.empty((rows, W), dtype=torch.int32, device=dev)
+    word_count = torch.empty((rows, W), dtype=torch.int32, device=dev)
+    _call('vqn_mesh_split_count', _ptr(triangles) if T else None, T, _ptr(codes) if V else None, V, K, _ptr(face_code) if T else None,
+          _ptr(block_count) if rows else None, _ptr(bitmap) if rows * W else None, _ptr(word_count) if rows * W else None)
+    return face_code, block_count, bitmap, word_count
+
+
+def mesh_split_emit(triangles, n_verts, n_codes, face_code, block_offset, bitmap, word_offset, n_faces, n_slots, out=None):
+    """The split from the flat exclusive prefix sums of mesh_split_count's counts and their totals -> (face_src int32 [F],
+    tris_local int32 [F, 3], vert_src int32 [S]).  out: these three, to be written in place."""
+    T = _mesh_tris(triangles, 'mesh_split_emit')
+    K, V = int(n_codes), int(n_verts)
+    B, W = mesh_split_shape(T, V)
+    for t, n in ((face_code, T), (block_offset, K * B), (bitmap, K * W), (word_offset, K * W)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != triangles.device or t.numel() != n:
+            raise VqnError('mesh_split_emit: face_code [T], block_offset [K, B], bitmap and word_offset [K, W]: contiguous int32 tensors on '
+                           'the device of the triangles')
+    if out is None:
+        out = (torch.empty((n_faces,), dtype=torch.int32, device=triangles.device),
+               torch.empty((n_faces, 3), dtype=torch.int32, device=triangles.device),
+               torch.empty((n_slots,), dtype=torch.int32, device=triangles.device))
+    face_src, tris_local, vert_src = out
+    nul = lambda t: _ptr(t) if t.numel() else None
+    _call('vqn_mesh_split_emit', nul(triangles), T, V, K, nul(face_code), nul(block_offset), nul(bitmap), nul(word_offset), int(n_faces),
+          int(n_slots), nul(face_src), nul(tris_local), nul(vert_src))
+    return face_src, tris_local, vert_src
 
 
 # --------------------------------------------------------------------------------------

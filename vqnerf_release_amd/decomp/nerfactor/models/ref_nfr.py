@@ -60,6 +60,14 @@ class Model(BrdfModel):
             raise ValueError('material_rows: no stage-2 model attached (load_stage2 attaches it)')
         return self._stage2.material_rows()
 
+    def materials_at(self, xyz, thres=None, mode='test'):
+        """The materials at points xyz [N, 3] alone: those of the stage-2 model whose frozen encoder this one carries
+        (vq_nfr.Model.materials_at), as material_rows.  Stage 3's own albedo and roughness also read the per-pixel reference colour,
+        which a point of a mesh does not have."""
+        if self._stage2 is None:
+            raise ValueError('materials_at: no stage-2 model attached (load_stage2 attaches it)')
+        return self._stage2.materials_at(xyz, thres=thres, mode=mode)
+
     def set_light(self, arr):
         """The stage-3 light is a CONSTANT: the reference loads the light stage 2 wrote (`np_light.npy`) into a plain tensor
         (ref_nfr.py:70-87), not a variable -- it gets no gradient and `loss_kwargs['env']` is None (:263, `self._light`)."""

@@ -446,6 +446,42 @@ class Model(BrdfModel):
         albedo, spec, rough = self._all_heads(codes, 'vq')
         return torch.cat([albedo, spec.expand(-1, 3), rough], -1).contiguous()
 
+    materials_slab = 1 << 18   # points per pass of materials_at (a point's 256-wide rows are 1 KiB each way)
+
+    @torch.no_grad()
+    def materials_at(self, xyz, thres=None, mode='test'):
+        """The materials at points xyz [N, 3] alone (a point's material depends on nothing else) -> dict of device tensors:
+        code int32 [N] (0-based: `embed` of vis_mat / fast_embed is code + 1); basecolor [N, 3], ks [N, 1], rough [N, 1] from the
+        main heads (vis_mat's albedo is (1 - ks) * basecolor, its spec ks * basecolor); vq_albedo [N, 3], vq_spec [N, 3 | 1],
+        vq_rough [N, 1] from the VQ heads on the quantised row, as `call` shows them (that row is the straight-through x + (q - x),
+        equal to the code q to an ulp, so they agree with material_rows()[code] to rounding, not bit for bit).  The same
+        kernels as `call` and vis_mat: the fused front (one launch) where it applies, else encoder, quantiser step and the two head
+        families as separate launches; the rows are bit-identical either way.  In slabs of materials_slab points; no host read."""
+        self._validate_mode(mode)
+        _C.require_device(xyz, 'materials_at')
+        x = xyz.detach().reshape(-1, 3).float().contiguous()
+        n, dev = x.shape[0], x.device
+        if n == 0:
+            raise _C.VqnError('materials_at: no points')
+        out = None
+        for s in range(0, n, self.materials_slab):
+            pts = x[s: s + self.materials_slab]
+            front = self._fused_front(pts, mode, thres, False)
+            if front is not None:
+                _, basecolor, ks, rough, vq, _, _, _, vq_heads, _ = front
+            else:
+                z_enc = self._pred_enc_at(pts)
+                vq, z_vq, _, _ = self._quantise(z_enc, mode, thres, want_indices=False)
+                basecolor, ks, rough = self._all_heads(z_enc, 'main')
+                vq_heads = self._all_heads(z_vq, 'vq')
+            rows = {'code': vq['encoding_indices'].reshape(-1).to(torch.int32), 'basecolor': basecolor, 'ks': ks, 'rough': rough,
+                    'vq_albedo': vq_heads[0], 'vq_spec': vq_heads[1], 'vq_rough': vq_heads[2]}
+            if out is None:
+                out = {k: torch.empty((n,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev) for k, v in rows.items()}
+            for k, v in rows.items():
+                out[k][s: s + pts.shape[0]] = v
+        return out
+
     def vis_mat(self, batch, mode='train', opt_scale=None, ref_batch=False, thres=None):
         self._validate_mode(mode)
         id_, hw, rayo, rayd, rgb, alpha, pred_alpha, xyz = batch[:8]

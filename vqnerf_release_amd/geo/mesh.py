@@ -14,6 +14,11 @@ refuses; it reads the host twice.
 
 For scoring a mesh (geo/geometry_eval.py): `read_ply` reads what `write_ply` writes and point-cloud files,
 `sample_surface` draws points of the surface uniformly by area through csrc/geometry_eval.hip.
+
+Material codes on the mesh (decomp/material_mesh.py): `smooth_labels` cleans per-vertex codes up by majority
+vote over the mesh, `face_labels` gives one code per face, `split_by_label` cuts the mesh into one sub-mesh per code with a compact
+vertex list each (csrc/mesh_materials.hip: integer kernels, one host read); `write_ply(extra=...)` / `read_ply(extra=...)` carry scalar
+vertex properties, `write_obj` / `write_mtl` write the faces grouped by material.
 """
 import numpy as np
 import torch
@@ -355,10 +360,15 @@ def _host_array(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
-def write_ply(path, vertices, triangles, normals=None, colors=None):
+_PLY_EXTRA_TYPES = {'int32': ('int', '<i4'), 'float32': ('float', '<f4'), 'uint8': ('uchar', 'u1')}
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None, extra=None):
     """Binary little-endian PLY: `element vertex` with float x, y, z and `element face` with `property list uchar int vertex_indices`
     (the layout trimesh writes for a bare triangle mesh).  vertices [V,3], triangles [T,3]: arrays or tensors.  normals [V,3]: float
-    nx, ny, nz after z; colors [V,3] (0..255): uchar red, green, blue after those (trimesh's order, what MeshLab and Blender read)."""
+    nx, ny, nz after z; colors [V,3] (0..255): uchar red, green, blue after those (trimesh's order, what MeshLab and Blender read).
+    extra {name: [V] array or tensor}: further scalar properties per vertex, after the colours, in the dict's order, typed by the
+    array's dtype (int32 -> int, float32 -> float, uint8 -> uchar; anything else raises); read_ply(extra=names) reads them back."""
     v = np.ascontiguousarray(_host_array(vertices).reshape(-1, 3), dtype='<f4')
     t = _host_array(triangles).reshape(-1, 3)
     faces = np.empty(len(t), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
@@ -371,8 +381,19 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
     if colors is not None:
         fields.append(('c', 'u1', (3,)))
         props += 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
-    rows = np.empty(len(v), dtype=fields)                                   # packed: 12 (+ 12) (+ 3) bytes per vertex
+    extras = []
+    for name, a in (extra or {}).items():
+        a = _host_array(a)
+        if str(a.dtype) not in _PLY_EXTRA_TYPES or a.reshape(-1).shape[0] != len(v) or not name.isidentifier():
+            raise ValueError(f'write_ply: extra[{name!r}] must be {len(v)} values of {sorted(_PLY_EXTRA_TYPES)}, got {a.dtype} {a.shape}')
+        ply_type, np_type = _PLY_EXTRA_TYPES[str(a.dtype)]
+        fields.append(('x_' + name, np_type))
+        props += f'property {ply_type} {name}\n'
+        extras.append(('x_' + name, a.reshape(-1)))
+    rows = np.empty(len(v), dtype=fields)                                   # packed: 12 (+ 12) (+ 3) bytes per vertex (+ the extras)
     rows['p'] = v
+    for field, a in extras:
+        rows[field] = a
     for name, a in (('n', normals), ('c', colors)):
         if a is not None:
             a = _host_array(a).reshape(-1, 3)
@@ -458,11 +479,13 @@ def _ply_rows(f, path, binary, name, count, props):
     return {p: a[:, i] for i, (p, _) in enumerate(props)}
 
 
-def read_ply(path, device='cuda'):
+def read_ply(path, device='cuda', extra=None):
     """-> (vertices f32 [V,3], triangles int32 [T,3] or None, normals f32 [V,3] or None), tensors on `device`.  Reads ASCII and binary
     little-endian files whose `vertex` element has x y z and perhaps nx ny nz (colours and other scalar properties are skipped) and
     whose `face` element, if any, is one list `vertex_indices` / `vertex_index` of three: what write_ply writes, and point clouds
-    without faces (DTU's scans).  Anything else -- big-endian data, faces that are not triangles -- raises VqnError."""
+    without faces (DTU's scans).  Anything else -- big-endian data, faces that are not triangles -- raises VqnError.
+    extra: names of scalar vertex properties (write_ply's `extra`, or red / green / blue) -> a fourth value, {name: tensor [V]} in the
+    file's type (an ASCII file's values as float64); a name the file does not have raises VqnError."""
     with open(path, 'rb') as f:
         binary, elements = _ply_header(f, path)
         vert = tri = None
@@ -483,8 +506,14 @@ def read_ply(path, device='cuda'):
         if len(tri) and (tri.min() < 0 or tri.max() >= len(xyz)):
             raise _C.VqnError(f'read_ply: {path}: a face names a vertex outside 0 .. {len(xyz) - 1}')
         tri = torch.as_tensor(np.array(tri, dtype=np.int32).reshape(-1, 3), device=device)        # (a copy: the file's bytes are read-only)
-    return (torch.as_tensor(np.ascontiguousarray(xyz), device=device), tri,
-            None if nrm is None else torch.as_tensor(np.ascontiguousarray(nrm), device=device))
+    out = (torch.as_tensor(np.ascontiguousarray(xyz), device=device), tri,
+           None if nrm is None else torch.as_tensor(np.ascontiguousarray(nrm), device=device))
+    if extra is None:
+        return out
+    missing = [k for k in extra if k not in vert]
+    if missing:
+        raise _C.VqnError(f'read_ply: {path}: the vertex element has no property {missing}')
+    return out + ({k: torch.as_tensor(np.array(vert[k]), device=device) for k in extra},)
 
 
 def sample_surface(vertices, triangles, n, generator=None, u=None):
@@ -500,3 +529,107 @@ def sample_surface(vertices, triangles, n, generator=None, u=None):
         raise _C.VqnError(f'sample_surface: u must be [{int(n)}, 3], got {tuple(u.shape)}')
     cum = torch.cumsum(_C.geom_tri_areas(vertices, triangles), 0)
     return _C.geom_sample_surface(vertices, triangles, cum, u.contiguous())
+
+
+# ---- material codes on the mesh: clean-up, face codes, split by code (csrc/mesh_materials.hip) ----------------
+def _label_inputs(triangles, codes, what):
+    _C.require_device(triangles, what)
+    _C.require_device(codes, what)
+    return triangles.detach().to(torch.int32).contiguous(), codes.detach().reshape(-1).to(torch.int32).contiguous()
+
+
+def smooth_labels(triangles, codes, n_codes, iters=2, self_weight=1):
+    """`iters` rounds of majority vote of the per-vertex codes [V] (int, 0 .. n_codes - 1) over the device mesh -> (codes, changed).
+    One round: vertex v receives, for every triangle corner it is, one vote for the code of each of the triangle's two other corners,
+    and self_weight votes for its own; it keeps its code if that holds the maximum, else takes the smallest code that does.  Every
+    round reads the codes of the round before; a vertex no triangle uses keeps its code.  changed int32 [iters] (device): the
+    vertices each round changed.  iters = 0 returns the same codes object and launches nothing.  No host read."""
+    if int(iters) == 0:
+        return codes, torch.empty((0,), dtype=torch.int32, device=codes.device)
+    triangles, codes = _label_inputs(triangles, codes, 'smooth_labels')
+    return _C.mesh_label_mode(triangles, codes, n_codes, iters, self_weight)
+
+
+def _split_count(triangles, codes, n_codes):
+    triangles, codes = _label_inputs(triangles, codes, 'split_by_label')
+    return (triangles, codes) + _C.mesh_split_count(triangles, codes, n_codes)
+
+
+def face_labels(triangles, codes, n_codes=_C.MESHMAT_MAX_CODES):
+    """One code per face, int32 [T] (device): with a, b, c the codes of its vertices, a if a == b or a == c, else b if b == c, else
+    min(a, b, c); -1 for a triangle with an index outside the vertices or a code outside [0, n_codes).  No host read."""
+    return _split_count(triangles, codes, n_codes)[2]
+
+
+def split_by_label(triangles, codes, n_codes):
+    """The device mesh cut into one sub-mesh per code -> dict of
+      face_code int32 [T] (face_labels); face_count [K] and face_offset [K + 1] (Python lists: the faces of each code and their
+      exclusive prefix sum); face_src int32 [F]: the original indices of the faces with a code, ordered by (code, original index);
+      vert_src int32 [S] with vert_offset [K + 1] (a list): for each code in turn the original ids of the vertices its faces use,
+      ascending (a vertex on a border appears once in every group that uses it); vert_count [K];
+      tris_local int32 [F, 3]: row j is face face_src[j], every vertex id replaced by its rank inside its group's slice of vert_src;
+      n_faces = F, n_slots = S, dropped = T - F.
+    Two kernels, two prefix sums between them, ONE host read (both offset lists, in one copy), as filter_components."""
+    K = int(n_codes)
+    triangles, codes, face_code, block_count, bitmap, word_count = _split_count(triangles, codes, K)
+    T, V = triangles.shape[0], codes.shape[0]
+    dev = triangles.device
+    if V == 0 or T == 0:
+        e = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+        return dict(face_code=face_code, face_count=[0] * K, face_offset=[0] * (K + 1), face_src=e(0), vert_src=e(0), vert_count=[0] * K,
+                    vert_offset=[0] * (K + 1), tris_local=e(0, 3), n_faces=0, n_slots=0, dropped=T)
+    B, W = block_count.shape[1], word_count.shape[1]
+    binc = torch.cumsum(block_count.reshape(-1), 0, dtype=torch.int32)      # (totals <= T and <= 3 T: inside int32)
+    winc = torch.cumsum(word_count.reshape(-1), 0, dtype=torch.int32)
+    ends = torch.cat([binc[B - 1::B], winc[W - 1::W]]).tolist()             # the one host read
+    face_offset, vert_offset = [0] + ends[:K], [0] + ends[K:]
+    F, S = face_offset[K], vert_offset[K]
+    block_offset = binc.sub_(block_count.reshape(-1))                       # exclusive prefix sums
+    word_offset = winc.sub_(word_count.reshape(-1))
+    face_src, tris_local, vert_src = _C.mesh_split_emit(triangles, V, K, face_code, block_offset, bitmap.reshape(-1), word_offset, F, S)
+    return dict(face_code=face_code, face_count=[b - a for a, b in zip(face_offset, face_offset[1:])], face_offset=face_offset,
+                face_src=face_src, vert_src=vert_src, vert_count=[b - a for a, b in zip(vert_offset, vert_offset[1:])],
+                vert_offset=vert_offset, tris_local=tris_local, n_faces=F, n_slots=S, dropped=T - F)
+
+
+def write_mtl(path, names, rows):
+    """Wavefront MTL: one `newmtl <name>` per entry of names with the lines of rows[i], a dict of Kd [3], Ks [3], Pr, Ns and illum
+    (decomp/material_mesh.py states how they follow from a material row).  Floats are written with nine significant digits: a
+    float32 read back from the text is the float32 that was written."""
+    with open(path, 'w') as f:
+        f.write('# materials of the VQ codes\n')
+        for name, row in zip(names, rows):
+            f.write(f'\nnewmtl {name}\n')
+            f.write('Kd %.9g %.9g %.9g\n' % tuple(float(x) for x in row['Kd']))
+            f.write('Ks %.9g %.9g %.9g\n' % tuple(float(x) for x in row['Ks']))
+            f.write('Pr %.9g\nNs %.9g\nillum %d\n' % (float(row['Pr']), float(row['Ns']), int(row['illum'])))
+
+
+def write_obj(path, vertices, triangles_sorted, face_offset, names, normals=None, mtllib=None):
+    """Wavefront OBJ of a mesh whose faces are sorted by material: `mtllib` (default: the path's own name with .mtl), every vertex as
+    `v x y z` (and `vn` with normals [V,3]), then for every group k with face_offset[k] < face_offset[k + 1] one `usemtl names[k]`
+    followed by its faces `f a b c` (`f a//a b//b c//c` with normals), 1-based.  triangles_sorted [F,3]: the faces in group order
+    (tris[face_src] of split_by_label).  Floats with nine significant digits."""
+    import os
+    v = _host_array(vertices).reshape(-1, 3)
+    t = _host_array(triangles_sorted).reshape(-1, 3).astype(np.int64) + 1
+    n = None if normals is None else _host_array(normals).reshape(-1, 3)
+    if len(face_offset) != len(names) + 1 or face_offset[0] != 0 or face_offset[-1] != len(t):
+        raise ValueError(f'write_obj: face_offset must run from 0 to {len(t)} over {len(names)} groups, got {list(face_offset)[:4]} ...')
+    if n is not None and len(n) != len(v):
+        raise ValueError(f'write_obj: {len(n)} normals for {len(v)} vertices')
+    if mtllib is None:
+        mtllib = os.path.splitext(os.path.basename(path))[0] + '.mtl'
+    with open(path, 'w') as f:
+        f.write(f'mtllib {mtllib}\n')
+        f.write(''.join('v %.9g %.9g %.9g\n' % tuple(r) for r in v.tolist()))
+        if n is not None:
+            f.write(''.join('vn %.9g %.9g %.9g\n' % tuple(r) for r in n.tolist()))
+        fmt = 'f %d//%d %d//%d %d//%d\n' if n is not None else 'f %d %d %d\n'
+        for k, name in enumerate(names):
+            a, b = int(face_offset[k]), int(face_offset[k + 1])
+            if a == b:
+                continue
+            f.write(f'usemtl {name}\n')
+            rows = t[a:b].tolist()
+            f.write(''.join(fmt % (tuple(x for i in r for x in (i, i)) if n is not None else tuple(r)) for r in rows))
