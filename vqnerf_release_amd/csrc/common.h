@@ -52,6 +52,23 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifdef __HIPCC__
 __device__ __forceinline__ void st_stream(f32x4* p, const f32x4 v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ f32x4 ld_stream(const f32x4* p) { return __builtin_nontemporal_load(p); }
+
+// a * b, a + b, a - b, each rounded to f32 on its own.  HIP's __fmul_rn / __fadd_rn / __fsub_rn are the plain operators, and the
+// compiler's default contraction fuses a product with a sum or difference in the same basic block into one fma: one rounding where a
+// statement that promises another framework's bits has two.  With contraction off inside these bodies neither operation carries the
+// permission to fuse, and they stay apart after inlining.
+__device__ __forceinline__ float vqn_mul_rn(const float a, const float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float vqn_add_rn(const float a, const float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float vqn_sub_rn(const float a, const float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 #endif
 
 static inline int vqn_num_cus() {

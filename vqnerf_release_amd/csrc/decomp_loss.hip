@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void vq_ema_update_kernel(const float* __restr
   __syncthreads();
   const float om = (float)(1.0 - decay);        // (1 - decay) taken in double, then rounded: what the framework statement multiplies by
   for (int k = tid; k < K; k += 256) {
-    const float hdn = __fsub_rn(hid_cs[k], __fmul_rn(__fsub_rn(hid_cs[k], counts[k]), om));      // (each step rounded as the framework
+    const float hdn = vqn_sub_rn(hid_cs[k], vqn_mul_rn(vqn_sub_rn(hid_cs[k], counts[k]), om));   // (each step rounded as the framework
                                                                                                //  statement rounds it: no contraction into an fma)
     hid_cs[k] = hdn;
     const float a = (float)((double)hdn / deb[0]);
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void vq_ema_update_kernel(const float* __restr
   const double d1 = deb[1];
   for (int i = tid; i < D * K; i += 256) {
     const int k = i % K;
-    const float hdn = __fsub_rn(hid_dw[i], __fmul_rn(__fsub_rn(hid_dw[i], dw[i]), om));
+    const float hdn = vqn_sub_rn(hid_dw[i], vqn_mul_rn(vqn_sub_rn(hid_dw[i], dw[i]), om));
     hid_dw[i] = hdn;
     const float a = (float)((double)hdn / d1);
     avg_dw[i] = a;
@@ -297,16 +297,16 @@ __global__ __launch_bounds__(256) void l2_normalize_rows_bwd_kernel(const float*
 // g = g_ste + (x - q) (g_loss 2 / numel)   (g_ste may be absent; g_loss a device scalar) -- separately rounded, as the framework ops were
 __global__ __launch_bounds__(256) void ste_commit_bwd_kernel(const f32x4* __restrict__ x, const f32x4* __restrict__ q, const f32x4* __restrict__ g_ste,
                                                              const float* __restrict__ g_loss, float two_over_numel, long n4, f32x4* __restrict__ out) {
-  const float t = __fmul_rn(g_loss[0], two_over_numel);
+  const float t = vqn_mul_rn(g_loss[0], two_over_numel);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     const f32x4 a = x[i], b = q[i];
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = __fmul_rn(__fsub_rn(a[j], b[j]), t);
+    for (int j = 0; j < 4; ++j) o[j] = vqn_mul_rn(vqn_sub_rn(a[j], b[j]), t);
     if (g_ste != nullptr) {
       const f32x4 c = g_ste[i];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = __fadd_rn(c[j], o[j]);
+      for (int j = 0; j < 4; ++j) o[j] = vqn_add_rn(c[j], o[j]);
     }
     out[i] = o;
   }
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void vq_train_bwd_kernel(const float* __restri
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   // (loss_post: the forward's second factor -- the commitment cost -- applied to the incoming adjoint as autograd's own multiplication would)
-  const float t_c = __fmul_rn(__fmul_rn(g_loss[0], loss_post), two_over_numel);
+  const float t_c = vqn_mul_rn(vqn_mul_rn(g_loss[0], loss_post), two_over_numel);
   const f32x4* xr = reinterpret_cast<const f32x4*>(x + row * D);
   const f32x4* nr = reinterpret_cast<const f32x4*>(xn + row * D);
   const f32x4* qr = reinterpret_cast<const f32x4*>(q + row * D);
@@ -337,11 +337,11 @@ __global__ __launch_bounds__(256) void vq_train_bwd_kernel(const float* __restri
       xv[k] = xr[i];
       const f32x4 a = nr[i], b = qr[i];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) gv[k][j] = __fmul_rn(__fsub_rn(a[j], b[j]), t_c);
+      for (int j = 0; j < 4; ++j) gv[k][j] = vqn_mul_rn(vqn_sub_rn(a[j], b[j]), t_c);
       if (gr != nullptr) {
         const f32x4 c = gr[i];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) gv[k][j] = __fadd_rn(c[j], gv[k][j]);
+        for (int j = 0; j < 4; ++j) gv[k][j] = vqn_add_rn(c[j], gv[k][j]);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) { x2 = fmaf(xv[k][j], xv[k][j], x2); xg = fmaf(xv[k][j], gv[k][j], xg); }
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256) void codebook_prep_kernel(const float* __restr
   float s2 = 0.f, cg = 0.f;
   for (int d = t; d < D; d += 256) {
     const float v = x[(size_t)d * K + k];
-    const float c = __fadd_rn(v, __fsub_rn(fminf(fmaxf(v, 0.f), 1.f), v));
+    const float c = vqn_add_rn(v, vqn_sub_rn(fminf(fmaxf(v, 0.f), 1.f), v));
     s2 = fmaf(c, c, s2);
     if (BWD) cg = fmaf(c, gy[(size_t)d * K + k], cg);
   }
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) void codebook_prep_kernel(const float* __restr
   const float tt = s2 > eps ? (s * s * s) * cg : 0.f;
   for (int d = t; d < D; d += 256) {
     const float v = x[(size_t)d * K + k];
-    const float c = __fadd_rn(v, __fsub_rn(fminf(fmaxf(v, 0.f), 1.f), v));
+    const float c = vqn_add_rn(v, vqn_sub_rn(fminf(fmaxf(v, 0.f), 1.f), v));
     out[(size_t)d * K + k] = BWD ? gy[(size_t)d * K + k] * s - c * tt : c * s;
   }
 }
@@ -448,7 +448,7 @@ __device__ __forceinline__ bool sim_later_wins(float da, int ia, float db, int i
 __global__ __launch_bounds__(256) void sim_smooth_fwd_kernel(const float* __restrict__ cb, int D, int K, float w, float* __restrict__ out) {
   __shared__ float best[256];
   __shared__ int bi[256];
-  __shared__ float cbs[SIM_LDS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float cbs[SIM_LDS_FLOATS];     // (read and written as float4 by the staging copy)
   const int t = threadIdx.x;
   const bool staged = D * K <= SIM_LDS_FLOATS;
   if (staged) {

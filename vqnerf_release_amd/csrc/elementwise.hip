@@ -15,7 +15,7 @@ __global__ __launch_bounds__(256) void clip_preserve_kernel(const float* __restr
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float v = x[i];
     const float c = fminf(fmaxf(v, lo), hi);                    // (NaN propagates through the sum below: v + (c - v) with v = NaN)
-    y[i] = __fadd_rn(v, __fsub_rn(c, v));
+    y[i] = vqn_add_rn(v, vqn_sub_rn(c, v));
   }
 }
 
@@ -26,8 +26,8 @@ __global__ __launch_bounds__(256) void ks_split_fwd_kernel(const float* __restri
     const long p = i / 3;
     const int c = (int)(i - 3 * p);
     const float k = ks[p * kc + (kc == 1 ? 0 : c)], b = bc[i];
-    spec[i] = __fmul_rn(k, b);
-    albedo[i] = __fmul_rn(__fsub_rn(1.0f, k), b);
+    spec[i] = vqn_mul_rn(k, b);
+    albedo[i] = vqn_mul_rn(vqn_sub_rn(1.0f, k), b);
   }
 }
 
@@ -40,10 +40,11 @@ __global__ __launch_bounds__(256) void ks_split_bwd_kernel(const float* __restri
     for (int c = 0; c < 3; ++c) {
       const float k = ks[p * kc + (kc == 1 ? 0 : c)], b = bc[3 * p + c];
       const float ga = g_alb != nullptr ? g_alb[3 * p + c] : 0.f, gs = g_spec != nullptr ? g_spec[3 * p + c] : 0.f;
-      g_bc[3 * p + c] = __fadd_rn(__fmul_rn(ga, __fsub_rn(1.0f, k)), __fmul_rn(gs, k));
-      gk[c] = __fsub_rn(__fmul_rn(gs, b), __fmul_rn(ga, b));     // d spec / d ks + d albedo / d ks = gs b - ga b
+      // (a sum or difference of two products next to each other is what the compiler fuses into an fma unless told not to: common.h)
+      g_bc[3 * p + c] = vqn_add_rn(vqn_mul_rn(ga, vqn_sub_rn(1.0f, k)), vqn_mul_rn(gs, k));
+      gk[c] = vqn_sub_rn(vqn_mul_rn(gs, b), vqn_mul_rn(ga, b));  // d spec / d ks + d albedo / d ks = gs b - ga b
     }
-    if (kc == 1) g_ks[p] = __fadd_rn(__fadd_rn(gk[0], gk[1]), gk[2]);
+    if (kc == 1) g_ks[p] = vqn_add_rn(vqn_add_rn(gk[0], gk[1]), gk[2]);
     else { g_ks[3 * p] = gk[0]; g_ks[3 * p + 1] = gk[1]; g_ks[3 * p + 2] = gk[2]; }
   }
 }
@@ -56,11 +57,11 @@ __global__ __launch_bounds__(256) void loss_total_kernel(const float* __restrict
   const float vl = vqloss[0], sm = sim != nullptr ? sim[0] : 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float* t = terms + 5 * i;
-    float l = __fadd_rn(__fadd_rn(t[0], t[1]), vl);
-    if (use_chr) l = __fadd_rn(l, t[2]);
-    if (use_smooth) l = __fadd_rn(l, t[3]);
-    if (sim != nullptr) l = __fadd_rn(l, sm);
-    if (use_lambert) l = __fadd_rn(l, t[4]);
+    float l = vqn_add_rn(vqn_add_rn(t[0], t[1]), vl);
+    if (use_chr) l = vqn_add_rn(l, t[2]);
+    if (use_smooth) l = vqn_add_rn(l, t[3]);
+    if (sim != nullptr) l = vqn_add_rn(l, sm);
+    if (use_lambert) l = vqn_add_rn(l, t[4]);
     out[i] = l;
   }
 }
