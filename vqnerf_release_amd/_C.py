@@ -66,6 +66,7 @@ i vqn_meanshift_assign(plpiidppp)""",
     'vqn_mesh_materials.h': """
 l vqn_mesh_label_scratch_bytes(ll)  i vqn_mesh_label_mode(plpliiippplp)  i vqn_mesh_split_count(plplippppp)
 i vqn_mesh_split_emit(pllippppllpppp)""",
+    'vqn_mesh_raster.h': 'i vqn_raster_count(plplpiifipppp)  i vqn_raster_resolve(plpliiiplpppppp)  i vqn_raster_interpolate(ppiiplplipipp)',
     'vqn_image_codec.h': """
 i vqn_jpeg_plan(llliilppi)  i vqn_jpeg_encode(pllliilplplpip)  i vqn_png_plan(llllilppi)  i vqn_png_encode(pllllilplplpip)""",
     'vqn_geometry_eval.h': """
@@ -867,6 +868,100 @@ def mesh_split_emit(triangles, n_verts, n_codes, face_code, block_offset, bitmap
     _call('vqn_mesh_split_emit', nul(triangles), T, V, K, nul(face_code), nul(block_offset), nul(bitmap), nul(word_offset), int(n_faces),
           int(n_slots), nul(face_src), nul(tris_local), nul(vert_src))
     return face_src, tris_local, vert_src
+
+
+# --------------------------------------------------------------------------------------
+# mesh rasteriser (csrc/mesh_raster.hip, include/vqn_mesh_raster.h; geo/mesh_render.py)
+RASTER_TILE = 16                   # pixels per side of a tile (VQN_RASTER_TILE)
+RASTER_SUBPIXEL_BITS = 8           # screen coordinates snap to 1 / 256 pixel (VQN_RASTER_SUBPIXEL_BITS)
+RASTER_MAX_SIDE = 8192             # H and W at most (VQN_RASTER_MAX_SIDE)
+RASTER_COORD_LIMIT = 1 << 23       # |snapped coordinate| below this, in sub-pixel units (VQN_RASTER_COORD_LIMIT)
+RASTER_CHUNK = 256                 # triangles staged in LDS at a time (VQN_RASTER_CHUNK)
+RASTER_STATS = 4                   # counters of dropped triangles (VQN_RASTER_STATS)
+RASTER_MAX_CHANNELS = 16           # attribute channels at most (VQN_RASTER_MAX_CHANNELS)
+RASTER_STAT_NAMES = ('bad_index', 'unusable_vertex', 'zero_area', 'culled')
+
+
+def raster_tiles(H, W):
+    """-> (TY, TX): the tile grid of an H x W image"""
+    return -(-int(H) // RASTER_TILE), -(-int(W) // RASTER_TILE)
+
+
+def _raster_mesh(vertices, triangles, what):
+    T = _mesh_tris(triangles, what)
+    if vertices.dtype != torch.float32 or not vertices.is_contiguous() or vertices.device != triangles.device or vertices.dim() != 2 \
+            or vertices.shape[1] != 3:
+        raise VqnError(f'{what}: expected contiguous float32 vertices [V, 3] on the device of the triangles, got {vertices.dtype} '
+                       f'{tuple(vertices.shape)} on {vertices.device}')
+    return T, vertices.shape[0]
+
+
+def _raster_side(H, W):
+    """the sides an allocation is sized by: a refused H or W allocates for 1 (the call itself refuses, with the reason)"""
+    ok = 1 <= int(H) <= RASTER_MAX_SIDE and 1 <= int(W) <= RASTER_MAX_SIDE
+    return (int(H), int(W)) if ok else (1, 1)
+
+
+def raster_count(vertices, triangles, P, H, W, near, cull, out=None):
+    """vqn_raster_count -> (pverts int32 [V, 3], tile_count int32 [TY * TX], stats int32 [RASTER_STATS]).  P: host floats [3, 4].
+    out: these three, to be written in place."""
+    T, V = _raster_mesh(vertices, triangles, 'raster_count')
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    if P.shape != (3, 4):
+        raise VqnError(f'raster_count: P is a host array [3, 4], got {P.shape}')
+    if out is None:
+        ty, tx = raster_tiles(*_raster_side(H, W))
+        dev = triangles.device
+        out = (torch.empty((V, 3), dtype=torch.int32, device=dev), torch.empty((ty * tx,), dtype=torch.int32, device=dev),
+               torch.empty((RASTER_STATS,), dtype=torch.int32, device=dev))
+    pverts, tile_count, stats = out
+    _call('vqn_raster_count', _ptr(vertices) if V else None, V, _ptr(triangles) if T else None, T, P.ctypes.data, int(H), int(W), float(near),
+          int(cull), _ptr(pverts) if V else None, _ptr(tile_count), _ptr(stats))
+    return pverts, tile_count, stats
+
+
+def raster_resolve(triangles, pverts, H, W, cull, tile_offset, n_pairs, out=None):
+    """vqn_raster_resolve from the exclusive prefix sum of raster_count's tile_count and its total -> (face int32 [H, W], depth f32
+    [H, W], bary f32 [H, W, 3]).  out = (cursor int32 [TY * TX], bin int32 [n_pairs], face, depth, bary): write into these."""
+    T = _mesh_tris(triangles, 'raster_resolve')
+    V = pverts.shape[0]
+    dev = triangles.device
+    if out is None:
+        h, w = _raster_side(H, W)
+        ty, tx = raster_tiles(h, w)
+        out = (torch.empty((ty * tx,), dtype=torch.int32, device=dev), torch.empty((max(int(n_pairs), 0),), dtype=torch.int32, device=dev),
+               torch.empty((h, w), dtype=torch.int32, device=dev), torch.empty((h, w), dtype=torch.float32, device=dev),
+               torch.empty((h, w, 3), dtype=torch.float32, device=dev))
+    cursor, bin_, face, depth, bary = out
+    for t, dt in ((pverts, torch.int32), (tile_offset, torch.int32), (cursor, torch.int32), (bin_, torch.int32), (face, torch.int32),
+                  (depth, torch.float32), (bary, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise VqnError('raster_resolve: pverts, tile_offset, cursor, bin and face are contiguous int32 tensors, depth and bary float32, on '
+                           'the device of the triangles')
+    _call('vqn_raster_resolve', _ptr(triangles) if T else None, T, _ptr(pverts) if V else None, V, int(H), int(W), int(cull), _ptr(tile_offset),
+          int(n_pairs), _ptr(cursor), _ptr(bin_) if bin_.numel() else None, _ptr(face), _ptr(depth), _ptr(bary))
+    return face, depth, bary
+
+
+def raster_interpolate(face, bary, triangles, attr, background, nearest=False, out=None):
+    """vqn_raster_interpolate: attr f32 [V, C] over (face [H, W], bary [H, W, 3]) -> f32 [H, W, C]; background f32 [C] (device)."""
+    T = _mesh_tris(triangles, 'raster_interpolate')
+    dev = triangles.device
+    H, W = face.shape
+    if attr.dim() != 2 or background.dim() != 1 or background.shape[0] != attr.shape[1]:
+        raise VqnError(f'raster_interpolate: attr [V, C] and background [C], got {tuple(attr.shape)} and {tuple(background.shape)}')
+    V, C = attr.shape
+    if out is None:
+        out = torch.empty((H, W, C if 1 <= C <= RASTER_MAX_CHANNELS else 1), dtype=torch.float32, device=dev)
+    for t, dt in ((face, torch.int32), (bary, torch.float32), (attr, torch.float32), (background, torch.float32), (out, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise VqnError('raster_interpolate: face is a contiguous int32 tensor, bary, attr, background and out float32, on the device of the '
+                           'triangles')
+    if bary.numel() != 3 * H * W:
+        raise VqnError(f'raster_interpolate: bary is [H, W, 3] of face [H, W], got {tuple(bary.shape)} and {tuple(face.shape)}')
+    _call('vqn_raster_interpolate', _ptr(face), _ptr(bary), H, W, _ptr(triangles) if T else None, T, _ptr(attr) if V else None, V, C,
+          _ptr(background) if C else None, int(bool(nearest)), _ptr(out))
+    return out
 
 
 # --------------------------------------------------------------------------------------

@@ -9,6 +9,10 @@ csrc/mesh_materials.hip through geo/mesh.py (`smooth_labels`, `split_by_label`).
         outdir/material_mesh.mtl    per code Kd (1 - ks) basecolor, Ks ks basecolor, Pr rough, Ns, illum 2
         outdir/code_%03d.ply        with parts=True: one sub-mesh per used code (or per code of `codes`), its own compact vertex list
         outdir/material_mesh.json   K; per code vertices, faces, surface area, connected regions; changed per smoothing round; dropped faces
+        outdir/material_mesh_view_%03d_{albedo,material,rough}.png
+                                    with views=[(P, H, W), ...]: the mesh drawn from each camera (geo/mesh_render.py): the diffuse colour
+                                    (linear -> sRGB over white), the code of the nearest corner through segmentation.PD_PALETTE (black off
+                                    the mesh: the image segmentation.scores takes against a hand-labelled idx.png), the roughness
 
 The driver takes the model, as decomp/materials.py does (a stage-3 model stands for the stage-2 model it was loaded from)."""
 import json
@@ -66,12 +70,31 @@ def region_counts(triangles, codes, n_codes):
     return torch.zeros((n_codes,), dtype=torch.int64, device=codes.device).scatter_add_(0, c.clamp(0, n_codes - 1), roots.long())
 
 
+def write_views(outdir, vertices, triangles, views, diffuse, label, rough):
+    """material_mesh_view_%03d_{albedo,material,rough}.png per camera (P, H, W) of `views` -> one row per view for the record"""
+    from PIL import Image
+    from vqnerf_release_amd.geo import mesh_render
+    rows = []
+    for i, (P, H, W) in enumerate(views):
+        r = mesh_render.render(vertices, triangles, P, int(H), int(W), colors=diffuse.float(), labels=label, background=1.0)
+        rough_img = mesh_render.interpolate(r, triangles, rough.float(), background=0.0)
+        albedo = torch.where(r['mask'][..., None], _u8(r['color'].reshape(-1, 3)).reshape(int(H), int(W), 3), torch.full_like(r['label'], 255))
+        images = {'albedo': albedo, 'material': r['label'],
+                  'rough': (torch.clamp(rough_img, 0.0, 1.0) * 255.0).to(torch.uint8)}
+        for name, img in images.items():
+            Image.fromarray(img.cpu().numpy()).save(os.path.join(outdir, 'material_mesh_view_%03d_%s.png' % (i, name)))
+        rows.append({'view': i, 'H': int(H), 'W': int(W), 'pixels': int(r['mask'].sum()), 'stats': r['stats']})
+    return rows
+
+
 @torch.no_grad()
-def run(model, mesh, outdir, smooth=2, self_weight=1, branch='vq', parts=False, codes=None, log=None):
+def run(model, mesh, outdir, smooth=2, self_weight=1, branch='vq', parts=False, codes=None, log=None, views=None):
     """-> the record written to outdir/material_mesh.json.  mesh: the path of a PLY file (mesh.read_ply) or (vertices [V, 3] f32,
     triangles [T, 3] int32[, normals [V, 3]]) on the device.  smooth / self_weight: the rounds and the own-code weight of
     mesh.smooth_labels.  branch: 'vq' -- every vertex shows material_rows()[its smoothed code], piecewise constant and equal to the
-    MTL -- or 'main', the continuous heads at the vertex.  parts: also one code_%03d.ply per used code, or per code of `codes`."""
+    MTL -- or 'main', the continuous heads at the vertex.  parts: also one code_%03d.ply per used code, or per code of `codes`.
+    views: a list of cameras (P [3, 4] on the host, H, W) as mesh_render.camera_from_rays gives them: three images per view of the
+    per-vertex values above; None writes nothing more and leaves the record as it is."""
     if branch not in ('vq', 'main'):
         raise ValueError(f"branch is 'vq' or 'main', got {branch!r}")
     if isinstance(mesh, (str, os.PathLike)):
@@ -117,6 +140,8 @@ def run(model, mesh, outdir, smooth=2, self_weight=1, branch='vq', parts=False, 
               'smooth': int(smooth), 'self_weight': int(self_weight), 'changed': changed.tolist(), 'dropped_faces': split['dropped'],
               'codes': [{'code': k, 'vertices': split['vert_count'][k], 'faces': split['face_count'][k], 'area': a, 'regions': r}
                         for k, (a, r) in enumerate(zip(area.tolist(), regions.tolist()))]}
+    if views is not None:
+        record['views'] = write_views(outdir, vertices, triangles, views, diffuse, label, rough)
     with open(os.path.join(outdir, 'material_mesh.json'), 'w') as f:
         json.dump(record, f, indent=1)
     if log is not None:

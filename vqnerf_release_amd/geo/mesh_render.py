@@ -1,0 +1,168 @@
+"""An exported mesh drawn from a dataset's camera, on the device: the tiled rasteriser of csrc/mesh_raster.hip (include/
+vqn_mesh_raster.h) gives per pixel the visible face, its depth and its barycentrics; masks, depth maps, normal, colour and material
+images are gathers over those three buffers.  DESIGN.md section 17.
+
+  camera_from_rays   the pin-hole matrix P [3, 4] of a ray set as `gen_rays_at` returns it, whatever the dataset
+  rasterize          (vertices, triangles, P) -> face, depth, bary, the counters of dropped triangles
+  interpolate        per-vertex attributes over a raster (linear, or the nearest corner for labels)
+  render             mask, depth, normal and, where given, colour and label images; to_uint8 gives their 8-bit forms
+
+Pixel (i, j) is sampled at the screen point (u, v) = (j, i), the point its ray passes through.  There is no clipping: a triangle with
+a vertex behind `near` is dropped and counted.  Object-centric scenes keep the camera outside the object, so nothing is lost there; a
+camera inside the mesh is not supported."""
+import math
+
+import numpy as np
+import torch
+
+from vqnerf_release_amd import _C
+
+REPROJECTION_TOL = 1e-3          # pixels: a ray set that misses its own pixels by more is not a pin-hole camera
+GRID = 16                        # rays per side of the coarse grid camera_from_rays solves over
+
+
+def camera_from_rays(rays_o, rays_v):
+    """rays_o, rays_v [H, W, 3] (pixel (i, j) at [i, j]; one origin) -> P float32 [3, 4] (numpy): P (x, 1) = (j w, i w, w) for a point
+    x on the ray of pixel (i, j), with w > 0 the distance from the camera along its optical axis.  A direct linear solve in float64
+    over a coarse grid of the rays: with P = [M | -M o], M d is proportional to (j, i, 1) for every direction d.  The pixel grid the rays
+    were shot through is whatever the dataset made it (a stretched `resolution_level` grid, a truncated principal point): it is part
+    of M.  Raises ValueError if a sampled ray reprojects more than REPROJECTION_TOL pixels from its own pixel."""
+    H, W = int(rays_v.shape[0]), int(rays_v.shape[1])
+    ii = np.unique(np.round(np.linspace(0, H - 1, min(H, GRID))).astype(np.int64))
+    jj = np.unique(np.round(np.linspace(0, W - 1, min(W, GRID))).astype(np.int64))
+    if len(ii) < 2 or len(jj) < 2:
+        raise ValueError(f'camera_from_rays: a {H} x {W} ray set does not determine a camera')
+    gi, gj = np.meshgrid(ii, jj, indexing='ij')
+    sel = (torch.as_tensor(gi.reshape(-1), device=rays_v.device), torch.as_tensor(gj.reshape(-1), device=rays_v.device))
+    d = rays_v[sel[0], sel[1]].detach().double().cpu().numpy()
+    o = rays_o[sel[0], sel[1]].detach().double().cpu().numpy()
+    if np.abs(o - o[0]).max() > 1e-6 * max(1.0, np.abs(o[0]).max()):
+        raise ValueError('camera_from_rays: the rays do not share one origin')
+    o = o[0]
+    scale = float(max(H, W))                                      # pixel coordinates of order 1 inside the solve
+    u, v = gj.reshape(-1) / scale, gi.reshape(-1) / scale
+    zero = np.zeros_like(d)
+    A = np.concatenate([np.concatenate([d, zero, -u[:, None] * d], 1), np.concatenate([zero, d, -v[:, None] * d], 1)], 0)
+    M = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    M = np.diag([scale, scale, 1.0]) @ M
+    M /= np.linalg.norm(M[2])
+    if (d @ M[2]).sum() < 0:
+        M = -M
+    P = np.concatenate([M, -(M @ o)[:, None]], 1).astype(np.float32)
+    h = (o + 2.0 * d) @ P[:, :3].astype(np.float64).T + P[:, 3].astype(np.float64)
+    with np.errstate(all='ignore'):
+        err = np.maximum(np.abs(h[:, 0] / h[:, 2] - gj.reshape(-1)), np.abs(h[:, 1] / h[:, 2] - gi.reshape(-1)))
+    if not (h[:, 2] > 0).all() or not np.isfinite(err).all() or err.max() > REPROJECTION_TOL:
+        raise ValueError(f'camera_from_rays: not a pin-hole camera: a ray reprojects {float(np.nanmax(err)):.3g} px from its own pixel '
+                         f'(more than {REPROJECTION_TOL})')
+    return P
+
+
+def camera_centre(P):
+    """the point every ray of P passes through, float64 [3]"""
+    P = np.asarray(P, np.float64)
+    return -np.linalg.solve(P[:, :3], P[:, 3])
+
+
+def _mesh(vertices, triangles):
+    return vertices.detach().float().contiguous(), triangles.detach().to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def rasterize(vertices, triangles, P, H, W, near=1e-3, cull=0):
+    """vertices f32 [V, 3] and triangles int32 [T, 3] on the device, P [3, 4] on the host -> dict(face int32 [H, W] (-1: background),
+    depth f32 [H, W] (+inf), bary f32 [H, W, 3] (0), stats {cause: dropped triangles, 'pairs': (triangle, tile) pairs}).  cull: 0, or
+    the sign of the screen-space area (y down) of the triangles to drop.  Two library calls with a prefix sum between them and one
+    read of the host: the total of the pairs and the counters."""
+    vertices, triangles = _mesh(vertices, triangles)
+    pverts, tile_count, stats = _C.raster_count(vertices, triangles, P, H, W, near, cull)
+    ends = torch.cumsum(tile_count, 0, dtype=torch.int64)
+    head = torch.cat([ends[-1:], stats.long()]).cpu().tolist()
+    tile_offset = (ends - tile_count).to(torch.int32)
+    face, depth, bary = _C.raster_resolve(triangles, pverts, H, W, cull, tile_offset, head[0])
+    return dict(face=face, depth=depth, bary=bary, stats=dict(zip(_C.RASTER_STAT_NAMES, head[1:]), pairs=head[0]))
+
+
+@torch.no_grad()
+def interpolate(raster, triangles, attr, background=0.0, nearest=False):
+    """attr [V, C] or [V] (any real dtype, taken as f32) over a raster -> f32 [H, W, C] or [H, W]: (b0 a0 + b1 a1) + b2 a2, or with
+    nearest the attribute of the corner with the largest barycentric (integer labels held as f32).  background: a number or a row [C]
+    for the pixels no face covers."""
+    triangles = triangles.detach().to(torch.int32).contiguous()
+    a = attr.detach().float()
+    flat = a.dim() == 1
+    a = (a[:, None] if flat else a).contiguous()
+    bg = torch.as_tensor(background, dtype=torch.float32, device=a.device).expand(a.shape[1]).contiguous()
+    out = _C.raster_interpolate(raster['face'], raster['bary'], triangles, a, bg, nearest)
+    return out[..., 0] if flat else out
+
+
+def _unit(v):
+    r = v.norm(dim=-1, keepdim=True)
+    return torch.where(r == 0, torch.full_like(v, math.sqrt(1.0 / 3.0)), v / r)
+
+
+def face_normals(vertices, triangles, P):
+    """unit geometric normals f32 [T, 3], each flipped towards the camera of P (a face seen edge-on keeps its winding's side)"""
+    p = vertices[triangles.long()]
+    n = _unit(torch.linalg.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]))
+    eye = torch.as_tensor(camera_centre(P), dtype=torch.float32, device=vertices.device)
+    away = ((eye[None] - p.mean(1)) * n).sum(-1) < 0
+    return torch.where(away[:, None], -n, n)
+
+
+@torch.no_grad()
+def render(vertices, triangles, P, H, W, normals=None, colors=None, labels=None, palette=None, near=1e-3, cull=0, background=1.0):
+    """-> device images {'mask' bool [H, W], 'depth' f32 [H, W] (+inf off the mesh), 'normal' f32 [H, W, 3], 'color' f32 [H, W, 3] (with
+    colors [V, 3], floats in [0, 1] or uint8), 'label' uint8 [H, W, 3] and 'label_index' int64 [H, W] (with labels [V], integers: the
+    nearest corner's, -1 off the mesh; the image through `palette`, default segmentation.PD_PALETTE, black off the mesh), 'stats'}.
+    normal: the interpolated vertex normals re-normalised, or without `normals` the geometric face normal turned towards the camera;
+    (1, 1, 1) / sqrt(3) off the mesh, as validate_image has it.  background: the colour image off the mesh."""
+    vertices, triangles = _mesh(vertices, triangles)
+    r = rasterize(vertices, triangles, P, H, W, near=near, cull=cull)
+    mask = r['face'] >= 0
+    out = {'mask': mask, 'depth': r['depth'], 'stats': r['stats'], 'face': r['face'], 'bary': r['bary']}
+    if normals is not None:
+        n = interpolate(r, triangles, normals)
+    elif triangles.shape[0]:
+        n = face_normals(vertices, triangles, P)[r['face'].clamp(min=0).long()]
+    else:
+        n = torch.zeros((H, W, 3), device=vertices.device)
+    m = mask[..., None].float()
+    out['normal'] = _unit(n) * m + _unit(torch.ones_like(n)) * (1.0 - m)
+    if colors is not None:
+        c = colors.detach()
+        c = c.float() / 255.0 if c.dtype == torch.uint8 else c.float()
+        out['color'] = interpolate(r, triangles, c, background=background)
+    if labels is not None:
+        if palette is None:
+            from vqnerf_release_amd.decomp.nerfactor.util.segmentation import PD_PALETTE as palette
+        lut = torch.as_tensor(np.asarray(palette, np.uint8), device=vertices.device)
+        index = interpolate(r, triangles, labels, background=-1.0, nearest=True).round().long()
+        if int(index.max()) >= lut.shape[0]:
+            raise _C.VqnError(f'render: label {int(index.max())} has no row in a palette of {lut.shape[0]}')
+        out['label_index'] = index
+        out['label'] = torch.where((index >= 0)[..., None], lut[index.clamp(min=0)], torch.zeros_like(lut[:1]))
+    return out
+
+
+def depth_image(depth, mask):
+    """depth scaled to [0, 1] between its smallest and largest value over the mask (0 off the mesh, 0 for a flat or empty view)"""
+    if not bool(mask.any()):
+        return torch.zeros_like(depth)
+    lo, hi = depth[mask].min(), depth[mask].max()
+    span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
+    return torch.where(mask, (depth - lo) / span, torch.zeros_like(depth))
+
+
+def to_uint8(images):
+    """The 8-bit forms of render's images, uint8 device tensors: mask and depth [H, W] (mask * 256 clipped, as validate_image's alpha;
+    depth_image * 255), normal [H, W, 3] (* 128 + 128, as validate_image), color (clamp * 255, as vis._device_images), label as it is."""
+    u8 = lambda t: t.clip(0, 255).to(torch.uint8)
+    out = {'mask': u8(images['mask'].float() * 256), 'depth': u8(depth_image(images['depth'], images['mask']) * 255.0),
+           'normal': u8(images['normal'] * 128 + 128)}
+    if 'color' in images:
+        out['color'] = (torch.clamp(images['color'], 0.0, 1.0) * 255.0).to(torch.uint8)
+    if 'label' in images:
+        out['label'] = images['label']
+    return out

@@ -359,6 +359,113 @@ class Runner:
             mesh_path = geometry_eval.newest_mesh(os.path.join(self.base_exp_dir, 'meshes'))
         return geometry_eval.evaluate(mesh_path, gt_path, out_json=mesh_path[:-4] + '_geometry.json', device=self.device, **kw)
 
+    # ---- the exported mesh drawn from the dataset's cameras (geo/mesh_render.py; no counterpart in the reference) ----
+    def _mesh_for_views(self, mesh_path):
+        """-> (path, vertices, triangles, normals | None, colours uint8 [V, 3] | None) of mesh_path or the newest `meshes/*.ply`"""
+        from vqnerf_release_amd import _C
+        from vqnerf_release_amd.geo import geometry_eval, mesh
+        if mesh_path is None:
+            mesh_path = geometry_eval.newest_mesh(os.path.join(self.base_exp_dir, 'meshes'))
+        try:
+            vertices, triangles, nrm, rgb = mesh.read_ply(mesh_path, device=self.device, extra=('red', 'green', 'blue'))
+            col = torch.stack([rgb[k] for k in ('red', 'green', 'blue')], -1).to(torch.uint8)
+        except _C.VqnError:
+            (vertices, triangles, nrm), col = mesh.read_ply(mesh_path, device=self.device), None
+        if triangles is None:
+            raise _C.VqnError(f'{mesh_path}: a point cloud has no faces to draw')
+        return mesh_path, vertices, triangles, nrm, col
+
+    def _view_camera(self, idx, resolution_level):
+        """-> (P, H, W, rays_o [H, W, 3], rays_d) of view idx at 1 / resolution_level, from the rays the dataset shoots"""
+        from vqnerf_release_amd.geo import mesh_render
+        rays_o, rays_d = self.dataset.gen_rays_at(idx, resolution_level=resolution_level)[:2]
+        H, W, _ = rays_o.shape
+        return mesh_render.camera_from_rays(rays_o, rays_d), H, W, rays_o, rays_d
+
+    @torch.no_grad()
+    def validate_mesh_image(self, idx=-1, resolution_level=-1, mesh_path=None):
+        """View `idx` of the mesh validate_mesh wrote -- mesh_path, or the newest `meshes/{iter:08d}.ply` -- from the camera whose rays
+        `dataset.gen_rays_at` shoots, at 1/resolution_level: `mesh_views/{iter:08d}_0_{idx}_{mask,depth,normal,color}.png` under
+        base_exp_dir (color only if the PLY carries colours; normal from the PLY's normals, else the face normal turned towards the
+        camera; depth scaled between the view's smallest and largest depth over the mask).  The mesh is rasterised on the device
+        (geo/mesh_render.py).  Arrays are in file order (R, G, B), the order the PLY holds its colours in.  Returns {name: uint8 array
+        as written}."""
+        from PIL import Image
+        from vqnerf_release_amd.geo import mesh_render
+        if idx < 0:
+            idx = int(np.random.randint(self.dataset.n_images))
+        if resolution_level < 0:
+            resolution_level = self.validate_resolution_level
+        _, vertices, triangles, nrm, col = self._mesh_for_views(mesh_path)
+        P, H, W = self._view_camera(idx, resolution_level)[:3]
+        images = mesh_render.render(vertices, triangles, P, H, W, normals=nrm, colors=col)
+        imgs = {k: v.cpu().numpy() for k, v in mesh_render.to_uint8(images).items()}
+        out_dir = os.path.join(self.base_exp_dir, 'mesh_views')
+        os.makedirs(out_dir, exist_ok=True)
+        for name, arr in imgs.items():
+            Image.fromarray(np.ascontiguousarray(arr)).save(os.path.join(out_dir, '{:0>8d}_{}_{}_{}.png'.format(self.iter_step, 0, idx, name)))
+        return imgs
+
+    @torch.no_grad()
+    def evaluate_mesh_views(self, views=None, resolution_level=-1, mesh_path=None, volume=False):
+        """A score of the mesh that needs no ground-truth mesh: per view of `views` (default: all) the intersection over union of the
+        mesh's silhouette with the dataset's own mask, `masks[idx, :, :, 0] > 0.5` at the rounded pixel positions the rays of that level
+        pass through (two empty masks score 1).  volume=True adds the same view rendered volumetrically (gen_geo.GeoExtractor.
+        compute_geo): `iou_volume` against its mask, and `depth_abs_mean` / `depth_abs_median` of |mesh depth - depth of its surface
+        point along the optical axis| over the pixels both hit (None where there are none).  Writes `meshes/{iter:08d}_views.json`
+        beside the mesh -- per-view rows, their means, the rasteriser's counters of dropped triangles summed over the views -- and
+        returns the dict.  A dataset without masks raises ValueError."""
+        import json
+        from vqnerf_release_amd.geo import mesh_render
+        masks = getattr(self.dataset, 'masks', None)
+        if masks is None:
+            raise ValueError('evaluate_mesh_views: the dataset has no masks to compare with')
+        if resolution_level < 0:
+            resolution_level = self.validate_resolution_level
+        mesh_path, vertices, triangles, _, _ = self._mesh_for_views(mesh_path)
+        views = list(range(self.dataset.n_images)) if views is None else [int(v) for v in views]
+        extractor = None
+        if volume:
+            from vqnerf_release_amd.geo.gen_geo import GeoExtractor
+            extractor = GeoExtractor(self.renderer, self.dataset.max_radius, use_white_bkgd=self.use_white_bkgd,
+                                     cos_anneal_ratio=self.get_cos_anneal_ratio())
+
+        def iou(a, b):
+            union = (a | b).sum()
+            return float((a & b).sum() / union) if int(union) else 1.0
+
+        rows, stats = [], {}
+        for idx in views:
+            P, H, W, rays_o, rays_d = self._view_camera(idx, resolution_level)
+            r = mesh_render.rasterize(vertices, triangles, P, H, W)
+            mask = r['face'] >= 0
+            full_h, full_w = masks.shape[1:3]
+            ty = torch.round(torch.linspace(0, full_h - 1, H, device=masks.device)).long()
+            tx = torch.round(torch.linspace(0, full_w - 1, W, device=masks.device)).long()
+            gt = (masks[idx, :, :, 0] > 0.5)[ty][:, tx].to(mask.device)
+            row = {'view': idx, 'H': H, 'W': W, 'iou': iou(mask, gt), 'mesh_pixels': int(mask.sum()), 'mask_pixels': int(gt.sum())}
+            if volume:
+                o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+                geo = extractor.compute_geo(o, d, *self.dataset.near_far_from_sphere(o, d), perturb_overwrite=0)
+                vol = geo['mask'].reshape(H, W) > 0
+                Pt = torch.as_tensor(P, device=mask.device)
+                vol_depth = (geo['surf'] @ Pt[2, :3] + Pt[2, 3]).reshape(H, W)
+                both = mask & vol
+                diff = (r['depth'] - vol_depth).abs()[both]
+                row.update({'iou_volume': iou(mask, vol), 'depth_pixels': int(both.sum()),
+                            'depth_abs_mean': float(diff.mean()) if diff.numel() else None,
+                            'depth_abs_median': float(diff.median()) if diff.numel() else None})
+            rows.append(row)
+            for k, v in r['stats'].items():
+                stats[k] = stats.get(k, 0) + int(v)
+        keys = [k for k in ('iou', 'iou_volume', 'depth_abs_mean', 'depth_abs_median') if rows and k in rows[0]]
+        mean = {k: (float(np.mean(vals)) if vals else None) for k in keys for vals in [[r[k] for r in rows if r[k] is not None]]}
+        record = {'mesh': os.path.basename(mesh_path), 'resolution_level': int(resolution_level), 'n_vertices': int(vertices.shape[0]),
+                  'n_faces': int(triangles.shape[0]), 'views': rows, 'mean': mean, 'stats': stats}
+        with open(mesh_path[:-4] + '_views.json', 'w') as f:
+            json.dump(record, f, indent=1)
+        return record
+
     # ---- checkpoints: same keys / file names as nerf_runner.py:210-232 ----
     def save_checkpoint(self):
         ckpt = {'nerf': self.nerf_outside.state_dict(), 'sdf_network_fine': self.sdf_network.state_dict(),
