@@ -141,7 +141,7 @@ def test_foreground_mask_is_the_models(ims, spp):
 def test_bytes_and_sheet(name):
     c = _case(name)
     f32, u8, sheet = c['got']['f32'], c['got']['u8'], c['got']['sheet']
-    want_u8 = (torch.clamp(_C.linear2srgb(f32), 0.0, 1.0) * 255.0).to(torch.uint8)       # the conversion of vis._device_images
+    want_u8 = (torch.clamp(_C.linear2srgb(f32), 0.0, 1.0) * 255.0).to(torch.uint8)       # the conversion of vis.to_uint8
     assert torch.equal(u8, want_u8)
     want_sheet = mb.sheet(u8.cpu().numpy(), c['order'], c['rows'], c['cols'], white_bg=CASES[name][6])
     assert np.array_equal(sheet.cpu().numpy(), want_sheet)

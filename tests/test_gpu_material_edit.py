@@ -352,7 +352,7 @@ def test_run_and_select_views(vq, ref, tmp_path):
     # a size mismatch between a view's files raises
     from PIL import Image
     Image.fromarray(np.zeros((H + 1, W), np.uint8)).save(os.path.join(root, 'batch000000000', 'pred_rough.png'))
-    with pytest.raises(ValueError, match='differ in size'):
+    with pytest.raises(ValueError, match='sizes differ'):
         edit.select_views(root, sel_f)
 
 

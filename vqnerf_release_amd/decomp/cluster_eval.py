@@ -2,7 +2,7 @@
 the paper's segmentation table) on the device scores of decomp/nerfactor/util/segmentation.py.
 
 `evaluate(pred_root, label_root, data_root)` walks the view directories `pred_root/batch<NNNNNNNNN>` that `train_nfr.render_views`
-writes (the same walk and the same PIL loader as decomp/metric_eval.py) and pairs view `...NNN`'s
+writes (the walk, the pairing by view number, the loaders and the size check are decomp/view_tree.py's) and pairs view N's
 
     prediction     pred_root/batch<NNNNNNNNN>/<pred_file>     `embed_map.png`, the code image `util/vis.py` writes
     ground truth   label_root/val_NNN/idx.png                 the hand-labelled image
@@ -25,37 +25,18 @@ The mean-shift baseline's files are written by decomp/meanshift.py (`run`: the c
 rebuilt: the averaging over the paper's five named scenes: a caller loops `evaluate`."""
 import json
 import os
-import re
 
 import numpy as np
 import torch
 
+from vqnerf_release_amd.decomp import view_tree
 from vqnerf_release_amd.decomp.nerfactor.util import segmentation
-
-_LABEL_MODES = ('L', 'I', 'I;16', 'I;16L', 'I;16B')
-
-
-def _load(path):
-    """-> (array, is_label): uint8 [H, W, 3] colours, or integer labels [H, W] for a single-channel integer file"""
-    from PIL import Image
-    with Image.open(path) as im:
-        if im.mode in _LABEL_MODES:
-            return np.asarray(im).astype(np.int32), True
-        return np.asarray(im.convert('RGB')), False
-
-
-def _alpha(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert('RGBA'))[..., 3]
 
 
 def _views(pred_root, label_root, data_root, pred_file):
     out = []
-    for name in sorted(os.listdir(pred_root)):
-        if not re.fullmatch(r'batch\d+', name) or not os.path.isdir(os.path.join(pred_root, name)):
-            continue
-        val = 'val_' + name[-3:]
+    for name in view_tree.view_dirs(pred_root, view_tree.BATCH_VIEWS):
+        val = view_tree.gt_view(name)
         paths = (os.path.join(pred_root, name, pred_file), os.path.join(label_root, val, 'idx.png'), os.path.join(data_root, val, 'rgba.png'))
         if all(os.path.exists(p) for p in paths):
             out.append((name,) + paths)
@@ -73,10 +54,9 @@ def evaluate(pred_root, label_root, data_root, n_views=None, alpha_thres=0.8, pr
         raise ValueError(f'{pred_root}: no view has {pred_file}, idx.png and rgba.png')
     gts, pds, alphas, kinds = [], [], [], set()
     for name, pred_path, idx_path, rgba_path in views:
-        (pd, pd_label), (gt, gt_label), alpha = _load(pred_path), _load(idx_path), _alpha(rgba_path)
-        if pd.shape[:2] != gt.shape[:2] or pd.shape[:2] != alpha.shape:
-            raise ValueError(f'{name}: image sizes differ: {pred_path} {pd.shape[:2]}, {idx_path} {gt.shape[:2]}, alpha {alpha.shape} '
-                             '(resizing is not implemented)')
+        (pd, pd_label), (gt, gt_label) = view_tree.read_colours_or_labels(pred_path), view_tree.read_colours_or_labels(idx_path)
+        alpha = view_tree.read_alpha(rgba_path)
+        view_tree.check_sizes(name, {pred_path: pd.shape[:2], idx_path: gt.shape[:2], 'alpha': alpha.shape})
         if pd_label != gt_label:
             raise ValueError(f'{name}: {pred_path} and {idx_path} must both be colour images or both be single-channel label images')
         kinds.add(gt_label)

@@ -28,7 +28,7 @@ NS_MAX = 1000.0               # the largest specular exponent an MTL holds
 
 
 def _u8(linear):
-    """the project's 8-bit sRGB bytes of linear colours (util/img.py, as vis._device_images quantises them)"""
+    """the project's 8-bit sRGB bytes of linear colours (util/img.py, as vis.to_uint8 quantises them)"""
     return (torch.clamp(imgutil.linear2srgb(linear.float().contiguous()), 0.0, 1.0) * 255.0).to(torch.uint8)
 
 

@@ -3,8 +3,8 @@ clustering of decomp/nerfactor/util/meanshift.py.
 
 `run(pred_scene, data_scene, dst_scene, bandwidth)` reads, for every `train_*` and `val_*` directory under `pred_scene` (the
 continuous model's renderings), `albedo.png` and `spec.png` as RGB and `rough.png` as one channel -- 7 byte features per pixel, each
-read as k / 255. -- and the mask alpha > 0 from `data_scene/<view>/rgba.png` (the loader of decomp/cluster_eval.py).  A size mismatch
-raises; nothing is resized.  The masked pixels of the training views, subsampled to `n_samples` by a seeded permutation on the device
+read as k / 255. -- and the mask alpha > 0 from `data_scene/<view>/rgba.png` (walk, loaders, size check: decomp/view_tree.py).  A size
+mismatch raises; nothing is resized.  The masked pixels of the training views, subsampled to `n_samples` by a seeded permutation on the device
 (the reference's cap of 10,000 answers sklearn's speed on the host; `n_samples=None` keeps every pixel), are clustered; every masked
 pixel of the validation views gets the label of its nearest centre.  Written:
 
@@ -13,15 +13,14 @@ pixel of the validation views gets the label of its nearest centre.  Written:
     dst_scene/batch<NNNNNNNNN>/labels.png         value i as `segmentation.PD_PALETTE[i - 1]` (R, G, B), black for 0
 
 NNN is the number in the view's own name (`val_007` -> `batch000000007`), which is what `cluster_eval` pairs on; the reference
-numbers the views in `os.listdir` order.  The files are then scored by
+numbers the views in the order its directory listing returns them.  The files are then scored by
 `cluster_eval.evaluate(dst_scene, label_root, data_root, pred_file='labels.png')`."""
 import os
-import re
 
 import numpy as np
 import torch
 
-from vqnerf_release_amd.decomp.cluster_eval import _alpha
+from vqnerf_release_amd.decomp import view_tree
 from vqnerf_release_amd.decomp.nerfactor.util import segmentation
 from vqnerf_release_amd.decomp.nerfactor.util.meanshift import MeanShift
 
@@ -30,26 +29,19 @@ FILES = ('albedo.png', 'spec.png', 'rough.png')
 
 def _view(pred_scene, data_scene, view, files):
     """-> (uint8 features [H, W, 7], mask [H, W])"""
-    from PIL import Image
-    planes = []
-    for name, mode in zip(files, ('RGB', 'RGB', 'L')):
-        with Image.open(os.path.join(pred_scene, view, name)) as im:
-            a = np.asarray(im.convert(mode))
-        planes.append(a if a.ndim == 3 else a[..., None])
-    alpha = _alpha(os.path.join(data_scene, view, 'rgba.png'))
-    if any(p.shape[:2] != alpha.shape for p in planes):
-        raise ValueError(f'{view}: image sizes differ: {[p.shape[:2] for p in planes]} under {pred_scene}, alpha {alpha.shape} '
-                         '(resizing is not implemented)')
-    return np.concatenate(planes, axis=-1), alpha > 0
+    paths = [os.path.join(pred_scene, view, name) for name in files]
+    planes = [view_tree.read_image(path, mode) for path, mode in zip(paths, ('RGB', 'RGB', 'L'))]
+    alpha = view_tree.read_alpha(os.path.join(data_scene, view, 'rgba.png'))
+    view_tree.check_sizes(view, dict([(path, p.shape[:2]) for path, p in zip(paths, planes)] + [('alpha', alpha.shape)]))
+    return np.concatenate([p if p.ndim == 3 else p[..., None] for p in planes], axis=-1), alpha > 0
 
 
 def run(pred_scene, data_scene, dst_scene, bandwidth, n_samples=10000, seed=0, files=FILES, device='cuda'):
     """-> {'centers': float64 [K, 7] (host), 'views': the batch directories written, 'n_fit': the pixels clustered, 'n_iter',
     'sample': those pixels, uint8 [n_fit, 7] on the device}.  See the module docstring."""
     device = torch.device(device)
-    names = sorted(v for v in os.listdir(pred_scene) if re.fullmatch(r'(train|val)_\d+', v) and os.path.isdir(os.path.join(pred_scene, v)))
     train, val = [], []
-    for view in names:
+    for view in view_tree.view_dirs(pred_scene, view_tree.SCENE_VIEWS):
         z, mask = _view(pred_scene, data_scene, view, files)
         if view.startswith('train_'):
             train.append(z[mask])
@@ -78,7 +70,7 @@ def run(pred_scene, data_scene, dst_scene, bandwidth, n_samples=10000, seed=0, f
         im = np.zeros(mask.shape, np.uint8)
         if mask.any():
             im[mask] = model.predict(torch.as_tensor(z[mask], device=device)).cpu().numpy().astype(np.uint8) + 1
-        out = 'batch%09d' % int(view.split('_')[1])
+        out = view_tree.batch_view(view_tree.view_number(view))
         os.makedirs(os.path.join(dst_scene, out), exist_ok=True)
         np.save(os.path.join(dst_scene, out, 'labels.npy'), im)
         Image.fromarray(colours[im]).save(os.path.join(dst_scene, out, 'labels.png'))

@@ -2,7 +2,8 @@
 the device metrics of decomp/nerfactor/util/metric.py.
 
 `evaluate(pred_root, gt_root)` walks the view directories `pred_root/batch<NNNNNNNNN>` that `train_nfr.render_views` writes and
-pairs view `...NNN` with the ground-truth directory `gt_root/val_NNN`:
+pairs view number N with the ground-truth directory `gt_root/val_NNN` (the walk, the pairing, the loaders and the size check are
+decomp/view_tree.py's):
 
     group   prediction                                   ground truth
     rgb     pred_rgb.png                                 rgba.png (its colour channels)
@@ -26,22 +27,16 @@ directory layouts, and the `cv2` resize of images whose sizes differ -- a size m
 import glob
 import json
 import os
-import re
 
 import numpy as np
 import torch
 
+from vqnerf_release_amd.decomp import view_tree
 from vqnerf_release_amd.decomp.nerfactor.util import metric
 
 _FIXED = (('rgb', ('pred_rgb.png',), 'rgba.png'), ('kd', ('pred_albedo.png',), 'albedo.png'),
           ('ks', ('pred_ks.png', 'pred_spec.png'), 'metal.png'), ('rough', ('pred_rough.png',), 'rough.png'))
 GROUPS = ('rgb', 'kd', 'ks', 'rough', 'env')
-
-
-def _load(path, mode='RGB'):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert(mode))
 
 
 def _first(dirname, names):
@@ -64,10 +59,8 @@ def _view_pairs(pred_dir, gt_dir, relight_dir):
 
 def _views(pred_root, gt_root, relight_root):
     out = []
-    for name in sorted(os.listdir(pred_root)):
-        if not re.fullmatch(r'batch\d+', name) or not os.path.isdir(os.path.join(pred_root, name)):
-            continue
-        gt_dir = os.path.join(gt_root, 'val_' + name[-3:])
+    for name in view_tree.view_dirs(pred_root, view_tree.BATCH_VIEWS):
+        gt_dir = os.path.join(gt_root, view_tree.gt_view(name))
         if not os.path.exists(os.path.join(gt_dir, 'rgba.png')):
             continue
         relight_dir = os.path.join(relight_root if relight_root is not None else pred_root, name)
@@ -82,11 +75,9 @@ def albedo_scale(views, device):
         p, g = os.path.join(pred_dir, 'pred_albedo.png'), os.path.join(gt_dir, 'albedo.png')
         if not (os.path.exists(p) and os.path.exists(g)):
             continue
-        pred = torch.as_tensor(_load(p), device=device).to(torch.float64) / 255.0
-        gt = torch.as_tensor(_load(g), device=device).to(torch.float64) / 255.0
-        alpha = torch.as_tensor(_load(os.path.join(gt_dir, 'rgba.png'), 'RGBA')[..., 3], device=device).to(torch.float64) / 255.0
-        if pred.shape != gt.shape or pred.shape[:2] != alpha.shape:
-            raise ValueError(f'{p}: image sizes differ ({tuple(pred.shape)}, {tuple(gt.shape)}, alpha {tuple(alpha.shape)})')
+        pred, gt, alpha = (torch.as_tensor(a, device=device).to(torch.float64) / 255.0
+                           for a in (view_tree.read_image(p), view_tree.read_image(g), view_tree.read_alpha(os.path.join(gt_dir, 'rgba.png'))))
+        view_tree.check_sizes(pred_dir, {p: pred.shape[:2], g: gt.shape[:2], 'alpha': alpha.shape})
         ratios.append((gt * alpha[..., None]).sum((0, 1)) / (pred * alpha[..., None]).sum((0, 1)))
     if not ratios:
         raise ValueError('use_scale: no view has both pred_albedo.png and albedo.png')
@@ -104,14 +95,11 @@ def evaluate(pred_root, gt_root, relight_root=None, alpha_thres=0.95, use_scale=
         pairs = _view_pairs(pred_dir, gt_dir, relight_dir)
         if not pairs:
             continue
-        alpha = _load(os.path.join(gt_dir, 'rgba.png'), 'RGBA')[..., 3]
-        pred, gt = [_load(p) for _, p, _ in pairs], [_load(g) for _, _, g in pairs]
-        for (_, p, g), a, b in zip(pairs, pred, gt):
-            if a.shape != b.shape or a.shape[:2] != alpha.shape:
-                raise ValueError(f'{name}: image sizes differ: {p} {a.shape[:2]}, {g} {b.shape[:2]}, alpha {alpha.shape} '
-                                 '(resizing is not implemented)')
-        pred_d = torch.as_tensor(np.stack(pred), device=device)
-        gt_d = torch.as_tensor(np.stack(gt), device=device)
+        alpha = view_tree.read_alpha(os.path.join(gt_dir, 'rgba.png'))
+        images = {path: view_tree.read_image(path) for _, p, g in pairs for path in (p, g)}
+        view_tree.check_sizes(name, dict({path: a.shape[:2] for path, a in images.items()}, alpha=alpha.shape))
+        pred_d = torch.as_tensor(np.stack([images[p] for _, p, _ in pairs]), device=device)
+        gt_d = torch.as_tensor(np.stack([images[g] for _, _, g in pairs]), device=device)
         if scale is not None:
             for i, (group, _, _) in enumerate(pairs):
                 if group == 'kd':

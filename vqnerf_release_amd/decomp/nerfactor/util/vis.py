@@ -13,7 +13,8 @@ pinned buffers on a side stream, and PNG / NPY encoding runs on worker threads (
 pass does not stall the kernels behind ~20 PNG encodes per view.  `writer.flush()` joins.
 
 `vis_batch(png='device')` goes one step further for views whose tensors are on the device: every 8-bit image the host path would
-write is formed there (the same f32 statements in the same order), all 3-channel images of the view are PNG-encoded as one batch and
+write is formed there (`view_files` says which entry becomes which file and `view_image` forms it, for numpy arrays and torch
+tensors alike: one table and one statement, which the host writer and the device writer both loop over), all 3-channel images of the view are PNG-encoded as one batch and
 all 1-channel images as another (util/png.py, csrc/png_encode.hip), and only the compressed bytes and the `.npy` arrays cross to the
 host; the worker threads take the IDAT CRC and write.  The files decode to the same pixels.  `pred_light.png` stays on the host path.
 
@@ -32,9 +33,14 @@ _EMBED_COLOURS = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 0],
                            [128, 0, 0], [0, 128, 0], [0, 0, 128], [128, 128, 0], [128, 0, 128], [0, 128, 128],
                            [255, 128, 128], [128, 255, 128], [128, 128, 255], [255, 255, 128], [255, 128, 255],
                            [128, 255, 255]], np.uint8)           # vq_nfr.py:1141-1146 (handed to cv2.imwrite, i.e. B, G, R)
+_EMBED_LUT = np.concatenate([np.zeros((1, 3), np.uint8), _EMBED_COLOURS[:, ::-1]])       # code -> R, G, B of embed_map.png; 0 = background
 
 
+# ---- the 8-bit images of a view: every statement once, for host arrays (numpy) and device tensors (torch) alike ----------------------
 def to_uint8(arr01):
+    """clip to [0, 1], times 255, truncating cast"""
+    if torch.is_tensor(arr01):
+        return (torch.clamp(arr01, 0.0, 1.0) * 255.0).to(torch.uint8)
     return (np.clip(arr01, 0.0, 1.0) * 255.0).astype(np.uint8)
 
 
@@ -45,24 +51,22 @@ def alpha_blend(a, alpha, b):
     return a * alpha + b * (1.0 - alpha)
 
 
+def composite(v, alpha, white_bg):
+    """v [H,W,3] over the white or black background with alpha [H,W] (already thresholded), in f32, not yet clipped"""
+    xp = torch if torch.is_tensor(v) else np
+    return alpha_blend(v, alpha, xp.ones_like(v) if white_bg else xp.zeros_like(v))
+
+
 def threshold_alpha(alpha, alpha_thres):
     """the stricter compositing alpha of vis_batch (vq_nfr.py:1039-1042): values below the threshold become 0.  numpy or torch."""
-    if torch.is_tensor(alpha):
-        return torch.where(alpha < alpha_thres, torch.zeros_like(alpha), alpha)
-    alpha = alpha.copy()
-    alpha[alpha < alpha_thres] = 0
-    return alpha
+    xp = torch if torch.is_tensor(alpha) else np
+    return xp.where(alpha < alpha_thres, xp.zeros_like(alpha), alpha)
 
 
 def composite_uint8(v, alpha, white_bg):
-    """The 8-bit image vis_batch writes for a colour entry: v [H,W,3] over the white or black background with alpha [H,W] (already
-    thresholded), clipped to [0, 1], times 255, truncated.  One statement for host arrays (`_write_view`) and device tensors
-    (decomp/video.py): the same f32 operations in the same order, so the PNG and the video frame hold the same bytes."""
-    if torch.is_tensor(v):
-        a = alpha[:, :, None]
-        bg = torch.ones_like(v) if white_bg else torch.zeros_like(v)
-        return (torch.clamp(v * a + bg * (1.0 - a), 0.0, 1.0) * 255.0).to(torch.uint8)
-    return to_uint8(alpha_blend(v, alpha, np.ones_like(v) if white_bg else np.zeros_like(v)))
+    """The 8-bit image vis_batch writes for a colour entry, and the frame decomp/video.py encodes: the same f32 operations in the same
+    order (multiply, multiply, add, clamp, times 255, truncating cast), so the PNG and the video frame hold the same bytes."""
+    return to_uint8(composite(v, alpha, white_bg))
 
 
 def relit_names(key, n_maps, probe_names, olat_names, olat_first_n):
@@ -85,11 +89,32 @@ def write_png(path, img_uint8):
 
 def embed_map(embed):
     """Code index image (0 = background, 1..18 = codes) -> the colour map of `_vis_embed`, RGB order of the written file."""
-    out = np.zeros(embed.shape + (3,), np.uint8)
+    if torch.is_tensor(embed):
+        e = torch.round(embed).to(torch.int64)
+        return torch.as_tensor(_EMBED_LUT, device=embed.device)[torch.where((e >= 1) & (e <= 18), e, torch.zeros_like(e))]
     e = np.rint(embed).astype(np.int64)
-    for i in range(1, 19):
-        out[e == i] = _EMBED_COLOURS[i - 1][::-1]
-    return out
+    return _EMBED_LUT[np.where((e >= 1) & (e <= 18), e, 0)]
+
+
+def embed_labels(rgb, device):
+    """The inverse of embed_map: embed_map.png (uint8 [H, W, 3], RGB) -> int32 labels [H * W] on the device, 0 for a colour that is
+    no code's."""
+    px = torch.as_tensor(rgb, device=device).reshape(-1, 3).to(torch.int32)
+    pal = torch.as_tensor(_EMBED_LUT[1:], device=device).to(torch.int32)
+    hit = (px[:, None, :] == pal[None]).all(-1)
+    return torch.where(hit.any(1), hit.to(torch.int32).argmax(1).to(torch.int32) + 1, torch.zeros((), dtype=torch.int32, device=device))
+
+
+def view_hw(to_vis):
+    """(H, W) of a `to_vis` dict, whose 'hw' is [2] or one row per pixel"""
+    hw = to_vis['hw']
+    return tuple(int(x) for x in (hw[0] if hw.ndim == 2 else hw).tolist())
+
+
+def light_names(model):
+    """(probe names, OLAT names, olat_first_n) of a model: the lights its relit images are named after (see relit_names)"""
+    light_res = getattr(model, 'light_res', (16, 32))
+    return list(getattr(model, 'novel_probes', {}) or {}), list(getattr(model, 'novel_olat', {}) or {}), int(np.prod(light_res)) // 2
 
 
 class AsyncWriter:
@@ -176,63 +201,90 @@ def _shape_views(host, hw):
     return out
 
 
-def _write_view(host, event, hw, id_, outdir, mode, white_bg, probe_names, olat_names, olat_first_n, alpha_thres, simp, full_vis_path,
-                pool_submit, scores=None):
+OVER_BG, AS_IS, NORMAL, EMBED = 'over the background', 'as it is', 'normal', 'embed map'
+
+
+def view_files(shapes, mode, simp, full_vis, probe_names, olat_names, olat_first_n):
+    """The files of one view (vq_nfr.py:1043-1110), for {key: image shape} in the order of the dict:
+    ([(file stem, key, index of the light or None, kind)] of the PNGs, [(key, 'outdir' | 'full_vis_path')] of the .npy arrays).
+    The one statement of the per-key rule: the host writer and the device writer both loop over it.  The order of the ladder is
+    behaviour."""
+    images, arrays = [], []
+    for k, shape in shapes.items():
+        if k in ('pred_rgb_olat', 'pred_rgb_probes'):
+            images += [(k + '_' + lname, k, i, OVER_BG) for i, lname in relit_names(k, shape[2], probe_names, olat_names, olat_first_n)]
+        elif k.endswith(('rgb', 'diff')):
+            images.append((k, k, None, OVER_BG))
+        elif k.endswith(('albedo', 'spec', 'rough', 'ks', 'basecolor')):
+            arrays.append((k, 'outdir'))
+            images.append((k, k, None, AS_IS))
+        elif k.endswith(('embed',)):
+            if full_vis:
+                arrays.append((k, 'full_vis_path'))
+            images.append(('embed_map', k, None, EMBED))
+        elif k.endswith(('z',)) and full_vis:                     # (catches '...xyz' too when full_vis is on, as the reference does)
+            arrays.append((k, 'full_vis_path'))
+        elif k.endswith(('xyz',)):
+            arrays.append((k, 'outdir'))
+        elif k.endswith('normal'):
+            images.append((k, k, None, NORMAL))
+        elif k.endswith('edit_mask'):
+            images.append((k, k, None, AS_IS))
+        elif k.endswith(('z',)):
+            pass                                                 # latent codes are only dumped under full_vis
+        elif mode != 'render' and not simp:
+            images.append((k, k, None, AS_IS))
+    return images, arrays
+
+
+def view_image(v, light, kind, alpha, white_bg):
+    """the 8-bit image of one row of view_files' table from the entry v, shaped as an image (numpy or torch); alpha: thresholded"""
+    if light is not None:
+        v = v[:, :, light, :]
+    if kind == EMBED:
+        return embed_map(v)
+    if kind == NORMAL:
+        v = (v + 1.0) / 2.0
+    return to_uint8(v if kind == AS_IS else composite(v, alpha, white_bg))
+
+
+def _scored(mode, simp):
+    """does metadata.json of such a pass carry the scores of gt_rgb against pred_rgb (where both exist)"""
+    return not simp and mode not in ('test', 'render')
+
+
+def write_metadata(outdir, id_, mode, simp, gt_u8, pred_u8, scores):
+    """metadata.json of a view: gt_u8 / pred_u8 the written 8-bit gt_rgb / pred_rgb or None, scores the device's (util/metric.py) or None"""
+    if simp:
+        return
+    meta = {'id': id_}
+    if _scored(mode, simp) and gt_u8 is not None and pred_u8 is not None:
+        meta['psnr'] = psnr_uint8(np.asarray(gt_u8), np.asarray(pred_u8))
+        if scores is not None:                                   # the device's scores of the same two images
+            from vqnerf_release_amd.decomp.nerfactor.util.metric import KEYS
+            meta.update(zip(KEYS, scores.tolist()))
+    with open(os.path.join(outdir, 'metadata.json'), 'w') as f:
+        json.dump(meta, f)
+
+
+def _save_arrays(d, arrays, outdir, full_vis_path, pool_submit):
+    return [pool_submit(np.save, os.path.join(full_vis_path if where == 'full_vis_path' else outdir, k + '.npy'), d[k]) for k, where in arrays]
+
+
+def _write_view(host, event, hw, id_, outdir, mode, white_bg, lights, alpha_thres, simp, full_vis_path, pool_submit, scores=None):
+    """a worker's share of the host path: the view's images formed in numpy, PIL and np.save on the pool"""
     if event is not None:
         event.synchronize()
     d = _shape_views(host, hw)
     os.makedirs(outdir, exist_ok=True)
     alpha = threshold_alpha(d['gt_alpha'], alpha_thres)
-    full_vis = full_vis_path is not None
-    jobs, written = [], {}
-
-    def png(key, arr01):
-        img = to_uint8(arr01)
-        written[key] = img
-        jobs.append(pool_submit(write_png, os.path.join(outdir, key + '.png'), img))
-
-    def over_bg(v):
-        return alpha_blend(v, alpha, np.ones_like(v) if white_bg else np.zeros_like(v))
-
-    def png_over_bg(key, v):
-        img = composite_uint8(v, alpha, white_bg)
-        written[key] = img
-        jobs.append(pool_submit(write_png, os.path.join(outdir, key + '.png'), img))
-
-    for k, v in d.items():
-        if k in ('pred_rgb_olat', 'pred_rgb_probes'):
-            for i, lname in relit_names(k, v.shape[2], probe_names, olat_names, olat_first_n):
-                png_over_bg(k + '_' + lname, v[:, :, i, :])
-        elif k.endswith(('rgb', 'diff')):
-            png_over_bg(k, v)
-        elif k.endswith(('albedo', 'spec', 'rough', 'ks', 'basecolor')):
-            jobs.append(pool_submit(np.save, os.path.join(outdir, k + '.npy'), v))
-            png(k, v)
-        elif k.endswith(('embed',)):
-            if full_vis:
-                jobs.append(pool_submit(np.save, os.path.join(full_vis_path, k + '.npy'), v))
-            jobs.append(pool_submit(write_png, os.path.join(outdir, 'embed_map.png'), embed_map(v)))
-        elif k.endswith(('z',)) and full_vis:                     # (catches '...xyz' too when full_vis is on, as the reference does)
-            jobs.append(pool_submit(np.save, os.path.join(full_vis_path, k + '.npy'), v))
-        elif k.endswith(('xyz',)):
-            jobs.append(pool_submit(np.save, os.path.join(outdir, k + '.npy'), v))
-        elif k.endswith('normal'):
-            png(k, over_bg((v + 1.0) / 2.0))
-        elif k.endswith('edit_mask'):
-            png(k, v)
-        elif k.endswith(('z',)):
-            pass                                                 # latent codes are only dumped under full_vis
-        elif mode != 'render' and not simp:
-            png(k, v)
-    meta = {'id': id_}
-    if not simp:
-        if mode not in ('test', 'render') and 'gt_rgb' in written and 'pred_rgb' in written:
-            meta['psnr'] = psnr_uint8(written['gt_rgb'], written['pred_rgb'])
-            if scores is not None:                               # the device's scores of the same two images (util/metric.py)
-                from vqnerf_release_amd.decomp.nerfactor.util.metric import KEYS
-                meta.update(zip(KEYS, scores.tolist()))
-        with open(os.path.join(outdir, 'metadata.json'), 'w') as f:
-            json.dump(meta, f)
+    images, arrays = view_files({k: v.shape for k, v in d.items()}, mode, simp, full_vis_path is not None, *lights)
+    jobs = _save_arrays(d, arrays, outdir, full_vis_path, pool_submit)
+    written = {}
+    for stem, k, light, kind in images:
+        written[stem] = view_image(d[k], light, kind, alpha, white_bg)
+        jobs.append(pool_submit(write_png, os.path.join(outdir, stem + '.png'), written[stem]))
+    write_metadata(outdir, id_, mode, simp, written.get('gt_rgb'), written.get('pred_rgb'), scores)
     for j in jobs:
         j.result()
 
@@ -248,70 +300,23 @@ def _write_bytes(path, head, stream):
 _png_encoder = None
 
 
-def _device_images(d, mode, white_bg, probe_names, olat_names, olat_first_n, alpha_thres, simp, full_vis_path, outdir):
-    """What `_write_view` writes for the view d = {key: f32 device tensor, shaped as an image}: ([(file name, uint8 device tensor
-    [H,W,3] | [H,W])], [(npy path, key)]), the images formed by the same f32 operations in the same order."""
-    alpha = threshold_alpha(d['gt_alpha'], alpha_thres)
-    full_vis = full_vis_path is not None
-    images, npy = [], []
-
-    def png(key, arr01):
-        images.append((key, (torch.clamp(arr01, 0.0, 1.0) * 255.0).to(torch.uint8)))
-
-    for k, v in d.items():
-        if k in ('pred_rgb_olat', 'pred_rgb_probes'):
-            for i, lname in relit_names(k, v.shape[2], probe_names, olat_names, olat_first_n):
-                images.append((k + '_' + lname, composite_uint8(v[:, :, i, :], alpha, white_bg)))
-        elif k.endswith(('rgb', 'diff')):
-            images.append((k, composite_uint8(v, alpha, white_bg)))
-        elif k.endswith(('albedo', 'spec', 'rough', 'ks', 'basecolor')):
-            npy.append((os.path.join(outdir, k + '.npy'), k))
-            png(k, v)
-        elif k.endswith(('embed',)):
-            if full_vis:
-                npy.append((os.path.join(full_vis_path, k + '.npy'), k))
-            lut = torch.zeros((19, 3), dtype=torch.uint8, device=v.device)
-            lut[1:] = torch.as_tensor(_EMBED_COLOURS[:, ::-1].copy(), device=v.device)
-            e = torch.round(v).to(torch.int64)
-            images.append(('embed_map', lut[torch.where((e >= 1) & (e <= 18), e, torch.zeros_like(e))]))
-        elif k.endswith(('z',)) and full_vis:
-            npy.append((os.path.join(full_vis_path, k + '.npy'), k))
-        elif k.endswith(('xyz',)):
-            npy.append((os.path.join(outdir, k + '.npy'), k))
-        elif k.endswith('normal'):
-            images.append((k, composite_uint8((v + 1.0) / 2.0, alpha, white_bg)))
-        elif k.endswith('edit_mask'):
-            png(k, v)
-        elif k.endswith(('z',)):
-            pass
-        elif mode != 'render' and not simp:
-            png(k, v)
-    return images, npy
-
-
-def _write_view_device(host, event, hw, id_, outdir, mode, simp, npy, files, pool_submit, scores=None):
+def _write_view_device(host, event, hw, id_, outdir, mode, simp, arrays, full_vis_path, files, pool_submit, scores=None):
+    """a worker's share of the device path: the fetched arrays through np.save, the encoded streams into their files"""
     if event is not None:
         event.synchronize()
     pair = [host.pop(k, None) for k in ('_gt_rgb_u8', '_pred_rgb_u8')]
     d = _shape_views(host, hw)
     os.makedirs(outdir, exist_ok=True)
-    jobs = [pool_submit(np.save, path, d[k]) for path, k in npy]
-    jobs += [pool_submit(_write_bytes, os.path.join(outdir, name + '.png'), head, stream) for name, head, stream in files]
-    meta = {'id': id_}
-    if not simp:
-        if mode not in ('test', 'render') and pair[0] is not None and pair[1] is not None:
-            meta['psnr'] = psnr_uint8(pair[0].numpy(), pair[1].numpy())
-            if scores is not None:
-                from vqnerf_release_amd.decomp.nerfactor.util.metric import KEYS
-                meta.update(zip(KEYS, scores.tolist()))
-        with open(os.path.join(outdir, 'metadata.json'), 'w') as f:
-            json.dump(meta, f)
+    jobs = _save_arrays(d, arrays, outdir, full_vis_path, pool_submit)
+    jobs += [pool_submit(_write_bytes, os.path.join(outdir, stem + '.png'), head, stream) for stem, head, stream in files]
+    write_metadata(outdir, id_, mode, simp, pair[0], pair[1], scores)
     for j in jobs:
         j.result()
 
 
 def _vis_batch_device(model, data_dict, hw, id_, outdir, mode, alpha_thres, simp, full_vis_path, writer, scores):
-    """the view's images formed and PNG-encoded on the device; the bytes, the .npy arrays and metadata.json through the writer"""
+    """the view's images formed (view_files, view_image on device tensors) and PNG-encoded on the device; the bytes, the .npy arrays and
+    metadata.json through the writer"""
     global _png_encoder
     from vqnerf_release_amd import _C
     from vqnerf_release_amd.decomp.nerfactor.util.png import PngEncoder
@@ -323,22 +328,20 @@ def _vis_batch_device(model, data_dict, hw, id_, outdir, mode, alpha_thres, simp
             raise _C.VqnError(f"vis_batch(png='device'): entry {k!r} is a {type(v).__name__}, not a device tensor")
         _C.require_device(v, "vis_batch(png='device')")
         d[k] = v.detach().to(torch.float32).reshape(_view_shape(k, tuple(v.shape), hw))
-    probe_names = list(getattr(model, 'novel_probes', {}) or {})
-    olat_names = list(getattr(model, 'novel_olat', {}) or {})
-    light_res = getattr(model, 'light_res', (16, 32))
-    images, npy = _device_images(d, mode, bool(model.white_bg), probe_names, olat_names, int(np.prod(light_res)) // 2, alpha_thres, simp,
-                                 full_vis_path, outdir)
+    alpha = threshold_alpha(d['gt_alpha'], alpha_thres)
+    table, arrays = view_files({k: v.shape for k, v in d.items()}, mode, simp, full_vis_path is not None, *light_names(model))
+    images = [(stem, view_image(d[k], light, kind, alpha, bool(model.white_bg))) for stem, k, light, kind in table]
     if _png_encoder is None:
         _png_encoder = PngEncoder()
     files = []
     for rank in (3, 2):                                          # all [H,W,3] images as one batch, all [H,W] images as another
-        group = [(name, img) for name, img in images if img.dim() == rank]
+        group = [(stem, img) for stem, img in images if img.dim() == rank]
         if group:
             head, streams = _png_encoder.streams(torch.stack([img for _, img in group]))
-            files += [(name, head, s) for (name, _), s in zip(group, streams)]
+            files += [(stem, head, s) for (stem, _), s in zip(group, streams)]
     written = dict(images)
-    fetch = {k: data_dict[k] for _, k in npy}
-    if not simp and mode not in ('test', 'render') and 'gt_rgb' in written and 'pred_rgb' in written:
+    fetch = {k: data_dict[k] for k, _ in arrays}
+    if _scored(mode, simp) and 'gt_rgb' in written and 'pred_rgb' in written:
         fetch['_gt_rgb_u8'], fetch['_pred_rgb_u8'] = written['gt_rgb'], written['pred_rgb']
     if scores is not None:
         fetch['_scores'] = scores
@@ -346,7 +349,7 @@ def _vis_batch_device(model, data_dict, hw, id_, outdir, mode, alpha_thres, simp
     scores = host.pop('_scores', None)
     if full_vis_path is not None:
         os.makedirs(full_vis_path, exist_ok=True)
-    writer.submit(_write_view_device, host, ev, hw, id_, outdir, mode, simp, npy, files, writer.pool.submit, scores)
+    writer.submit(_write_view_device, host, ev, hw, id_, outdir, mode, simp, arrays, full_vis_path, files, writer.pool.submit, scores)
     return writer
 
 
@@ -362,15 +365,10 @@ def vis_light_uint8(light, h=None):
 
 def _device_scores(data_dict, hw, white_bg, alpha_thres):
     """psnr, mse, psnr_luma, ssim, ssim_luma (float64 [5], on the device) of gt_rgb against pred_rgb, both composited as
-    `_write_view` composites the PNGs it writes (the same f32 operations in the same order; the kernel quantises as to_uint8)"""
+    the written PNGs are (`composite`: the same f32 operations in the same order; the kernel quantises as to_uint8)"""
     from vqnerf_release_amd.decomp.nerfactor.util import metric
-    alpha = data_dict['gt_alpha'].detach().to(torch.float32).reshape(-1, 1)
-    alpha = torch.where(alpha < alpha_thres, torch.zeros_like(alpha), alpha)
-    pair = []
-    for k in ('gt_rgb', 'pred_rgb'):
-        v = data_dict[k].detach().to(torch.float32).reshape(-1, 3)
-        bg = torch.ones_like(v) if white_bg else torch.zeros_like(v)
-        pair.append((v * alpha + bg * (1.0 - alpha)).reshape(1, hw[0], hw[1], 3))
+    alpha = threshold_alpha(data_dict['gt_alpha'].detach().to(torch.float32).reshape(hw), alpha_thres)
+    pair = [composite(data_dict[k].detach().to(torch.float32).reshape(hw + (3,)), alpha, white_bg)[None] for k in ('gt_rgb', 'pred_rgb')]
     return metric.image_metrics_raw(pair[0], pair[1]).view(torch.float64)[0, :len(metric.KEYS)]
 
 
@@ -402,25 +400,22 @@ def vis_batch(model, data_dict, outdir, mode='train', light_vis_h=256, alpha_thr
     if mode == 'train':                                          # randomly sampled rays do not form an image
         return writer
     data_dict = dict(data_dict)
-    hw_t = data_dict.pop('hw')
-    hw = tuple(int(x) for x in (hw_t[0] if hw_t.ndim == 2 else hw_t).tolist())
+    hw = view_hw(data_dict)
+    del data_dict['hw']
     id_ = data_dict.pop('id')
     if isinstance(id_, (list, tuple)):
         id_ = id_[0]
     if isinstance(id_, bytes):
         id_ = id_.decode()
     scores = None
-    if metrics and not simp and mode not in ('test', 'render') and all(data_dict.get(k) is not None for k in ('gt_rgb', 'pred_rgb', 'gt_alpha')):
+    if metrics and _scored(mode, simp) and all(data_dict.get(k) is not None for k in ('gt_rgb', 'pred_rgb', 'gt_alpha')):
         scores = _device_scores(data_dict, hw, bool(model.white_bg), alpha_thres)
     if png == 'device':
         return _vis_batch_device(model, data_dict, hw, str(id_), outdir, mode, alpha_thres, simp, full_vis_path, writer, scores)
     host, ev = writer.fetch({k: v for k, v in dict(data_dict, **({} if scores is None else {'_scores': scores})).items() if v is not None})
     scores = host.pop('_scores', None)
-    probe_names = list(getattr(model, 'novel_probes', {}) or {})
-    olat_names = list(getattr(model, 'novel_olat', {}) or {})
-    light_res = getattr(model, 'light_res', (16, 32))
     if full_vis_path is not None:
         os.makedirs(full_vis_path, exist_ok=True)
-    writer.submit(_write_view, host, ev, hw, str(id_), outdir, mode, bool(model.white_bg), probe_names, olat_names,
-                  int(np.prod(light_res)) // 2, alpha_thres, simp, full_vis_path, writer.pool.submit, scores)
+    writer.submit(_write_view, host, ev, hw, str(id_), outdir, mode, bool(model.white_bg), light_names(model), alpha_thres, simp, full_vis_path,
+                  writer.pool.submit, scores)
     return writer

@@ -10,18 +10,18 @@ Streams, all in `outroot`, `<scene>` in front:
   edit     the streams of relight after the material replacement `dst`.  With `selection` (a material_edit.Selection) the rows are picked
            on the device by vq_model.fast_render(edit_select=...) as decomp/edit.run does, the stage-3 model takes the same rows, and
            the masks are written the way the reference's window writes them (outroot/auto_sel/test_{i:03d}.npy, bool [H, W, 3], and
-           auto_sel/dst.json); with `mask_dir` such files are read instead (gen_video.py:219-240) and `dst` defaults to its dst.json.
+           auto_sel/dst.json); with `mask_dir` such files are read instead (gen_video.py:219-240) and `dst` defaults to its dst.json
+           (both directions through decomp/view_tree.py, which edit.run writes through as well).
 A frame of a stream is exactly the 8-bit image `vis_batch` writes for the same key (util/vis.py: composite_uint8 over the configured
 background with the thresholded alpha).  frames=True also writes those per-frame directories through vis_batch: outroot/test_{i:03d}/
 for the stage-3 model and outroot/vq/test_{i:03d}/ for the VQ model (the reference lets the second model overwrite the first one's
 files of the same name).  Not here: the reference's `vq_dcomps` / `gen_comps` modes (train_nfr.render_views over the video dataset
 writes those components), the environment-map inset, audio, and sharding: one AVI is one ordered stream."""
-import json
 import os
 
-import numpy as np
 import torch
 
+from vqnerf_release_amd.decomp import view_tree
 from vqnerf_release_amd.decomp.nerfactor.util import material_edit, mjpeg, vis
 
 MODES = ('recon', 'relight', 'edit')
@@ -50,8 +50,7 @@ def stream_names(scene, mode, probe_names=(), olat_names=(), olat_first_n=0, ref
 
 def frames_of(to_vis, streams, tag, white_bg, alpha_thres=ALPHA_THRES):
     """{stream name: uint8 [H, W, 3] device tensor} of the streams of model `tag` from its `to_vis`"""
-    hw_t = to_vis['hw']
-    H, W = (int(x) for x in (hw_t[0] if hw_t.ndim == 2 else hw_t).tolist())
+    H, W = vis.view_hw(to_vis)
     alpha = vis.threshold_alpha(to_vis['gt_alpha'].detach().to(torch.float32).reshape(H, W), alpha_thres)
     out = {}
     for name, t, key, i in streams:
@@ -61,19 +60,6 @@ def frames_of(to_vis, streams, tag, white_bg, alpha_thres=ALPHA_THRES):
         v = v.reshape(H, W, 3) if i is None else v.reshape(H, W, v.shape[1], 3)[:, :, i, :]
         out[name] = vis.composite_uint8(v, alpha, white_bg)
     return out
-
-
-def _light_names(model):
-    light_res = getattr(model, 'light_res', (16, 32))
-    return list(getattr(model, 'novel_probes', {}) or {}), list(getattr(model, 'novel_olat', {}) or {}), int(np.prod(light_res)) // 2
-
-
-def _read_mask(mask_dir, i, n, device):
-    m = np.load(os.path.join(mask_dir, 'test_{i:03d}.npy'.format(i=i)))
-    if m.size not in (n, 3 * n):
-        raise ValueError(f'{mask_dir}/test_{i:03d}.npy has {m.size} entries, the view has {n} pixels (resizing is not implemented)')
-    rows = m.reshape(n, -1)[:, 0] != 0
-    return torch.as_tensor(rows, device=device).to(torch.uint8)
 
 
 @torch.no_grad()
@@ -91,15 +77,14 @@ def run(model, dataset, outroot, mode, vq_model=None, opt_scale=None, selection=
         if selection is not None and vq_model is None:
             raise ValueError('a selection is made on the codes of the VQ model: give vq_model')
         if dst is None and mask_dir is not None:
-            with open(os.path.join(mask_dir, 'dst.json')) as f:
-                dst = json.load(f)
+            dst = view_tree.read_dst(mask_dir)
         if dst is None:
             raise ValueError('an edit needs the material dst')
     elif selection is not None or mask_dir is not None or dst is not None:
         raise ValueError(f'selection, mask_dir and dst belong to mode edit, not {mode!r}')
     scene = scene or os.path.basename(os.path.normpath(outroot))
     writer = writer or vis.default_writer()
-    probes, olats, first_n = _light_names(model)
+    probes, olats, first_n = vis.light_names(model)
     vq_olat = bool(vq_model is not None and getattr(vq_model, 'render_olat', False))
     streams = stream_names(scene, mode, probes, olats, first_n, ref_olat=False, vq=vq_model is not None and mode != 'recon', vq_olat=vq_olat)
     relit = dict(relight_olat=True, relight_probes=True) if mode != 'recon' else {}
@@ -108,8 +93,7 @@ def run(model, dataset, outroot, mode, vq_model=None, opt_scale=None, selection=
     sink = None
     sel_dir = os.path.join(outroot, 'auto_sel')
     if mode == 'edit' and selection is not None:
-        from vqnerf_release_amd.decomp import edit
-        edit._write_dst(sel_dir, dst)
+        view_tree.write_dst(sel_dir, dst)
     try:
         for i, f in enumerate(files):
             batch = dataset.view(f)
@@ -130,10 +114,11 @@ def run(model, dataset, outroot, mode, vq_model=None, opt_scale=None, selection=
                                                               gen_embed=True, **vq_kw)
                     rows = (pred['edit_mask'][:, 0] != 0).to(torch.uint8)
                     host, ev = writer.fetch({'mask': pred['edit_mask']})
-                    hw = tuple(int(x) for x in batch[1][0].tolist())
-                    writer.submit(edit._save_selection, host, ev, hw, os.path.join(sel_dir, 'test_{i:03d}.npy'.format(i=i)))
+                    writer.submit(view_tree.write_selection, os.path.join(sel_dir, view_tree.frame_view(i) + '.npy'),
+                                  host['mask'].numpy().reshape(vis.view_hw(vq_vis)), ev)
                 else:
-                    rows = _read_mask(mask_dir, i, n, batch[5].device)
+                    rows = view_tree.read_selection(os.path.join(mask_dir, view_tree.frame_view(i) + '.npy'), n)
+                    rows = torch.as_tensor(rows, device=batch[5].device).to(torch.uint8)
                     if vq_model is not None:
                         _, _, _, vq_vis = vq_model.fast_render(batch, mode='test', edit_material=dst, edit_rows=rows, **vq_kw)
                 kw.update(edit_material=dst, edit_rows=rows)
@@ -148,7 +133,7 @@ def run(model, dataset, outroot, mode, vq_model=None, opt_scale=None, selection=
                 sink = mjpeg.VideoSink(outroot, [s[0] for s in streams], (W, H), fps, mjpeg.JpegEncoder(quality=quality), writer=writer)
             sink.push(images)
             if frames:
-                name = 'test_{i:03d}'.format(i=i)
+                name = view_tree.frame_view(i)
                 model.vis_batch(to_vis, os.path.join(outroot, name), mode='test', writer=writer, png=png)
                 if vq_vis is not None:
                     vq_model.vis_batch(vq_vis, os.path.join(outroot, 'vq', name), mode='test', writer=writer, png=png)

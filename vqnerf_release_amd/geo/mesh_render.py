@@ -157,7 +157,7 @@ def depth_image(depth, mask):
 
 def to_uint8(images):
     """The 8-bit forms of render's images, uint8 device tensors: mask and depth [H, W] (mask * 256 clipped, as validate_image's alpha;
-    depth_image * 255), normal [H, W, 3] (* 128 + 128, as validate_image), color (clamp * 255, as vis._device_images), label as it is."""
+    depth_image * 255), normal [H, W, 3] (* 128 + 128, as validate_image), color (clamp * 255, as vis.to_uint8), label as it is."""
     u8 = lambda t: t.clip(0, 255).to(torch.uint8)
     out = {'mask': u8(images['mask'].float() * 256), 'depth': u8(depth_image(images['depth'], images['mask']) * 255.0),
            'normal': u8(images['normal'] * 128 + 128)}
