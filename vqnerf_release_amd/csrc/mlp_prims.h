@@ -503,6 +503,39 @@ __device__ __forceinline__ void init_rows(const f32x4* __restrict__ rows /* tile
   }
 }
 
+// A two-image layer computed IN PLACE by a 4-wave workgroup (neus_points2w_kernel): gemm_tiles2's K loop per output tile (its operand
+// pipeline, its accumulation order per image: init, then the K rows ascending), the epilogue applied to the row quads as they leave
+// the accumulators -- epi(ot, img, rq, v) also issues whatever leaves for memory from there (stash stores) -- and both tiles of the
+// wave (w and w + 4: n_out_tiles <= 8) of both images held in registers until a workgroup barrier says that every wave is done
+// reading the layer's input; then the rows go over it at dst_row0, then a second barrier.  EVERY wave reaches both barriers, with
+// or without a tile.  Two such workgroups share a CU, each in a phase of its own: one's epilogues, barrier waits and VALU-only phases
+// run under the other's K loops.
+template <class Init, class Epi>
+__device__ __forceinline__ void gemm_tiles2_in_place(f32x4* __restrict__ lds, const int img_stride, const KSegs ks,
+                                                     const f32x4* __restrict__ w, const int n_out_tiles, const int wave, const int lane,
+                                                     const int dst_row0, Init init, Epi epi) {
+  f32x4 held0[2][4], held1[2][4], nopre[4];
+  gemm_tiles2<4>(lds, img_stride, ks, w, n_out_tiles, wave, lane, nopre, false, nullptr, init,
+                 [&](int ot, int im, int rq, const f32x16& acc) {          // (im, rq: compile-time at every call)
+                   f32x4 v = {acc[4 * rq], acc[4 * rq + 1], acc[4 * rq + 2], acc[4 * rq + 3]};
+                   epi(ot, im, rq, v);
+                   if (ot == wave) held0[im][rq] = v; else held1[im][rq] = v;
+                 });
+  __syncthreads();
+#pragma unroll
+  for (int im = 0; im < 2; ++im) {
+    if (wave < n_out_tiles) {
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) lds[im * img_stride + (dst_row0 + wave * 4 + rq) * 64 + lane] = held0[im][rq];
+    }
+    if (wave + 4 < n_out_tiles) {
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) lds[im * img_stride + (dst_row0 + (wave + 4) * 4 + rq) * 64 + lane] = held1[im][rq];
+    }
+  }
+  __syncthreads();
+}
+
 // positional encoding feature f of a 3-vector (embedder.py:16-34): [x, sin(2^k x), cos(2^k x)]_k
 __device__ __forceinline__ float posenc_feat(int f, float x0, float x1, float x2) {
   if (f < 3) return f == 0 ? x0 : (f == 1 ? x1 : x2);

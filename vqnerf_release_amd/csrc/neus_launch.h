@@ -62,11 +62,12 @@ static eng::TrainOut neus_train_out(float* const* tensors, const int nL, const i
 // bytes of activation stash one image needs (the fine forms; see vqn_neus_fine_scratch_bytes)
 static int64_t neus_stash_bytes(const SdfDesc& sd) { return (int64_t)(sd.n_lin - 1) * 4 * sd.max_tiles * 1024; }
 
-// Workgroups of a persistent launch over groups of `images` tiles: as many as stay resident (one 512-thread two-image workgroup per CU,
-// two 256-thread one-image ones), no more than there are groups, and no more than `scratch_bytes` holds stashes of `per_img` bytes per
-// image (per_img == 0: the kernel keeps no stash).  0 = the scratch holds not even one workgroup's.
-static long pair_grid(const long n_tiles, const int images, const int64_t per_img, const int64_t scratch_bytes) {
-  return vqn_grid_in_scratch(vqn_grid((n_tiles + images - 1) / images, images == 1 ? 2 : 1), images * per_img, scratch_bytes);
+// Workgroups of a persistent launch over groups of `images` tiles: as many as stay resident (`per_cu` on each CU: one 512-thread
+// multi-image workgroup, two 256-thread ping-pong one-image ones, two to four in-place one-image ones), no more than there are groups,
+// and no more than `scratch_bytes` holds stashes of `per_img` bytes per image (per_img == 0: the kernel keeps no stash).  0 = the
+// scratch holds not even one workgroup's.
+static long pair_grid(const long n_tiles, const int images, const int per_cu, const int64_t per_img, const int64_t scratch_bytes) {
+  return vqn_grid_in_scratch(vqn_grid((n_tiles + images - 1) / images, per_cu), images * per_img, scratch_bytes);
 }
 
 // ---- the backward (vqn_neus_train_bwd, vqn_neus_train_bwd_x3): one pass, two engines.  What differs between them stays in their files:
@@ -150,6 +151,6 @@ static int train_bwd_args(const char* fn, const int32_t* desc, const void* w0, c
   tp->ED = outs[nC + 2];
   for (int l = 1; l <= nL; ++l) tp->UD[l] = outs[nC + 3 + l - 1];
   for (int l = 0; l < nL; ++l) tp->AB[l] = outs[nC + 3 + nL + l];
-  *grid = pair_grid((P + 31) / 32, 2, per_img, scratch_bytes);
+  *grid = pair_grid((P + 31) / 32, 2, 1, per_img, scratch_bytes);
   return VQN_OK;
 }

@@ -8,8 +8,11 @@
 // here the input gradient is an explicit reverse sweep over the same packed weights (transposed
 // packs), reusing the forward activations stashed per tile, so the forward runs once.
 //
-// Execution model: 256-thread workgroups (4 waves), persistent over tiles of 32 points, 2 workgroups
-// per CU.  See mlp_prims.h for the LDS "activation image" and the weight-pack layout.
+// Execution model: persistent workgroups over tiles of 32 points.  Narrow networks: one image per 256-thread workgroup, two
+// workgroups per CU (neus_points_kernel).  Networks of 5 .. 8 tiles: the fine entry runs two in-place images per 256-thread
+// workgroup, two independent workgroups per CU (neus_points2w_kernel); the SDF-only entry four in-place images per 512-thread
+// workgroup (neus_pointsN_kernel); the training forward two ping-pong images per 512-thread workgroup (neus_points2_kernel).
+// See mlp_prims.h for the LDS "activation image" and the weight-pack layout.
 #include "neus_launch.h"
 #include <stdlib.h>
 
@@ -716,6 +719,252 @@ __global__ __launch_bounds__(512, 1) void neus_pointsN_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Workgroup form of the fine kernel (its default for networks of 5 .. 8 tiles; the SDF-only entry measured slower on it than on its
+// four-image form and keeps that: profiles/neus_wg_ab.json):
+// TWO 32-point images per 256-thread workgroup, every layer IN PLACE (gemm_tiles2_in_place), so an image is its E rows
+// (no more than the embedding and the colour extras fill) plus ONE 4 max_tiles-row activation buffer, 37 KB at the shipped shape, and
+// TWO INDEPENDENT workgroups share a CU: the two waves of a SIMD belong to different workgroups in unrelated phases, one's epilogues,
+// barrier waits and VALU-only phases under the other's K loops, where the 512-thread forms above run them in lockstep with the matrix
+// pipe empty.  A weight fragment still feeds both images (8 MFMAs per fetched float4: the L2 weight stream of the two-image form).
+// max_tiles <= 8: a wave holds tiles w and w + 4.  Per point the arithmetic and its order are those of neus_points2_kernel, the
+// embedding-gradient GEMMs included (wte_split_k's K slices: a fresh accumulator per slice, the partials added in slice order in
+// registers -- there are no parking rows in place --, then the E rows).
+struct SmallsW {             // Smalls<2> with the row-dot partials of four waves, not eight
+  float pts[2][96], dirs[2][96], part[2][384], grad[2][96];
+};
+
+__device__ __forceinline__ void wte_in_place(f32x4* __restrict__ lds, const int IS, const int k_row0, const int ng,
+                                             const f32x4* __restrict__ w, const int emb_tiles, const int KS, const int e_row0,
+                                             const int e_rows, const bool accumulate, const int wave, const int lane) {
+  const int gk = (ng + KS - 1) / KS;
+  for (int u = wave; u < 2 * emb_tiles; u += 4) {                     // (tile, image) units; no barrier in here
+    const int t = u % emb_tiles;
+    f32x4* li = lds + (size_t)(u / emb_tiles) * IS;
+    const f32x4* __restrict__ wp = w + (size_t)t * ng * 64 + lane;
+    f32x16 sum;
+    for (int k = 0; k < KS; ++k) {
+      f32x16 acc;
+      init_zero(acc);
+      const int g0 = k * gk, g1 = min(ng, g0 + gk);
+      for (int g = g0; g < g1; g += 8) {
+        f32x4 a[8], b[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int gg = min(g + i, ng - 1);
+          a[i] = wp[gg * 64]; b[i] = li[(k_row0 + gg) * 64 + lane];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          if (g + i < g1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][j], b[i][j], acc, 0, 0, 0);
+          }
+      }
+      if (k == 0) sum = acc; else sum += acc;
+    }
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq)
+      if (t * 4 + rq < e_rows) {                                       // (rows past the last embedding feature are never read)
+        f32x4 v = acc_quad(sum, rq);
+        if (accumulate) v += li[(e_row0 + t * 4 + rq) * 64 + lane];
+        li[(e_row0 + t * 4 + rq) * 64 + lane] = v;
+      }
+  }
+}
+
+template <bool FOLD>
+__global__ __launch_bounds__(256, 2) void neus_points2w_kernel(
+    const SdfDesc sd, const ColDesc cd, const f32x4* __restrict__ wsdf, const f32x4* __restrict__ wcol,
+    const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ zv,
+    const float* __restrict__ pts_direct, const float* __restrict__ dirs_direct, const long P, const int S,
+    f32x4* __restrict__ scratch, float* __restrict__ out_sdf, float* __restrict__ out_grad,
+    float* __restrict__ out_rgb) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
+  const int MT = sd.max_tiles;
+  const int X0 = max(sd.emb_rows, cd.extra_rows);
+  const int IS = (X0 + 4 * MT) * 64;
+  SmallsW* sm = reinterpret_cast<SmallsW*>(lds + (size_t)2 * IS);
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n_lin = sd.n_lin;
+  const int emb_tiles = (sd.emb_feats + 31) >> 5;
+  const int ks_wte = min(8, MT) / emb_tiles;             // wte_split_k's K slices
+  const long n_tiles = (P + 31) >> 5, n_pairs = (n_tiles + 1) >> 1;
+  const size_t per_img = (size_t)(n_lin - 1) * 4 * MT * 64;
+  f32x4* save0 = scratch + (size_t)blockIdx.x * 2 * per_img;
+  const int feat_slot = (n_lin - 2) * 4 * MT;
+  f32x4 nopre[4];
+
+  for (long pair = blockIdx.x; pair < n_pairs; pair += gridDim.x) {
+    // ---------------- points of both tiles, positional encoding -> E rows ----------------
+    if (tid < 64) {
+      const int im = tid >> 5, t = tid & 31;
+      load_point<true>(((2 * pair + im) << 5) + t, P, S, rays_o, rays_d, zv, pts_direct, dirs_direct, sm->pts[im] + t * 3, sm->dirs[im] + t * 3);
+    }
+    __syncthreads();
+    for (int u = wave; u < 2 * sd.emb_rows; u += 4) {                 // (image, embedding row) units
+      const int im = u / sd.emb_rows, r = u - im * sd.emb_rows;
+      const float xs = sm->pts[im][p * 3 + 0] * sd.scale, ys = sm->pts[im][p * 3 + 1] * sd.scale, zs = sm->pts[im][p * 3 + 2] * sd.scale;
+      f32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = emb_feat(row_feat(r, h, j), sd.emb_feats, xs, ys, zs);
+      lds[(size_t)im * IS + (E0 + r) * 64 + lane] = v;
+    }
+    __syncthreads();
+
+    // ---------------- SDF hidden layers, in place ----------------
+    for (int l = 0; l < n_lin - 1; ++l) {
+      const LayerDesc L = sd.layers[l];
+      const KSegs ks = (l == 0) ? KSegs{E0, sd.emb_rows, 0, 0}
+                                : KSegs{X0, 4 * sd.layers[l - 1].n_out_tiles, E0, (l == sd.skip) ? sd.emb_rows : 0};
+      const bool do_save = l < n_lin - 2;
+      const f32x4* bp = wsdf + L.b_off;
+      gemm_tiles2_in_place(lds, IS, ks, wsdf + L.w_off, L.n_out_tiles, wave, lane, X0,
+                           [&](int ot, int, f32x16& acc) { init_bias(bp, ot, lane, acc); },
+                           [&](int ot, int im, int rq, f32x4& v) {
+#pragma unroll
+                             for (int j = 0; j < 4; ++j) v[j] = act_fwd<ACT_SOFTPLUS100>(v[j]);
+                             if (do_save) st_stream(save0 + (size_t)im * per_img + (size_t)l * 4 * MT * 64 + (ot * 4 + rq) * 64 + lane, v);
+                           });
+    }
+    const int hid_rows = 4 * sd.layers[n_lin - 2].n_out_tiles;
+
+    // ---------------- last layer: sdf row (VALU dot, per image) [+ feature rows, or the folded colour input, -> stash] ----------------
+    for (int im = 0; im < 2; ++im) rowdot<1>(lds + (size_t)im * IS, X0, hid_rows, wsdf + sd.last_w_off, sm->part[im], wave, lane);
+    if (sd.layers[n_lin - 1].n_out_tiles > 0) {
+      const LayerDesc L = sd.layers[n_lin - 1];
+      const f32x4* bp = FOLD ? wcol + cd.reserved2 : wsdf + L.b_off;
+      gemm_tiles2<4>(lds, IS, KSegs{X0, hid_rows, 0, 0}, FOLD ? wcol + cd.reserved1 : wsdf + L.w_off,
+                     FOLD ? cd.layers[0].n_out_tiles : L.n_out_tiles, wave, lane, nopre, false, nullptr,
+                     [&](int ot, int, f32x16& acc) { init_bias(bp, ot, lane, acc); },
+                     [&](int ot, int im, int rq, const f32x16& acc) {
+                       st_stream(save0 + (size_t)im * per_img + (size_t)feat_slot * 64 + (ot * 4 + rq) * 64 + lane, acc_quad(acc, rq));
+                     });
+    }
+    __syncthreads();
+    if (tid < 64) {
+      const int im = tid >> 5, t = tid & 31;
+      const long pt = ((2 * pair + im) << 5) + t;
+      if (pt < P) out_sdf[pt] = sdf_raw(sm->part[im], t, sd.last_b_off, sd.last_bias, wsdf) / sd.scale;
+    }
+    // ---------------- reverse sweep: d sdf / d x ----------------
+    // G_pre(last hidden) = w_sdf_row (.) act'(h), in place
+    for (int im = 0; im < 2; ++im) {
+      f32x4* li = lds + (size_t)im * IS;
+      for (int r0 = wave; r0 < hid_rows; r0 += 32) {            // 8 rows per pass: all fetches first (one L2 round trip per pass)
+        f32x4 v[8], wv[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const int r = min(r0 + 4 * c, hid_rows - 1);
+          v[c] = li[(X0 + r) * 64 + lane];
+          wv[c] = wsdf[sd.last_w_off + r * 2 + h];
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (r0 + 4 * c < hid_rows) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[c][j] = wv[c][j] * act_bwd_from_out<ACT_SOFTPLUS100>(v[c][j]);
+            li[(X0 + r0 + 4 * c) * 64 + lane] = v[c];
+          }
+      }
+    }
+    __syncthreads();
+    for (int l = n_lin - 2; l >= 1; --l) {
+      const LayerDesc L = sd.layers[l];
+      if (l == sd.skip)                                 // the embedding part of the skip layer reads the same rows: before they are overwritten
+        wte_in_place(lds, IS, X0, 4 * L.n_out_tiles, wsdf + L.wTE_off, emb_tiles, ks_wte, E0, sd.emb_rows, false, wave, lane);
+      f32x4 hv[2][4];                                   // the stashed forward activations of a tile: requested before its K loop
+      gemm_tiles2_in_place(lds, IS, KSegs{X0, 4 * L.n_out_tiles, 0, 0}, wsdf + L.wT_off, sd.layers[l - 1].n_out_tiles, wave, lane, X0,
+                           [&](int ot, int im, f32x16& acc) {
+                             const f32x4* sv = save0 + (size_t)im * per_img + (size_t)(l - 1) * 4 * MT * 64;
+#pragma unroll
+                             for (int rq = 0; rq < 4; ++rq) hv[im][rq] = ld_stream(sv + (ot * 4 + rq) * 64 + lane);
+                             init_zero(acc);
+                           },
+                           [&](int, int im, int rq, f32x4& v) {
+#pragma unroll
+                             for (int j = 0; j < 4; ++j) v[j] *= act_bwd_from_out<ACT_SOFTPLUS100>(hv[im][rq][j]);
+                           });
+    }
+    wte_in_place(lds, IS, X0, 4 * sd.layers[0].n_out_tiles, wsdf + sd.layers[0].wTE_off, emb_tiles, ks_wte, E0, sd.emb_rows, sd.skip >= 1,
+                 wave, lane);
+    __syncthreads();
+    // chain through the embedding: thread (image, point pp, component c) sums its features in a fixed order
+    if (tid < 192) {
+      const int im = tid / 96, r = tid - 96 * im, pp = r & 31, c = r >> 5;
+      const f32x4* li = lds + (size_t)im * IS;
+      const float g = embed_chain([&](int f) { return lds_feat(li, E0, f, pp); }, c, sd.multires, sm->pts[im] + pp * 3, sd.scale);
+      sm->grad[im][pp * 3 + c] = g;
+      const long pt = ((2 * pair + im) << 5) + pp;
+      if (pt < P) out_grad[pt * 3 + c] = g;
+    }
+    __syncthreads();
+    if (cd.n_lin == 0) continue;          // SDFNetwork.gradient(): no colour net (the same for every wave: a kernel argument)
+
+    // ---------------- colour network, in place ----------------
+    const int feat_rows = 4 * sd.layers[n_lin - 1].n_out_tiles;
+    for (int im = 0; im < 2; ++im) {
+      f32x4* li = lds + (size_t)im * IS;
+      const float px = sm->pts[im][p * 3 + 0], py = sm->pts[im][p * 3 + 1], pz = sm->pts[im][p * 3 + 2];
+      const float dx = sm->dirs[im][p * 3 + 0], dy = sm->dirs[im][p * 3 + 1], dz = sm->dirs[im][p * 3 + 2];
+      for (int r = wave; r < cd.extra_rows; r += 4) {
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          v[j] = col_extra_feat(row_feat(r, h, j), px, py, pz, dx, dy, dz, sm->grad[im] + p * 3, cd.n_view_feats, cd.extra_feats);
+        li[(E0 + r) * 64 + lane] = v;
+      }
+      const f32x4* sv = save0 + (size_t)im * per_img + (size_t)feat_slot * 64;
+      for (int r0 = wave; r0 < (FOLD ? 0 : feat_rows); r0 += 32) {          // (unfolded) the feature rows back from the stash
+        f32x4 v[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = ld_stream(sv + min(r0 + 4 * c, feat_rows - 1) * 64 + lane);
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (r0 + 4 * c < feat_rows) li[(X0 + r0 + 4 * c) * 64 + lane] = v[c];
+      }
+    }
+    __syncthreads();
+    int in_rows = feat_rows;
+    auto relu = [&](int, int, int, f32x4& v) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = act_fwd<ACT_RELU>(v[j]);
+    };
+    if (FOLD) {                                   // colour layer 0 = relu(P + Wc0[:, extras] . extras): K = the extras rows only
+      const LayerDesc L = cd.layers[0];
+      gemm_tiles2_in_place(lds, IS, KSegs{E0, cd.extra_rows, 0, 0}, wcol + cd.reserved3, L.n_out_tiles, wave, lane, X0,
+                           [&](int ot, int im, f32x16& acc) {
+                             const f32x4* pp = save0 + (size_t)im * per_img + (size_t)feat_slot * 64 + ot * 256 + lane;
+#pragma unroll
+                             for (int rq = 0; rq < 4; ++rq) {
+                               const f32x4 v = ld_stream(pp + rq * 64);
+                               acc[4 * rq + 0] = v[0]; acc[4 * rq + 1] = v[1]; acc[4 * rq + 2] = v[2]; acc[4 * rq + 3] = v[3];
+                             }
+                           },
+                           relu);
+      in_rows = 4 * L.n_out_tiles;
+    }
+    for (int l = FOLD ? 1 : 0; l < cd.n_lin - 1; ++l) {
+      const LayerDesc L = cd.layers[l];
+      const f32x4* bp = wcol + L.b_off;
+      gemm_tiles2_in_place(lds, IS, KSegs{X0, in_rows, E0, l == 0 ? cd.extra_rows : 0}, wcol + L.w_off, L.n_out_tiles, wave, lane, X0,
+                           [&](int ot, int, f32x16& acc) { init_bias(bp, ot, lane, acc); }, relu);
+      in_rows = 4 * L.n_out_tiles;
+    }
+    for (int im = 0; im < 2; ++im) rowdot<3>(lds + (size_t)im * IS, X0, in_rows, wcol + cd.last_w_off, sm->part[im], wave, lane);
+    __syncthreads();
+    if (tid < 192) {
+      const int im = tid / 96, r = tid - 96 * im, pp = r & 31, o = r >> 5;
+      const float v = rgb_out(sm->part[im], pp, o, cd.last_b_off, cd.last_bias[o], cd.squeeze_out, wcol);
+      const long pt = ((2 * pair + im) << 5) + pp;
+      if (pt < P) out_rgb[pt * 3 + o] = v;
+    }
+    __syncthreads();
+  }
+}
+
+
 int check_sdf_desc(const SdfDesc& d) {
   if (d.n_lin < 2 || d.n_lin > VQN_MAX_SDF_LAYERS) return 1;
   if (d.max_tiles < 1 || d.max_tiles > 16) return 2;
@@ -761,8 +1010,24 @@ int sdf_images(const SdfDesc& sd) {
 template <int NIMG>
 int launch_sdf_images(const char* fn, const SdfDesc& sd, const f32x4* ws, const float* rays_o, const float* rays_d, const float* z,
                       const float* pts, const int64_t P, const int S, float* out_sdf, void* stream) {
-  return vqn_launch(fn, neus_pointsN_kernel<NIMG>, pair_grid((P + 31) / 32, NIMG, 0, 0), 512, lds_bytes_sdf<NIMG>(sd), stream, sd, ws,
+  return vqn_launch(fn, neus_pointsN_kernel<NIMG>, pair_grid((P + 31) / 32, NIMG, 1, 0, 0), 512, lds_bytes_sdf<NIMG>(sd), stream, sd, ws,
                     rays_o, rays_d, z, pts, (long)P, S, out_sdf);
+}
+
+// ---- the workgroup form (neus_points2w_kernel): two in-place two-image workgroups on a CU
+size_t lds_bytes_wg(const SdfDesc& sd, const int extra_rows) {
+  return (size_t)2 * ((sd.emb_rows > extra_rows ? sd.emb_rows : extra_rows) + 4 * sd.max_tiles) * 1024 + sizeof(SmallsW);
+}
+
+// The workgroup form for this network?  Where the two-image form would run, max_tiles <= 8 and the LDS holds two workgroups; else the
+// two-image form as before.  VQN_NEUS_FORM=images (read once) keeps the two-image form everywhere: for A/B runs and tests, like
+// VQN_NEUS_SDF_IMAGES and VQN_NEUS_TILE32 (which keeps the ping-pong one-image form).
+bool use_wg_form(const SdfDesc& sd, const int extra_rows) {
+  static const bool images = [] {
+    const char* e = getenv("VQN_NEUS_FORM");
+    return e != nullptr && strcmp(e, "images") == 0;
+  }();
+  return !images && use_two_images(sd.max_tiles) && sd.max_tiles <= 8 && 2 * lds_bytes_wg(sd, extra_rows) <= 160 * 1024;
 }
 
 bool extras_rows_ok(const ColDesc& cd) { return cd.extra_rows >= 1 && cd.extra_rows <= 8; }
@@ -784,11 +1049,11 @@ extern "C" int vqn_neus_sdf_points(const int32_t* sdf_desc, const float* wbuf_sd
   if (images == 4) return launch_sdf_images<4>(__func__, sd, ws, rays_o, rays_d, z, pts, P, S, out_sdf, stream);
   if (images == 3) return launch_sdf_images<3>(__func__, sd, ws, rays_o, rays_d, z, pts, P, S, out_sdf, stream);
   if (images == 2)
-    return vqn_launch(__func__, neus_points2_kernel<false>, pair_grid(n_tiles, 2, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws,
+    return vqn_launch(__func__, neus_points2_kernel<false>, pair_grid(n_tiles, 2, 1, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws,
                       nullptr, rays_o, rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
   const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  return vqn_launch(__func__, neus_points_kernel<false>, pair_grid(n_tiles, 1, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o, rays_d,
+  return vqn_launch(__func__, neus_points_kernel<false>, pair_grid(n_tiles, 1, 2, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o, rays_d,
                     z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr);
 }
 
@@ -815,7 +1080,7 @@ extern "C" int vqn_neus_train_fwd(const int32_t* sdf_desc, const float* wbuf_sdf
                   outf_tiles >= sd.layers[sd.n_lin - 1].n_out_tiles, "tile counts");   // (outf_tiles = ceil(F / 32): with F - 1 no multiple of 32
                   // that is the features' own tile count, and row 32 outf_tiles -- padding past the last feature -- is not stored, see the kernel)
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
-  const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
+  const long grid = pair_grid((P + 31) / 32, 2, 1, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
   return vqn_launch(__func__, neus_points2_kernel<true, true>, grid, 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd,
                     reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr, nullptr, pts, dirs,
@@ -834,7 +1099,9 @@ extern "C" int64_t vqn_neus_fine_scratch_bytes(const int32_t* sdf_desc) {
 #ifdef VQN_DIAG_STASH_ROT
   return (int64_t)VQN_DIAG_STASH_ROT * vqn_num_cus() * 2 * neus_stash_bytes(sd);
 #else
-  return (int64_t)vqn_num_cus() * 2 * neus_stash_bytes(sd);
+  // (two images per workgroup; the workgroup form keeps two workgroups on a CU, the others one: never less than before.  Asked
+  // without a colour net, so for the narrowest E rows: room for the workgroup form whenever some launch on this network may take it)
+  return (int64_t)vqn_num_cus() * (use_wg_form(sd, 0) ? 4 : 2) * neus_stash_bytes(sd);
 #endif
 }
 
@@ -855,13 +1122,21 @@ extern "C" int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_s
   const int64_t per_img = neus_stash_bytes(sd);
   const f32x4* ws = reinterpret_cast<const f32x4*>(wbuf_sdf);
   const f32x4* wc = reinterpret_cast<const f32x4*>(wbuf_col);
+  if (use_wg_form(sd, cd.extra_rows)) {
+    const bool fold = cd.n_lin != 0 && cd.reserved1 > 0;
+    const long grid = pair_grid(n_tiles, 2, 2, per_img, scratch_bytes);
+    VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
+    return vqn_launch(__func__, fold ? neus_points2w_kernel<true> : neus_points2w_kernel<false>, grid, 256,
+                      lds_bytes_wg(sd, cd.extra_rows), stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S,
+                      reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);
+  }
   if (use_two_images(sd.max_tiles)) {
     const bool fold = cd.n_lin != 0 && cd.reserved1 > 0;
 #ifdef VQN_DIAG_STASH_ROT
-    const long grid = pair_grid(n_tiles, 2, 0, 0);
+    const long grid = pair_grid(n_tiles, 2, 1, 0, 0);
     VQN_CHECK_ARG((int64_t)VQN_DIAG_STASH_ROT * grid * 2 * per_img <= scratch_bytes, "diag build: scratch must hold ROT regions per workgroup");
 #else
-    const long grid = pair_grid(n_tiles, 2, per_img, scratch_bytes);
+    const long grid = pair_grid(n_tiles, 2, 1, per_img, scratch_bytes);
 #endif
     VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
     return vqn_launch(__func__, fold ? neus_points2_kernel<true, false, true> : neus_points2_kernel<true>, grid, 512, lds_bytes<2>(sd.max_tiles),
@@ -870,7 +1145,7 @@ extern "C" int vqn_neus_fine_points(const int32_t* sdf_desc, const float* wbuf_s
   }
   const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  const long grid = pair_grid(n_tiles, 1, per_img, scratch_bytes);
+  const long grid = pair_grid(n_tiles, 1, 2, per_img, scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
   return vqn_launch(__func__, neus_points_kernel<true>, grid, 256, lds, stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P, S,
                     reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);

@@ -421,11 +421,11 @@ extern "C" int vqn_neus_sdf_points_f16s(const int32_t* sdf_desc, const float* wb
   const long n_tiles = (P + 31) / 32;
   const f32x4* ws = reinterpret_cast<const f32x4*>(wbuf_sdf);
   if (use_two_images(sd.max_tiles))
-    return vqn_launch(__func__, neus_points_f16s_kernel<false, 2>, pair_grid(n_tiles, 2, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd,
+    return vqn_launch(__func__, neus_points_f16s_kernel<false, 2>, pair_grid(n_tiles, 2, 1, 0, 0), 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd,
                       ws, nullptr, rays_o, rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr);
   const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  return vqn_launch(__func__, neus_points_f16s_kernel<false, 1>, pair_grid(n_tiles, 1, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o,
+  return vqn_launch(__func__, neus_points_f16s_kernel<false, 1>, pair_grid(n_tiles, 1, 2, 0, 0), 256, lds, stream, sd, cd, ws, nullptr, rays_o,
                     rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr);
 }
 
@@ -443,14 +443,14 @@ extern "C" int vqn_neus_fine_points_f16s(const int32_t* sdf_desc, const float* w
   const f32x4* ws = reinterpret_cast<const f32x4*>(wbuf_sdf);
   const f32x4* wc = reinterpret_cast<const f32x4*>(wbuf_col);
   if (use_two_images(sd.max_tiles)) {
-    const long grid = pair_grid(n_tiles, 2, neus_stash_bytes(sd), scratch_bytes);
+    const long grid = pair_grid(n_tiles, 2, 1, neus_stash_bytes(sd), scratch_bytes);
     VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
     return vqn_launch(__func__, neus_points_f16s_kernel<true, 2>, grid, 512, lds_bytes<2>(sd.max_tiles), stream, sd, cd, ws, wc, rays_o, rays_d,
                       z, pts, dirs, (long)P, S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);
   }
   const size_t lds = lds_bytes<1>(sd.max_tiles);
   VQN_CHECK_SHAPE(lds <= 160 * 1024, "network too wide for LDS");
-  const long grid = pair_grid(n_tiles, 1, neus_stash_bytes(sd), scratch_bytes);
+  const long grid = pair_grid(n_tiles, 1, 2, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
   return vqn_launch(__func__, neus_points_f16s_kernel<true, 1>, grid, 256, lds, stream, sd, cd, ws, wc, rays_o, rays_d, z, pts, dirs, (long)P,
                     S, reinterpret_cast<f32x4*>(scratch), out_sdf, out_grad, out_rgb);

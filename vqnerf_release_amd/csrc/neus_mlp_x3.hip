@@ -449,7 +449,7 @@ extern "C" int vqn_neus_sdf_points_x3(const int32_t* sdf_desc, const float* wbuf
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
   return vqn_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<false, 2> : neus_points_x3_kernel<false, 1>,
-                    pair_grid((P + 31) / 32, 2, 0, 0), 512, lds2, stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), nullptr, rays_o,
+                    pair_grid((P + 31) / 32, 2, 1, 0, 0), 512, lds2, stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), nullptr, rays_o,
                     rays_d, z, pts, nullptr, (long)P, S, nullptr, out_sdf, nullptr, nullptr, TrainOut{});
 }
 
@@ -465,7 +465,7 @@ extern "C" int vqn_neus_fine_points_x3(const int32_t* sdf_desc, const float* wbu
   if (rc != VQN_OK || P == 0) return rc;
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
-  const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
+  const long grid = pair_grid((P + 31) / 32, 2, 1, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
   return vqn_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2> : neus_points_x3_kernel<true, 1>, grid, 512, lds2, stream, sd,
                     cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), rays_o, rays_d, z, pts, dirs,
@@ -496,7 +496,7 @@ extern "C" int vqn_neus_train_fwd_x3(const int32_t* sdf_desc, const float* wbuf_
   for (int i = 0; i < n_tensors; ++i) VQN_CHECK_ARG(tensors[i] != nullptr, "null tensor pointer");
   const size_t lds2 = lds_bytes_x3(sd.max_tiles);
   VQN_CHECK_SHAPE(lds2 <= 160 * 1024, "network too wide for LDS");
-  const long grid = pair_grid((P + 31) / 32, 2, neus_stash_bytes(sd), scratch_bytes);
+  const long grid = pair_grid((P + 31) / 32, 2, 1, neus_stash_bytes(sd), scratch_bytes);
   VQN_CHECK_ARG(grid >= 1, "scratch too small (see vqn_neus_fine_scratch_bytes)");
   return vqn_launch(__func__, x3_nacc() == 2 ? neus_points_x3_kernel<true, 2, true> : neus_points_x3_kernel<true, 1, true>, grid, 512, lds2,
                     stream, sd, cd, reinterpret_cast<const f32x4*>(wbuf_sdf), reinterpret_cast<const f32x4*>(wbuf_col), nullptr, nullptr,
