@@ -67,6 +67,9 @@ i vqn_meanshift_assign(plpiidppp)""",
 l vqn_mesh_label_scratch_bytes(ll)  i vqn_mesh_label_mode(plpliiippplp)  i vqn_mesh_split_count(plplippppp)
 i vqn_mesh_split_emit(pllippppllpppp)""",
     'vqn_mesh_raster.h': 'i vqn_raster_count(plplpiifipppp)  i vqn_raster_resolve(plpliiiplpppppp)  i vqn_raster_interpolate(ppiiplplipipp)',
+    'vqn_mesh_rays.h': """
+i vqn_rays_grid_plan(pplfp)  i vqn_rays_count(plplpppp)  i vqn_rays_bin(plplpplpppp)  i vqn_rays_cast(plpplppppplpppp)
+i vqn_rays_occluded(plpplppppplpp)  i vqn_rays_light_visibility(plpplppplpifipp)""",
     'vqn_image_codec.h': """
 i vqn_jpeg_plan(llliilppi)  i vqn_jpeg_encode(pllliilplplpip)  i vqn_png_plan(llllilppi)  i vqn_png_encode(pllllilplplpip)""",
     'vqn_geometry_eval.h': """
@@ -961,6 +964,138 @@ def raster_interpolate(face, bary, triangles, attr, background, nearest=False, o
         raise VqnError(f'raster_interpolate: bary is [H, W, 3] of face [H, W], got {tuple(bary.shape)} and {tuple(face.shape)}')
     _call('vqn_raster_interpolate', _ptr(face), _ptr(bary), H, W, _ptr(triangles) if T else None, T, _ptr(attr) if V else None, V, C,
           _ptr(background) if C else None, int(bool(nearest)), _ptr(out))
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# mesh ray caster (csrc/mesh_rays.hip, include/vqn_mesh_rays.h; geo/mesh_rays.py)
+RAYS_MAX_AXIS = 1024               # cells per axis at most (VQN_RAYS_MAX_AXIS)
+RAYS_MAX_CELLS = 1 << 24           # cells at most (VQN_RAYS_MAX_CELLS)
+RAYS_STATS = 3                     # counters of dropped triangles (VQN_RAYS_STATS)
+RAYS_MARGIN_INV = 16               # a triangle's box is widened by 1 / 16 cell before it is binned (VQN_RAYS_MARGIN_INV)
+RAYS_PACKED_FLOATS = 12            # floats of a packed triangle (VQN_RAYS_PACKED_FLOATS)
+RAYS_MAX_LIGHTS = 65536            # lights of rays_light_visibility at most (VQN_RAYS_MAX_LIGHTS)
+RAYS_TILE = 64                     # points x lights of the staged tile (VQN_RAYS_TILE)
+RAYS_MIN_DIR_LOG2 = -60            # a ray is cast only if max |d component| >= 2^-60 (VQN_RAYS_MIN_DIR_LOG2)
+RAYS_LANES_POINTS = 0              # a wave holds 64 neighbouring points of one light (VQN_RAYS_LANES_POINTS)
+RAYS_LANES_LIGHTS = 1              # a wave holds 64 lights of one point (VQN_RAYS_LANES_LIGHTS)
+RAYS_STAT_NAMES = ('bad_index', 'nonfinite_vertex', 'zero_area')
+
+
+def rays_grid_plan(lo, hi, n_tris, cell=None):
+    """The grid over a mesh of n_tris triangles whose finite vertices have the bounding box lo .. hi (three floats each; host only)
+    -> GeomGrid.  cell: its size, None for the default.  A plan the library refuses raises ValueError with its reason."""
+    grid = GeomGrid()
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float32), np.ascontiguousarray(hi, dtype=np.float32)
+    if lo.shape != (3,) or hi.shape != (3,):
+        raise VqnError(f'rays_grid_plan: lo and hi are three floats each, got {lo.shape} and {hi.shape}')
+    rc = lib().vqn_rays_grid_plan(lo.ctypes.data, hi.ctypes.data, int(n_tris), 0.0 if cell is None else float(cell), ctypes.addressof(grid))
+    if rc != 0:
+        raise ValueError(lib().vqn_last_error().decode())
+    return grid
+
+
+def _rays_cells(grid):
+    """the cells an allocation is sized by: a grid the call itself refuses allocates for 1"""
+    d = [int(x) for x in grid.dims]
+    ok = all(1 <= x <= RAYS_MAX_AXIS for x in d) and d[0] * d[1] * d[2] == int(grid.cells) <= RAYS_MAX_CELLS
+    return int(grid.cells) if ok else 1
+
+
+def _rays_tensors(what, dev, i32=(), f32=(), u8=()):
+    for ts, dt in ((i32, torch.int32), (f32, torch.float32), (u8, torch.uint8)):
+        for t in ts:
+            if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise VqnError(f'{what}: expected a contiguous {dt} tensor on {dev}, got {t.dtype} contiguous={t.is_contiguous()} on {t.device}')
+
+
+def rays_count(vertices, triangles, grid, out=None):
+    """vqn_rays_count -> (cell_count int32 [cells], stats int32 [RAYS_STATS]).  out: these two, to be written in place."""
+    T, V = _raster_mesh(vertices, triangles, 'rays_count')
+    dev = triangles.device
+    if out is None:
+        out = (torch.empty((_rays_cells(grid),), dtype=torch.int32, device=dev), torch.empty((RAYS_STATS,), dtype=torch.int32, device=dev))
+    cell_count, stats = out
+    _rays_tensors('rays_count', dev, i32=(cell_count, stats))
+    _call('vqn_rays_count', _ptr(vertices) if V else None, V, _ptr(triangles) if T else None, T, ctypes.addressof(grid), _ptr(cell_count),
+          _ptr(stats))
+    return cell_count, stats
+
+
+def rays_bin(vertices, triangles, grid, cell_offset, n_pairs, out=None):
+    """vqn_rays_bin from the exclusive prefix sum of rays_count's cell_count and its total -> (bin int32 [n_pairs], packed f32
+    [T, RAYS_PACKED_FLOATS]).  out = (cursor int32 [cells], bin, packed): write into these."""
+    T, V = _raster_mesh(vertices, triangles, 'rays_bin')
+    dev = triangles.device
+    if out is None:
+        out = (torch.empty((_rays_cells(grid),), dtype=torch.int32, device=dev), torch.empty((max(int(n_pairs), 0),), dtype=torch.int32, device=dev),
+               torch.empty((T, RAYS_PACKED_FLOATS), dtype=torch.float32, device=dev))
+    cursor, bin_, packed = out
+    _rays_tensors('rays_bin', dev, i32=(cell_offset, cursor, bin_), f32=(packed,))
+    _call('vqn_rays_bin', _ptr(vertices) if V else None, V, _ptr(triangles) if T else None, T, ctypes.addressof(grid), _ptr(cell_offset),
+          int(n_pairs), _ptr(cursor), _ptr(bin_) if bin_.numel() else None, _ptr(packed) if T else None)
+    return bin_, packed
+
+
+def _rays_scene(what, packed, grid, cell_offset, n_pairs, bin_):
+    """checks of a built grid -> its leading arguments"""
+    if packed.dim() != 2 or packed.shape[1] != RAYS_PACKED_FLOATS or not packed.is_cuda:
+        raise VqnError(f'{what}: packed is a device tensor [T, {RAYS_PACKED_FLOATS}], got {tuple(packed.shape)} on {packed.device}')
+    _rays_tensors(what, packed.device, i32=(cell_offset, bin_), f32=(packed,))
+    T = packed.shape[0]
+    return (_ptr(packed) if T else None, T, ctypes.addressof(grid), _ptr(cell_offset), int(n_pairs), _ptr(bin_) if bin_.numel() else None)
+
+
+def _rays_rays(what, dev, o, d, tmin, tmax):
+    _rays_tensors(what, dev, f32=(o, d, tmin, tmax))
+    n = tmin.numel()
+    if o.dim() != 2 or o.shape != (n, 3) or d.shape != (n, 3) or tmax.numel() != n:
+        raise VqnError(f'{what}: o, d [n, 3] and tmin, tmax [n], got {tuple(o.shape)}, {tuple(d.shape)}, {tuple(tmin.shape)}, {tuple(tmax.shape)}')
+    return n
+
+
+def rays_cast(packed, grid, cell_offset, n_pairs, bin_, o, d, tmin, tmax, out=None):
+    """vqn_rays_cast -> (face int32 [n], t f32 [n], uv f32 [n, 2]).  out: these three, to be written in place."""
+    scene = _rays_scene('rays_cast', packed, grid, cell_offset, n_pairs, bin_)
+    dev = packed.device
+    n = _rays_rays('rays_cast', dev, o, d, tmin, tmax)
+    if out is None:
+        out = (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
+               torch.empty((n, 2), dtype=torch.float32, device=dev))
+    face, t, uv = out
+    _rays_tensors('rays_cast', dev, i32=(face,), f32=(t, uv))
+    nul = lambda x: _ptr(x) if n else None
+    _call('vqn_rays_cast', *scene, nul(o), nul(d), nul(tmin), nul(tmax), n, nul(face), nul(t), nul(uv))
+    return face, t, uv
+
+
+def rays_occluded(packed, grid, cell_offset, n_pairs, bin_, o, d, tmin, tmax, out=None):
+    """vqn_rays_occluded -> uint8 [n]"""
+    scene = _rays_scene('rays_occluded', packed, grid, cell_offset, n_pairs, bin_)
+    dev = packed.device
+    n = _rays_rays('rays_occluded', dev, o, d, tmin, tmax)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.uint8, device=dev)
+    _rays_tensors('rays_occluded', dev, u8=(out,))
+    nul = lambda x: _ptr(x) if n else None
+    _call('vqn_rays_occluded', *scene, nul(o), nul(d), nul(tmin), nul(tmax), n, nul(out))
+    return out
+
+
+def rays_light_visibility(packed, grid, cell_offset, n_pairs, bin_, points, normals, lights, bias, lanes=RAYS_LANES_POINTS, out=None):
+    """vqn_rays_light_visibility: points, normals f32 [n, 3], lights f32 [L, 3] -> f32 [n, L]"""
+    scene = _rays_scene('rays_light_visibility', packed, grid, cell_offset, n_pairs, bin_)
+    dev = packed.device
+    _rays_tensors('rays_light_visibility', dev, f32=(points, normals, lights))
+    if points.dim() != 2 or points.shape[1] != 3 or normals.shape != points.shape or lights.dim() != 2 or lights.shape[1] != 3:
+        raise VqnError(f'rays_light_visibility: points, normals [n, 3] and lights [L, 3], got {tuple(points.shape)}, {tuple(normals.shape)}, '
+                       f'{tuple(lights.shape)}')
+    n, L = points.shape[0], lights.shape[0]
+    if out is None:
+        out = torch.empty((n, L if 1 <= L <= RAYS_MAX_LIGHTS else 1), dtype=torch.float32, device=dev)
+    _rays_tensors('rays_light_visibility', dev, f32=(out,))
+    nul = lambda x: _ptr(x) if n else None
+    _call('vqn_rays_light_visibility', *scene, nul(points), nul(normals), n, _ptr(lights) if L else None, L, float(bias), int(lanes), nul(out))
     return out
 
 

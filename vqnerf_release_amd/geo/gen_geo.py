@@ -95,6 +95,20 @@ class GeoExtractor:
         lvis[fg] = lvis_fg
         return lvis
 
+    @torch.no_grad()
+    def compute_vis_mesh(self, surf, normal, mask, mesh_rays, bias=None):
+        """The question of compute_vis asked of the exported mesh (geo/mesh_rays.MeshRays) instead of the network: surf, normal [R,3],
+        mask [R,1] -> lvis [R, L] for the same lights, 1 where the light is in front of the point and the segment from the point (lifted
+        by `bias` along its normal; None: the MeshRays default) to the light meets no triangle, else 0.  Zeros on background pixels and
+        back-lit lights, the layout compute_vis returns; one fused kernel, no ray is stored."""
+        dev = surf.device
+        L = self.lxyz.shape[1]
+        fg = mask[:, 0] > 0
+        lvis = torch.zeros(surf.shape[0], L, device=dev)
+        if bool(fg.any()):
+            lvis[fg] = mesh_rays.light_visibility(surf[fg].contiguous(), normal[fg].contiguous(), self.lxyz[0].to(dev), bias)
+        return lvis
+
     @staticmethod
     def save_view(view_dir, H, W, geo, lvis=None):
         """The on-disk contract of the decomp loaders (shape_unit.py:68-78): xyz.npy, normal.npy [H,W,3], lvis.npy [H,W,L]
@@ -126,28 +140,32 @@ class GeoExtractor:
 
     @torch.no_grad()
     def extract_views(self, dataset, scene_out_dir, is_train=True, resolution_level=1, num_p=None, p_i=None, no_vis=False,
-                      alpha_thres=0.5, log=None):
+                      alpha_thres=0.5, log=None, mesh=None):
         """The per-view loop of gen_geo.py:126-180: geometry buffers (+ light visibility unless `no_vis`) of every view of
         `dataset` into `scene_out_dir/{train,val}_{idx:03d}/`.  Views are independent, so multi-GPU extraction is a split of
         the view range with no collective -- `--num_p / --p_i` in the reference (README.md:45-53), by default rank /
         world_size of the process group here.  Training views use the ground-truth mask for visibility (the decomp stage
-        trains on it) and alpha_thres 0.5; validation views use the predicted mask at `alpha_thres`.  Returns the indices done."""
+        trains on it) and alpha_thres 0.5; validation views use the predicted mask at `alpha_thres`.  Returns the indices done.
+        mesh: None, or the exported mesh -- a geo/mesh_rays.MeshRays, a (vertices, triangles) pair or the path of a PLY: the light
+        visibility then comes from compute_vis_mesh (rays against the mesh) instead of compute_vis; everything else is the same."""
         return self._extract(dataset, scene_out_dir, 'train_' if is_train else 'val_', resolution_level, num_p, p_i, no_vis,
-                             0.5 if is_train else alpha_thres, gt_mask=is_train, metadata=None, log=log)
+                             0.5 if is_train else alpha_thres, gt_mask=is_train, metadata=None, log=log, mesh=mesh)
 
     @torch.no_grad()
-    def extract_video(self, videoset, scene_out_dir, resolution_level=1, num_p=None, p_i=None, no_vis=False, alpha_thres=0.5, log=None):
+    def extract_video(self, videoset, scene_out_dir, resolution_level=1, num_p=None, p_i=None, no_vis=False, alpha_thres=0.5, log=None,
+                      mesh=None):
         """The loop of the reference's geo/NeuS-ours2/gen_video.py:134-179 over a camera path (models/videoset.py): the files of
         `save_view` into `scene_out_dir/test_{idx:03d}/`, plus `metadata.json` {focal, cx, cy, cam_transform_mat} (:165-169), which
         is what decomp/nerfactor/datasets/video_nfr.py makes its rays from.  There is no ground truth along a path: visibility is
         always computed on the predicted mask at `alpha_thres`.  Same split of the view range and the same skipping of finished
-        views as extract_views (a view counts as finished only with its metadata.json)."""
+        views as extract_views (a view counts as finished only with its metadata.json), and the same `mesh`."""
         return self._extract(videoset, scene_out_dir, 'test_', resolution_level, num_p, p_i, no_vis, alpha_thres, gt_mask=False,
-                             metadata=videoset.metadata, log=log)
+                             metadata=videoset.metadata, log=log, mesh=mesh)
 
-    def _extract(self, dataset, scene_out_dir, prefix, resolution_level, num_p, p_i, no_vis, alpha_thres, gt_mask, metadata, log):
+    def _extract(self, dataset, scene_out_dir, prefix, resolution_level, num_p, p_i, no_vis, alpha_thres, gt_mask, metadata, log, mesh=None):
         """views p_i * ceil(n / num_p) ... of `dataset` that are not finished yet -> their directories; gt_mask: visibility on the set's
-        own masks where it has them at the rendered size; metadata: idx -> the dict of the view's metadata.json, or None for no file"""
+        own masks where it has them at the rendered size; metadata: idx -> the dict of the view's metadata.json, or None for no file;
+        mesh: see extract_views (its grid is built once, at the first view that needs it)"""
         import json
         import math
         from vqnerf_release_amd import parallel
@@ -177,7 +195,12 @@ class GeoExtractor:
                 gt = getattr(dataset, 'masks', None)
                 if gt_mask and gt is not None and tuple(gt.shape[1:3]) == (H, W):
                     mask = (gt[idx, :, :, :1].reshape(-1, 1) > 0).float().to(o.device)
-                lvis = self.compute_vis(geo['surf'], geo['normal'], mask)
+                if mesh is None:
+                    lvis = self.compute_vis(geo['surf'], geo['normal'], mask)
+                else:
+                    from vqnerf_release_amd.geo.mesh_rays import as_mesh_rays
+                    mesh = as_mesh_rays(mesh, o.device)
+                    lvis = self.compute_vis_mesh(geo['surf'], geo['normal'], mask, mesh)
             self.save_view(view_dir, H, W, geo, lvis)
             done.append(idx)
             if log is not None:

@@ -407,6 +407,40 @@ class Runner:
         return imgs
 
     @torch.no_grad()
+    def validate_mesh_visibility(self, idx=-1, resolution_level=-1, mesh_path=None, bias=None):
+        """The light visibility of view `idx` of the mesh, with no network call: the surface points are the rasteriser's own depth
+        along the dataset's rays, the normals the face normals turned towards the camera, the lights those of gen_geo.GeoExtractor,
+        the rays cast against the mesh (geo/mesh_rays.py).  Writes `mesh_views/{iter:08d}_0_{idx}_lvis.png`, the mean over the
+        lights with save_view's `lvis.png` scaling u8(clip(mean * 256, 0, 255)) -- an ambient-occlusion picture of the mesh, black
+        off it.  Returns the uint8 array [H, W] as written."""
+        from PIL import Image
+        from vqnerf_release_amd.decomp.brdf.renderer import gen_light_xyz
+        from vqnerf_release_amd.geo import mesh_render
+        from vqnerf_release_amd.geo.mesh_rays import MeshRays
+        if idx < 0:
+            idx = int(np.random.randint(self.dataset.n_images))
+        if resolution_level < 0:
+            resolution_level = self.validate_resolution_level
+        _, vertices, triangles, _, _ = self._mesh_for_views(mesh_path)
+        P, H, W, rays_o, rays_d = self._view_camera(idx, resolution_level)
+        vertices, triangles = vertices.float().contiguous(), triangles.to(torch.int32).contiguous()
+        r = mesh_render.rasterize(vertices, triangles, P, H, W)
+        fg = (r['face'] >= 0).reshape(-1)
+        mean = torch.zeros(H * W, device=vertices.device)
+        if bool(fg.any()):
+            o, d = rays_o.reshape(-1, 3)[fg].to(vertices.device).float(), rays_d.reshape(-1, 3)[fg].to(vertices.device).float()
+            axis = torch.as_tensor(P[2, :3], device=vertices.device)                 # depth is the distance along the optical axis
+            points = o + d * (r['depth'].reshape(-1)[fg] / (d @ axis))[:, None]
+            normals = mesh_render.face_normals(vertices, triangles, P)[r['face'].reshape(-1)[fg].long()]
+            lights = torch.tensor(gen_light_xyz(16, 32)[0].reshape(-1, 3), dtype=torch.float32, device=vertices.device)
+            mean[fg] = MeshRays(vertices, triangles).light_visibility(points, normals, lights, bias).mean(-1)
+        img = np.clip(mean.reshape(H, W).cpu().numpy() * 256, 0, 255).astype(np.uint8)
+        out_dir = os.path.join(self.base_exp_dir, 'mesh_views')
+        os.makedirs(out_dir, exist_ok=True)
+        Image.fromarray(img).save(os.path.join(out_dir, '{:0>8d}_{}_{}_lvis.png'.format(self.iter_step, 0, idx)))
+        return img
+
+    @torch.no_grad()
     def evaluate_mesh_views(self, views=None, resolution_level=-1, mesh_path=None, volume=False):
         """A score of the mesh that needs no ground-truth mesh: per view of `views` (default: all) the intersection over union of the
         mesh's silhouette with the dataset's own mask, `masks[idx, :, :, 0] > 0.5` at the rounded pixel positions the rays of that level
