@@ -1575,19 +1575,33 @@ def geom_reduce(d2, idx, n_ref, thresholds=(), q_normals=None, ref_normals=None)
 
 # --------------------------------------------------------------------------------------
 # reflectance path (csrc/mlp_chain.hip, csrc/brdf_shade.hip)
-def mlp_chain_fwd(desc, wbuf, x, out_widths, mode='f32'):
+def mlp_chain_fwd(desc, wbuf, x, out_widths, mode='f32', outs=None, lds=None):
     """Run a layer program (decomp/packing.py) over x [N, in_stride]; returns one [N, w] tensor per output slot.
-    mode 'f16s': the split-precision kernel (program and pack must come from ChainBuilder(mode='f16s'))."""
+    mode 'f16s': the split-precision kernel (program and pack must come from ChainBuilder(mode='f16s')).
+    outs / lds: the caller's own output buffers, one per slot ([N, ld] float32 device tensors), and their leading dimensions
+    (lds[i] >= out_widths[i]; default: the widths); they are returned as given."""
     assert mode in ('f32', 'f16s')
     entry = 'vqn_mlp_chain_fwd' if mode == 'f32' else 'vqn_mlp_chain_fwd_f16s'
     _f32c(wbuf, 'wbuf'); _f32c(x, 'x')
     d, dp = _i32(desc)
     N = x.shape[0]
     assert x.shape[1] == int(d[8]), (x.shape, int(d[8]))
-    outs = [torch.empty((N, w), dtype=torch.float32, device=x.device) for w in out_widths]
+    lds = list(out_widths) if lds is None else list(lds)
+    assert len(lds) == len(out_widths) <= 4 and all(ld >= w for ld, w in zip(lds, out_widths)), (lds, out_widths)
+    if outs is None:
+        outs = [torch.empty((N, ld), dtype=torch.float32, device=x.device) for ld in lds]
+        if lds != list(out_widths):
+            outs = [o[:, :w] for o, w in zip(outs, out_widths)]
+        ptrs = [o.data_ptr() for o in outs]
+    else:
+        assert len(outs) == len(out_widths)
+        for i, (o, ld) in enumerate(zip(outs, lds)):
+            _f32c(o, f'outs[{i}]')
+            assert o.numel() >= N * ld, (i, tuple(o.shape), N, ld)
+        ptrs = [o.data_ptr() for o in outs]
     args = []
     for i in range(4):
-        args += [_ptr(outs[i]), out_widths[i]] if i < len(outs) else [None, 0]
+        args += [ptrs[i], lds[i]] if i < len(outs) else [None, 0]
     _call(entry, dp, _ptr(wbuf), _ptr(x), N, *args)
     return outs
 
